@@ -6,7 +6,19 @@ Step = one RBloomFilter.contains(Collection) pass (M/RedissonBloomFilter.java:15
 batch of 100M synthetic 32-byte keys (50% previously added) against ONE 2^32-bit filter with
 k = 7, keys resident in HBM when the timed region starts.
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3|c4|c5] [--legs c1,c3,c4,c5|none]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py --full [--workload c2|c3|c4|c5] [--legs c1,c3,c4,c5|none] ...
+
+A plain run does what the headline figure needs and no more: set up the filter and the keys, W
+warm-up steps, K timed steps, the outputs of the last timed step to DIR if asked for, one JSON
+line.  Everything else this file measures or checks runs under --full only: the legs, the CPU
+baseline, the request rooflines (gather / stream peaks measured in the same run, PMC traffic), the
+direct-kernel A/B, the non-power-of-two filter, the host-buffer path, the timed setup add, C3's add
+half, the replica digest of a one-rank run.
+
+--dump-outputs DIR writes what a caller of the timed call holds after the last timed step as
+DIR/<name>.npy (float64; OUTPUTS below names them per workload).  The inputs are seeded, so two
+builds run with the same arguments can be compared file by file.
 
 Multi-GPU: one rank per GPU.  The driver launches N > 1 through torch.distributed.run; when
 WORLD_SIZE is unset and --gpus N > 1, bench.py launches those N ranks itself (a child
@@ -22,7 +34,8 @@ Every rank asserts WORLD_SIZE == --gpus.
 RBX_BENCH_SHARED_GPU=1 rehearses N ranks on one GPU (gloo for the bench's own collectives and
 for the C4 register exchange: RCCL needs a GPU per rank).
 
-Printed JSON (rank 0, one line): `roofline` for the C2 contains call (the partitioned pipeline,
+Printed JSON (rank 0, one line; the request, PMC and cpu_baseline fields with --full only):
+`roofline` for the C2 contains call (the partitioned pipeline,
 HIP events on the launch stream), its PMC traffic per access class (profiles/traffic.json from
 tools/profile_round.sh), a streaming-floor roofline of the same call, and `cpu_baseline`: the
 multithreaded C restatement (oracle/rbx_oracle_mt.c) on the host cores on C2 and C1 samples.
@@ -52,9 +65,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: legs, CPU baseline, request rooflines, "
+                        "direct-kernel A/B, non-power-of-two filter, host-buffer path, timed adds")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step to DIR/<name>.npy (float64)")
     p.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5"])
     p.add_argument("--legs", default="c1,c3,c4,c5",
-                   help="legs carried in the C2 line: comma list of c1,c3,c4,c5 or 'none'")
+                   help="with --full, legs carried in the C2 line: comma list of c1,c3,c4,c5 or 'none'")
     p.add_argument("--leg-steps", type=int, default=10)
     p.add_argument("--keys", type=int, default=100_000_000, help="keys (C2/C3) or elements (C4) per step per GPU")
     p.add_argument("--tenants", type=int, default=100_000, help="C3 tenant count (whole node)")
@@ -214,6 +232,44 @@ class Timer:
         self.e1.record(self.stream)
         torch.cuda.synchronize()
         self.ms = self.e0.elapsed_time(self.e1)
+
+
+# --dump-outputs: the files per workload
+OUTPUTS = {
+    "c2": "present_count: keys reported present by the last timed contains call (all the timed call returns); "
+          "present_flags_sample: the per-key answers of one more call of the same keys made after the timed steps "
+          "with a per-key output, at DUMP_SAMPLE seeded positions",
+    "c3": "present_counts: keys reported present per tenant by the last timed call",
+    "c4": "changed: the PFADD reply (0/1) of each of the 10k HLLs in the last timed step",
+    "c5": "reply_sample: the per-command replies of the last timed step at DUMP_SAMPLE seeded positions; "
+          "counts: the call's two totals over warm-up and timed steps",
+}
+DUMP_SAMPLE = 1 << 20  # elements kept of a per-key output (8 MiB as float64)
+
+
+def dump_sample(t):
+    """A per-key device tensor at fixed seeded positions (all of it if no longer than the sample)."""
+    import numpy as np
+    import torch
+
+    if t.numel() <= DUMP_SAMPLE:
+        return t
+    idx = np.sort(np.random.default_rng(0x5EEDD0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+    return t[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(dirname, rank, arrays):
+    """DIR/<name>.npy (rank 0; other ranks DIR/<name>_rank<r>.npy), float64."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().to("cpu", torch.float64).numpy()
+        path = os.path.join(dirname, name + (f"_rank{rank}" if rank else "") + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        log(f"[bench] wrote {path} {a.shape}")
 
 
 def gather_peak(client, nbytes, nkeys, k, stream, gen):
@@ -450,26 +506,30 @@ def run_c2(args, world, rank, local):
     fresh = torch.randint(0, 256, (n - half, 32), dtype=torch.uint8, device="cuda", generator=g)
     probe = torch.cat([added, fresh])
     del fresh
-    cnt = torch.zeros(4, dtype=torch.int64, device="cuda")  # [0] add, [1] warmup, [2] timed, [3] A/B
+    # [0] add, [1] warmup, [2] timed steps but the last, [3] A/B, [4] last timed step, [5] --dump-outputs call
+    cnt = torch.zeros(6, dtype=torch.int64, device="cuda")
 
-    # setup: add the first half (timed separately: the "add" half of the metric), after one
+    # setup: add the first half.  --full times it (the "add" half of the metric), after one
     # untimed add of the same keys into a scratch filter (first-call scratch allocations)
-    fw = client.getBloomFilter("bench-c2-warm")
-    fw.tryInitRaw(SIZE, K)
-    hw = BloomHandle(client, "bench-c2-warm")
-    hw.add_dev(device_keys(added.data_ptr(), half, 32), cnt.data_ptr(), stream=sptr)
-    torch.cuda.synchronize()
-    hw.close()
-    fw.delete()
-    cnt.zero_()
-    torch.cuda.synchronize()
+    if args.full:
+        fw = client.getBloomFilter("bench-c2-warm")
+        fw.tryInitRaw(SIZE, K)
+        hw = BloomHandle(client, "bench-c2-warm")
+        hw.add_dev(device_keys(added.data_ptr(), half, 32), cnt.data_ptr(), stream=sptr)
+        torch.cuda.synchronize()
+        hw.close()
+        fw.delete()
+        cnt.zero_()
+        torch.cuda.synchronize()
     with Timer(stream) as t_add:
         h.add_dev(device_keys(added.data_ptr(), half, 32), cnt.data_ptr(), stream=sptr)
     n_new = int(cnt[0].item())
     # the replicas are one filter: equal digests of `GET bench-c2` on every rank
-    digest = f.digest()
-    digests = gather_over_ranks(world, digest - (1 << 64) if digest >= 1 << 63 else digest)
-    assert len(set(digests)) == 1 and digests[0] != 0, f"replicas differ: {digests}"
+    digest, digests = None, []
+    if args.full or world > 1:
+        digest = f.digest()
+        digests = gather_over_ranks(world, digest - (1 << 64) if digest >= 1 << 63 else digest)
+        assert len(set(digests)) == 1 and digests[0] != 0, f"replicas differ: {digests}"
 
     dk = device_keys(probe.data_ptr(), n, 32)
     for _ in range(args.warmup):
@@ -477,24 +537,88 @@ def run_c2(args, world, rank, local):
     torch.cuda.synchronize()
     present_one = int(cnt[1].item()) // max(args.warmup, 1) if args.warmup else None
 
-    gathers_per_s = gather_peak(client, SIZE // 8, n, K, stream, g)  # same 512 MiB working set
-    writes_per_s = stream_write_peak(client, 2 << 30, stream)
+    gathers_per_s = writes_per_s = None
+    if args.full:
+        gathers_per_s = gather_peak(client, SIZE // 8, n, K, stream, g)  # same 512 MiB working set
+        writes_per_s = stream_write_peak(client, 2 << 30, stream)
 
-    # timed region
+    # timed region (the last step counts into a word of its own: what --dump-outputs writes)
     cnt[2].zero_()
     barrier(world)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with Timer(stream) as t_main:
-        for _ in range(args.steps):
-            h.contains_dev(dk, cnt.data_ptr() + 16, stream=sptr)
+        for s in range(args.steps):
+            h.contains_dev(dk, cnt.data_ptr() + (32 if s == args.steps - 1 else 16), stream=sptr)
     wall = time.perf_counter() - t0
     barrier(world)
     kern_ms = t_main.ms / args.steps
-    total_present = int(cnt[2].item())
+    last_present = int(cnt[4].item())
+    total_present = int(cnt[2].item()) + last_present
     if present_one is not None:
         assert total_present == present_one * args.steps, "contains count changed between steps"
     assert total_present >= half * args.steps  # no false negatives
+    if args.dump_outputs:
+        flags = torch.empty(n, dtype=torch.uint8, device="cuda")
+        h.contains_dev(dk, cnt.data_ptr() + 40, flags.data_ptr(), stream=sptr)
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, rank, {"present_count": torch.tensor([last_present]),
+                                               "present_flags_sample": dump_sample(flags)})
+        del flags
+
+    step_s = max_over_ranks(world, max(kern_ms / 1e3, 0.0))
+    keys_all = sum_over_ranks(world, n * args.steps)
+    value = keys_all / (step_s * args.steps)
+    algo_bytes = n * (32 + K * 8)  # SURVEY 8(d): 32 B key + k x 8 B gathered per key
+    achieved = algo_bytes / (kern_ms / 1e3) / 1e9
+    floor_bytes = n * 32 + SIZE // 8  # what any streaming design must move: the keys and the bitmap once
+    res = {
+        "metric": "Bloom contains keys/sec (whole node), C2: one 2^32-bit filter, k=7, 32-byte keys",
+        "value": value, "unit": "keys/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8", "data": "synthetic",
+        "config": {"workload": f"C2 RBloomFilter.contains(Collection) of {n / 1e6:g}M random 32-byte keys "
+                               "(50% present) vs one 2^32-bit k=7 filter per GPU",
+                   "keys_per_gpu": n, "key_bytes": 32, "size_bits": SIZE, "k": K,
+                   "parallelism": f"replicas x{world} of one filter (same adds on every rank, bitmap digests "
+                                  f"equal), each replica serving its own {n / 1e6:g}M-key contains stream "
+                                  "(weak scaling), no data-path collective"},
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS,
+                     "algorithmic_bytes_per_launch": algo_bytes,
+                     # one contains call = the partitioned pipeline's kernels in sequence on one stream
+                     "kernel": "contains pipeline: k_bk_stage1<32,8,512,2> + k_bk_emit2<1024,6> + k_bk_probe + "
+                               "k_bk_misses + k_bk_final",
+                     "kernel_avg_ms": kern_ms,
+                     # the pipeline's own floor: keys + bitmap streamed once (3.74 GB per call)
+                     "streaming_floor": {"bytes_per_launch": floor_bytes,
+                                         "achieved": floor_bytes / (kern_ms / 1e3) / 1e9,
+                                         "frac": floor_bytes / (kern_ms / 1e3) / 1e9 / HBM_PEAK_GBS}},
+        "extra": {"add_new_keys": n_new, "present_per_step": total_present // args.steps, "wall_s_timed": wall,
+                  "replica_digest": f"{digest:016x}" if digest is not None else None,
+                  "replicas_identical": len(set(digests)) == 1 if digests else None},
+    }
+    if args.full:
+        c2_full(args, rank, client, h, dk, added, cnt, stream, res, t_add, gathers_per_s, writes_per_s)
+    h.close()
+    f.delete()
+    client.shutdown()
+    del added, probe
+    torch.cuda.empty_cache()
+    return res
+
+
+def c2_full(args, rank, client, h, dk, added, cnt, stream, res, t_add, gathers_per_s, writes_per_s):
+    """--full: what the C2 line carries beside the headline figure (added to res in place)."""
+    import torch
+
+    from redisson_amd import BloomHandle, device_keys
+    from redisson_amd import _lib as L
+
+    K = 7
+    n, half, sptr = args.keys, args.keys // 2, stream.cuda_stream
+    kern_ms = res["roofline"]["kernel_avg_ms"]
+    present_step = res["extra"]["present_per_step"]
 
     # A/B reference: the same step through the direct early-exit kernel (k_bloom_contains)
     L.lib().rbx_tune(b"contains_partition", 0)
@@ -504,7 +628,7 @@ def run_c2(args, world, rank, local):
             h.contains_dev(dk, cnt.data_ptr() + 24, stream=sptr)
     L.lib().rbx_tune(b"contains_partition", 2)
     direct_ms = t_dir.ms / 3
-    assert int(cnt[3].item()) == 4 * (total_present // args.steps), "direct and partitioned counts differ"
+    assert int(cnt[3].item()) == 4 * present_step, "direct and partitioned counts differ"
     # SURVEY 8(d) C2's second filter: tryInit(448_089_842, 0.01) -> m = 4,294,967,293 bits, k = 7
     # (not a power of two: the exact 63-bit modulo instead of a mask), the same keys
     fn = client.getBloomFilter("bench-c2-tryinit")
@@ -528,12 +652,6 @@ def run_c2(args, world, rank, local):
     fn.delete()
     hostpath = None if args.no_hostpath or rank != 0 else host_path_rate(client, "bench-c2")
 
-    step_s = max_over_ranks(world, max(kern_ms / 1e3, 0.0))
-    keys_all = sum_over_ranks(world, n * args.steps)
-    value = keys_all / (step_s * args.steps)
-    algo_bytes = n * (32 + K * 8)  # SURVEY 8(d): 32 B key + k x 8 B gathered per key
-    achieved = algo_bytes / (kern_ms / 1e3) / 1e9
-    floor_bytes = n * 32 + SIZE // 8  # what any streaming design must move: the keys and the bitmap once
     # profiles/traffic.json holds PMC counts of 100M-key calls (the default workload); a run with
     # another --keys gets no PMC-derived fields rather than counts of a different call
     pmc_ok = n == C2_PROFILED_KEYS
@@ -541,60 +659,32 @@ def run_c2(args, world, rank, local):
                load_traffic(args.traffic_json, "contains_pipeline")) if pmc_ok else None
     reqf = request_fields(args.traffic_json if pmc_ok else None, "contains_pipeline", kern_ms, gathers_per_s,
                           writes_per_s)
-    res = {
-        "metric": "Bloom contains keys/sec (whole node), C2: one 2^32-bit filter, k=7, 32-byte keys",
-        "value": value, "unit": "keys/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u8", "data": "synthetic",
-        "config": {"workload": f"C2 RBloomFilter.contains(Collection) of {n / 1e6:g}M random 32-byte keys "
-                               "(50% present) vs one 2^32-bit k=7 filter per GPU",
-                   "keys_per_gpu": n, "key_bytes": 32, "size_bits": SIZE, "k": K,
-                   "parallelism": f"replicas x{world} of one filter (same adds on every rank, bitmap digests "
-                                  f"equal), each replica serving its own {n / 1e6:g}M-key contains stream "
-                                  "(weak scaling), no data-path collective"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "algorithmic_bytes_per_launch": algo_bytes,
-                     # one contains call = the partitioned pipeline's kernels in sequence on one stream
-                     "kernel": "contains pipeline: k_bk_stage1<32,8,512,2> + k_bk_emit2<1024,6> + k_bk_probe + "
-                               "k_bk_misses + k_bk_final",
-                     "kernel_avg_ms": kern_ms,
-                     # the pipeline's own floor: keys + bitmap streamed once (3.74 GB per call)
-                     "streaming_floor": {"bytes_per_launch": floor_bytes,
-                                         "achieved": floor_bytes / (kern_ms / 1e3) / 1e9,
-                                         "frac": floor_bytes / (kern_ms / 1e3) / 1e9 / HBM_PEAK_GBS},
-                     # the binding limit: memory requests at the L2->EA interface (PMC TCC_EA0_RD/WRREQ),
-                     # reads against the measured random-gather request rate at this working set,
-                     # writes against the measured streaming-write request rate
-                     **reqf,
-                     # north-star definition: keys/s x k / measured random-gather peak at this
-                     # working set (> 1: early exit and LDS probes avoid most random gathers)
-                     "gather_peak_per_s": gathers_per_s, "gather_frac": (n * K / (kern_ms / 1e3)) / gathers_per_s},
-        "extra": {"add_keys_per_s_per_gpu": half / (t_add.ms / 1e3), "add_new_keys": n_new,
-                  "pmc_fields": "profiles/traffic.json (100M-key calls)" if pmc_ok else
-                  f"omitted: PMC profiled at {C2_PROFILED_KEYS} keys per call, this run {n}",
-                  "replica_digest": f"{digest:016x}", "replicas_identical": len(set(digests)) == 1,
-                  "present_per_step": total_present // args.steps, "wall_s_timed": wall,
-                  "contains_direct_kernel_ms": direct_ms,
-                  "contains_direct_keys_per_s_per_gpu": n / (direct_ms / 1e3),
-                  # the setup add = the partitioned add pipeline (add_partitioned.hip), PMC per call
-                  "add_ms": t_add.ms,
-                  "add_traffic": (load_traffic(args.traffic_json, "add_pipeline", "hbm_bytes_by_class") or
-                                  load_traffic(args.traffic_json, "add_pipeline")) if pmc_ok else None,
-                  "add_requests_per_call": load_traffic(args.traffic_json, "add_pipeline", "requests_per_launch")
-                  if pmc_ok else None,
-                  # of which atomics (PMC TCC_ATOMIC: non-owner counters, stage-1 reservations)
-                  "add_atomic_requests_per_call": load_traffic(args.traffic_json, "add_pipeline",
-                                                               "atomic_requests_per_launch") if pmc_ok else None,
-                  "host_path": hostpath,
-                  "c2_tryinit_nonpow2": nonpow2},
-    }
-    h.close()
-    f.delete()
-    client.shutdown()
-    del added, probe
-    torch.cuda.empty_cache()
-    return res
+    res["roofline"].update({
+        "traffic": traffic,
+        # the binding limit: memory requests at the L2->EA interface (PMC TCC_EA0_RD/WRREQ),
+        # reads against the measured random-gather request rate at this working set,
+        # writes against the measured streaming-write request rate
+        **reqf,
+        # north-star definition: keys/s x k / measured random-gather peak at this
+        # working set (> 1: early exit and LDS probes avoid most random gathers)
+        "gather_peak_per_s": gathers_per_s, "gather_frac": (n * K / (kern_ms / 1e3)) / gathers_per_s})
+    res["extra"].update({
+        "add_keys_per_s_per_gpu": half / (t_add.ms / 1e3),
+        "pmc_fields": "profiles/traffic.json (100M-key calls)" if pmc_ok else
+        f"omitted: PMC profiled at {C2_PROFILED_KEYS} keys per call, this run {n}",
+        "contains_direct_kernel_ms": direct_ms,
+        "contains_direct_keys_per_s_per_gpu": n / (direct_ms / 1e3),
+        # the setup add = the partitioned add pipeline (add_partitioned.hip), PMC per call
+        "add_ms": t_add.ms,
+        "add_traffic": (load_traffic(args.traffic_json, "add_pipeline", "hbm_bytes_by_class") or
+                        load_traffic(args.traffic_json, "add_pipeline")) if pmc_ok else None,
+        "add_requests_per_call": load_traffic(args.traffic_json, "add_pipeline", "requests_per_launch")
+        if pmc_ok else None,
+        # of which atomics (PMC TCC_ATOMIC: non-owner counters, stage-1 reservations)
+        "add_atomic_requests_per_call": load_traffic(args.traffic_json, "add_pipeline",
+                                                     "atomic_requests_per_launch") if pmc_ok else None,
+        "host_path": hostpath,
+        "c2_tryinit_nonpow2": nonpow2})
 
 
 # ------------------------------------------------------------------------------------------
@@ -687,32 +777,39 @@ def run_c3(args, world, rank, local, steps, warmup):
     keys = torch.randint(0, 256, (n, 16), dtype=torch.uint8, device="cuda", generator=g)
     seg = torch.arange(nt + 1, dtype=torch.int64, device="cuda") * per
     counts = torch.zeros(nt, dtype=torch.int64, device="cuda")
+    counts_last = torch.zeros(nt, dtype=torch.int64, device="cuda")  # the last timed step's (--dump-outputs)
     arr = (C.c_void_p * nt)(*[h.h.value for h in handles])
     dk = device_keys(keys.data_ptr(), n, 16)
 
-    def step():
+    def step(out=counts):
         assert L.lib().rbx_bloom_contains_multi_dev(client.ctx, arr, nt, seg.data_ptr(), C.byref(dk), None,
-                                                     counts.data_ptr(), sptr) == 0
+                                                     out.data_ptr(), sptr) == 0
 
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
     barrier(world)
     with Timer(stream) as t:
-        for _ in range(steps):
-            step()
+        for s in range(steps):
+            step(counts_last if s == steps - 1 else counts)
     ms = t.ms / steps
     step_s = max_over_ranks(world, ms / 1e3)
     value = sum_over_ranks(world, n) / step_s
     per_rank_tenants = gather_over_ranks(world, nt)
-    present = int(counts.sum().item()) / max(warmup + steps, 1)
-    add = c3_add_half(args, client, arr, nt, per, k, seg, stream, g, steps, warmup, world) if args.c3_add else None
+    present = int((counts.sum() + counts_last.sum()).item()) / max(warmup + steps, 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"present_counts": counts_last})
+    add = None
+    if args.c3_add and args.full:
+        add = c3_add_half(args, client, arr, nt, per, k, seg, stream, g, steps, warmup, world)
     del pool
-    # request roofline at C3's locality: `per` consecutive keys gather inside one 1.8 MB slice
-    tbl = torch.empty(4 << 30, dtype=torch.uint8, device="cuda")
-    peak = segment_gather_peak(client, tbl.data_ptr(), tbl.numel(), (size + 7) // 8, per, n, stream)
-    del tbl
-    wpeak = stream_write_peak(client, 1 << 30, stream)
+    peak = wpeak = None
+    if args.full:
+        # request roofline at C3's locality: `per` consecutive keys gather inside one 1.8 MB slice
+        tbl = torch.empty(4 << 30, dtype=torch.uint8, device="cuda")
+        peak = segment_gather_peak(client, tbl.data_ptr(), tbl.numel(), (size + 7) // 8, per, n, stream)
+        del tbl
+        wpeak = stream_write_peak(client, 1 << 30, stream)
     if add is not None:
         # the add half against the same request roofline (reads at the segment-gather rate, writes at
         # the stream-write rate): request_frac = its request floor / its call time
@@ -739,12 +836,14 @@ def run_c3(args, world, rank, local, steps, warmup):
                    "parallelism": f"CRC16-slot sharded x{world} (no data-path collective)"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": load_traffic(tj, kname, "hbm_bytes_by_class") or load_traffic(tj, kname),
-                     "kernel": kdesc, "kernel_avg_ms": ms,
-                     "request_peak_kind": "k_gather_segments: 4 random loads per key inside its tenant's slice",
-                     **request_fields(tj, kname, ms, peak, wpeak)},
+                     "kernel": kdesc, "kernel_avg_ms": ms},
         "extra": {"setup_s": setup_s, "present_fraction": present / n},
     }
+    if args.full:
+        res["roofline"].update({
+            "traffic": load_traffic(tj, kname, "hbm_bytes_by_class") or load_traffic(tj, kname),
+            "request_peak_kind": "k_gather_segments: 4 random loads per key inside its tenant's slice",
+            **request_fields(tj, kname, ms, peak, wpeak)})
     if add is not None:
         res["add"] = add
     for h in handles:
@@ -892,12 +991,19 @@ def run_c5(args, world, rank, local, steps, warmup):
     value = sum_over_ranks(world, n) / step_s
     top = int(torch.bincount(kf.long(), minlength=nt).max().item())
     del pool
-    tbl = torch.empty(4 << 30, dtype=torch.uint8, device="cuda")
-    # read-request peak: the larger of the tenant-slice gather rate (uniform tenants, one key per
-    # slice) and the uniform 512 MiB gather rate -- Zipf-hot tenants gather above the former
-    peak = max(segment_gather_peak(client, tbl.data_ptr(), tbl.numel(), 1_797_199, 1, n, stream),
-               gather_peak(client, 512 << 20, n, 7, stream, g))
-    del tbl
+    if args.dump_outputs:
+        if not args.c5_replies:
+            raise SystemExit("--dump-outputs needs the replies written (--c5-replies 1)")
+        dump_outputs(args.dump_outputs, rank, {"reply_sample": dump_sample(replies), "counts": counts})
+    peak = wpeak = None
+    if args.full:
+        tbl = torch.empty(4 << 30, dtype=torch.uint8, device="cuda")
+        # read-request peak: the larger of the tenant-slice gather rate (uniform tenants, one key per
+        # slice) and the uniform 512 MiB gather rate -- Zipf-hot tenants gather above the former
+        peak = max(segment_gather_peak(client, tbl.data_ptr(), tbl.numel(), 1_797_199, 1, n, stream),
+                   gather_peak(client, 512 << 20, n, 7, stream, g))
+        del tbl
+        wpeak = stream_write_peak(client, 1 << 30, stream)
     nadds = int(op.sum().item())
     # a contains = 64 B key + k x 8 B gathered = 144 B, an add +80 B RMW (k x 8 B); plus
     # the 1-byte reply every command writes
@@ -921,15 +1027,16 @@ def run_c5(args, world, rank, local, steps, warmup):
                    "parallelism": f"CRC16-slot sharded x{world} (no data-path collective)"},
         "roofline": {"bound": "hbm", "achieved": algo / (ms / 1e3) / 1e9, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": algo / (ms / 1e3) / 1e9 / HBM_PEAK_GBS,
-                     "traffic": load_traffic(tj, "stream_pipeline", "hbm_bytes_by_class") or
-                     load_traffic(tj, "stream_pipeline"),
                      "kernel": C5_KERNELS, "kernel_avg_ms": ms,
-                     "algorithmic_bytes_per_launch": algo, "adds_per_launch": nadds,
-                     "request_peak_kind": "max(k_gather_segments one key per tenant slice, k_gather_probe "
-                                          "over 512 MiB) for reads; k_stream_write for writes",
-                     **request_fields(tj, "stream_pipeline", ms, peak,
-                                      stream_write_peak(client, 1 << 30, stream))},
+                     "algorithmic_bytes_per_launch": algo, "adds_per_launch": nadds},
     }
+    if args.full:
+        res["roofline"].update({
+            "traffic": load_traffic(tj, "stream_pipeline", "hbm_bytes_by_class") or
+            load_traffic(tj, "stream_pipeline"),
+            "request_peak_kind": "max(k_gather_segments one key per tenant slice, k_gather_probe "
+                                 "over 512 MiB) for reads; k_stream_write for writes",
+            **request_fields(tj, "stream_pipeline", ms, peak, wpeak)})
     for h in handles:
         h.close()
     client.shutdown()
@@ -996,11 +1103,13 @@ def run_c4(args, world, rank, local, steps, warmup):
             step()
     ms = t.ms / steps
     changed_last = int((changed != 0).sum().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"changed": changed})
     arr = arrs[-1]
     del el
     nbytes = NH * 16384
     merge = {"allreduce_bytes": nbytes, "nranks_rccl": None, "rccl_max_allreduce_ms": None}
-    if world > 1 and not shared_gpu():
+    if args.full and world > 1 and not shared_gpu():
         # element-partitioned registers -> ONE RCCL uint8 max all-reduce over xGMI
         import torch.distributed as dist
 
@@ -1027,7 +1136,7 @@ def run_c4(args, world, rank, local, steps, warmup):
         merge.update({"exchange": "RCCL ncclAllReduce(ncclUint8, ncclMax), pack -> all-reduce -> unpack_max",
                       "nranks_rccl": nr.value, "rccl_max_allreduce_ms": mt * 1e3,
                       "algbw_GBps": algbw, "busbw_GBps": algbw * 2 * (world - 1) / world})
-    elif world > 1:
+    elif args.full and world > 1:
         # shared-GPU rehearsal: the same pack / unpack_max exchange, the all-reduce over gloo
         import torch.distributed as dist
 
@@ -1044,11 +1153,12 @@ def run_c4(args, world, rank, local, steps, warmup):
         mt = max_over_ranks(world, time.perf_counter() - t0)
         merge.update({"exchange": "gloo (shared-GPU rehearsal: RCCL needs one GPU per rank)",
                       "exchange_ms": mt * 1e3})
-    out = np.zeros(NH, np.uint64)
-    t0 = time.perf_counter()
-    assert L.lib().rbx_hll_count_each_handles(client.ctx, arr, NH, out.ctypes.data_as(L.u64p)) == 0
-    count_ms = (time.perf_counter() - t0) * 1e3
-    peak_gbs = stream_read_peak(client, 8 << 30, stream)
+    if args.full:
+        out = np.zeros(NH, np.uint64)
+        t0 = time.perf_counter()
+        assert L.lib().rbx_hll_count_each_handles(client.ctx, arr, NH, out.ctypes.data_as(L.u64p)) == 0
+        count_ms = (time.perf_counter() - t0) * 1e3
+        peak_gbs = stream_read_peak(client, 8 << 30, stream)
     step_s = max_over_ranks(world, ms / 1e3)
     value = sum_over_ranks(world, n) / step_s
     achieved = n * 16 / (ms / 1e3) / 1e9
@@ -1062,17 +1172,19 @@ def run_c4(args, world, rank, local, steps, warmup):
                    "elements_per_gpu": n, "parallelism": f"element-partitioned x{world}"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": (load_traffic(args.traffic_json, "k_hll_pfadd", "hbm_bytes_by_class") or
-                                 load_traffic(args.traffic_json, "k_hll_pfadd"))
-                     if (args.elements, world) == (1_000_000_000, 1) else None,
                      # the step: PFADD registers (k_hll_pfadd) + the sparse strings of the fresh keys
                      # replayed to their promotion (k_hll_sparse_replay); achieved over the whole step
-                     "kernel": "k_hll_pfadd<16> + k_hll_sparse_replay<16>", "kernel_avg_ms": ms,
-                     # elems/s x 16 B / the measured HBM stream-read peak
-                     "stream_read_peak_GBps": peak_gbs, "stream_frac": achieved / peak_gbs},
-        "extra": {"pfcount_10k_ms": count_ms, "mean_count": float(out.mean()), "merge": merge,
-                  "changed_replies_last_step": changed_last},
+                     "kernel": "k_hll_pfadd<16> + k_hll_sparse_replay<16>", "kernel_avg_ms": ms},
+        "extra": {"changed_replies_last_step": changed_last},
     }
+    if args.full:
+        res["roofline"].update({
+            "traffic": (load_traffic(args.traffic_json, "k_hll_pfadd", "hbm_bytes_by_class") or
+                        load_traffic(args.traffic_json, "k_hll_pfadd"))
+            if (args.elements, world) == (1_000_000_000, 1) else None,
+            # elems/s x 16 B / the measured HBM stream-read peak
+            "stream_read_peak_GBps": peak_gbs, "stream_frac": achieved / peak_gbs})
+        res["extra"].update({"pfcount_10k_ms": count_ms, "mean_count": float(out.mean()), "merge": merge})
     for hs in sets:
         for hp in hs:
             L.lib().rbx_hll_close(hp)
@@ -1115,7 +1227,8 @@ def main():
         return
     if args.workload == "c2":
         res = run_c2(args, world, rank, local)
-        legs = [] if args.legs == "none" else [x for x in args.legs.split(",") if x]
+        args.dump_outputs = None  # the headline's outputs only, not the legs'
+        legs = [] if args.legs == "none" or not args.full else [x for x in args.legs.split(",") if x]
         ls, lw = min(args.steps, args.leg_steps), min(args.warmup, 2)
         res["legs"] = {}
         for leg in legs:
@@ -1139,7 +1252,7 @@ def main():
 
                 traceback.print_exc()
                 res["legs"][leg] = {"error": f"{type(e).__name__}: {e}"}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     elif args.workload == "c4":
         res = run_c4(args, world, rank, local, args.steps, args.warmup)

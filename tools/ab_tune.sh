@@ -9,7 +9,7 @@ mkdir -p "$R/gpurun_out"
 for i in $(seq "$N"); do
   for t in "$@"; do
     tune=$t; [ "$t" = "-" ] && tune=""
-    timeout -k 10 240 python3 "$R/bench.py" --workload "$W" --steps 10 --warmup 2 --no-cpu-baseline --no-hostpath --legs none \
+    timeout -k 10 240 python3 "$R/bench.py" --full --workload "$W" --steps 10 --warmup 2 --no-cpu-baseline --no-hostpath --legs none \
       --tune "$tune" > "$R/gpurun_out/abt_run.log" 2>&1 || exit 1
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(json.dumps({'tune': sys.argv[2], 'ms_per_step': d['ms_per_step'], 'value': d['value'], 'add_ms': d.get('extra', {}).get('add_ms')}))" \
       "$R/gpurun_out/abt_run.log" "$t" >> "$R/gpurun_out/abt_$W.jsonl" || exit 1

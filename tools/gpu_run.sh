@@ -5,8 +5,8 @@
 # steps (run in order; the first failure, time limit or crash ends the call -- no GPU step after it):
 #   tests            the whole -m gpu suite              tests=<pytest -k expr>   a subset
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (default line)      bench=<args, '+' for ' '>
-#   kstats=<args>    rocprofv3 --kernel-trace --stats of bench.py <args> (summary CSV kept)
+#   bench            python bench.py --full (every leg) bench=<args, '+' for ' '>
+#   kstats=<args>    rocprofv3 --kernel-trace --stats of bench.py --full <args> (summary CSV kept)
 #   profile=<args>   tools/profile_round.sh <tag> <args> (kernel stats + PMC passes + traffic.json)
 #   micro=<args>     python tools/microbench.py <args>
 set -u
@@ -37,13 +37,13 @@ for step in "$@"; do
         || { echo "smoke failed"; tail -20 "$O/smoke_$i.log"; exit 1; }
       tail -1 "$O/smoke_$i.log" ;;
     bench)
-      timeout -k 10 600 python -u bench.py $arg > "$O/bench_$i.json" 2> "$O/bench_$i.err" \
+      timeout -k 10 600 python -u bench.py --full $arg > "$O/bench_$i.json" 2> "$O/bench_$i.err" \
         || { echo "bench failed"; tail -20 "$O/bench_$i.err"; exit 1; }
       tail -c 600 "$O/bench_$i.json"; echo ;;
     kstats)
       D=$O/kstats_$i
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o run -- \
-        python3 "$R/bench.py" --no-cpu-baseline --no-hostpath $arg > "$D.log" 2>&1) \
+        python3 "$R/bench.py" --full --no-cpu-baseline --no-hostpath $arg > "$D.log" 2>&1) \
         || { echo "kstats failed"; tail -20 "$D.log"; exit 1; }
       f=$(find "$D" -name "*kernel_stats.csv" | head -1)
       cp "$f" "$O/kernel_stats_$i.csv" && rm -rf "$D"

@@ -14,7 +14,7 @@ while [ $# -ge 2 ]; do
   [ "$tune" = "-" ] && tune=""
   D=$R/gpurun_out/kstb_${TAG}_$i
   if [ "$lib" = "-" ]; then unset RBX_LIB_PATH; else export RBX_LIB_PATH=$R/$lib; fi
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o run -- python3 "$R/bench.py" --workload "$W" --steps 3 --warmup 1 --no-cpu-baseline --no-hostpath --legs none --tune "$tune" > "$D.log" 2>&1 || exit 1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o run -- python3 "$R/bench.py" --full --workload "$W" --steps 3 --warmup 1 --no-cpu-baseline --no-hostpath --legs none --tune "$tune" > "$D.log" 2>&1 || exit 1
   f=$(find "$D" -name "*kernel_stats.csv" | head -1)
   python3 -c "
 import csv,sys

@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/profile_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp || exit 1
-B="$R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-hostpath --legs none $*"
+B="$R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-hostpath --legs none $*"
 SB=${RBX_STREAM_BYTES:-"k_bk_stage1=3.2e9 k_bloom_contains=3.2e9"}
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 $B > "$OUT/trace.log" 2>&1 || exit 1
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o p -- python3 $B > "$OUT/pmc_fetch.log" 2>&1 || exit 1
