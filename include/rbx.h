@@ -199,6 +199,62 @@ int rbx_bloom_import(rbx_ctx *ctx, const char *name, const uint8_t *bytes, uint6
 /* SET name from a DEVICE buffer (device-resident snapshot restore); synchronous. */
 int rbx_bloom_import_dev(rbx_ctx *ctx, const char *name, const uint8_t *d_bytes, uint64_t len, void *stream);
 
+/* ---- RBitSet (by binary name) -- M/api/RBitSet.java, impl M/RedissonBitSet.java ---------------
+ * The bit set of `name` is the Redis string under that key: the one a Bloom filter of the same
+ * name keeps its bits in (createBitSet, M/RedissonBloomFilter.java:203-205), so these calls and the
+ * rbx_bloom_* calls see each other's writes.  Bit i is byte i>>3, mask 0x80 >> (i&7); offsets end
+ * at 2^32 - 1 (a larger one: RBX_E_REDIS "ERR bit offset is not an integer or out of range").  A
+ * write grows the string like SETBIT -- whatever the value written -- and keeps the key's timeout;
+ * a missing key reads as the empty string.  A key of another type gives RBX_E_WRONGTYPE.
+ * clear() (:492-494) is DEL name: rbx_del_n. */
+/* get(bitIndex) = GETBIT  :277-279 */
+int rbx_bitset_get(rbx_ctx *ctx, rbx_name name, uint64_t index, int *bit);
+/* set(bitIndex, value) / clear(bitIndex) = SETBIT, *old (nullable) = the bit before  :302-305 */
+int rbx_bitset_set(rbx_ctx *ctx, rbx_name name, uint64_t index, int value, int *old);
+/* set(long[] indexArray, value) = one BITFIELD of `set u1 index value` sub-commands, void  :312-324.
+ * BITFIELD parses every sub-command before it runs any: an index past the offset limit fails the
+ * call with nothing changed.  n = 0 sends nothing (no key is created). */
+int rbx_bitset_set_indexes(rbx_ctx *ctx, rbx_name name, const uint64_t *indexes, uint64_t n, int value);
+/* n GETBITs in one call, out[i] = bit indexes[i] (engine extension, like containsEach) */
+int rbx_bitset_get_indexes(rbx_ctx *ctx, rbx_name name, const uint64_t *indexes, uint64_t n, uint8_t *out);
+/* The same two over DEVICE index arrays, enqueued on `stream` (d_out: device bytes).  Exception to
+ * the *_dev convention: each waits once on the stream for the maximum index (the offset check,
+ * the string's growth and its new length are host decisions). */
+int rbx_bitset_set_indexes_dev(rbx_ctx *ctx, rbx_name name, const uint64_t *d_indexes, uint64_t n, int value,
+                               void *stream);
+int rbx_bitset_get_indexes_dev(rbx_ctx *ctx, rbx_name name, const uint64_t *d_indexes, uint64_t n, uint8_t *d_out,
+                               void *stream);
+/* set(fromIndex, toIndex, value) / clear(fromIndex, toIndex): a batch of one SETBIT per index of
+ * [from, to), in order  :442-454.  from >= to sends nothing.  to > 2^32 applies [from, 2^32) and
+ * then returns RBX_E_REDIS (the pipelined-batch rule of RBX_E_REDIS above). */
+int rbx_bitset_set_range(rbx_ctx *ctx, rbx_name name, uint64_t from, uint64_t to, int value);
+/* and / or / xor (:362-388) and not (:462-464) = BITOP op dest src_0 .. src_{nsrc-1} ([redis-7.2]
+ * bitops.c bitopCommand): the result is as long as the longest source, a shorter source reads as
+ * zero past its end and a missing one is the empty string.  dest may be any of the sources
+ * (Redisson passes its own name as the first, :381-388).  *result_len (nullable) = the reply.  A
+ * result of length 0 deletes dest; otherwise dest is overwritten and loses its timeout (setKey
+ * without KEEPTTL).  NOT takes one source (else RBX_E_REDIS).  A {name}:config hash as dest or
+ * source gives RBX_E_WRONGTYPE with dest untouched.  The one divergence from Redis: an HLL key is
+ * a string there and a legal BITOP operand; here it is refused with RBX_E_WRONGTYPE. */
+enum { RBX_BITOP_AND = 0, RBX_BITOP_OR = 1, RBX_BITOP_XOR = 2, RBX_BITOP_NOT = 3 };
+int rbx_bitset_op(rbx_ctx *ctx, int op, rbx_name dest, const rbx_name *srcs, uint32_t nsrc, uint64_t *result_len);
+/* cardinality() = BITCOUNT  :482-484;  size() = STRLEN * 8  :472-474 */
+int rbx_bitset_cardinality(rbx_ctx *ctx, rbx_name name, uint64_t *out);
+int rbx_bitset_size(rbx_ctx *ctx, rbx_name name, uint64_t *out);
+/* length(): the Lua script of lengthAsync  :428-439 -- not java.util.BitSet.length().  It looks at
+ * the string's LAST byte only (BITPOS key 1 -1): the highest set bit of that byte + 1.  When that
+ * byte is zero, or the key is missing, its loop runs over bits 0 and -1: 1 if bit 0 is set, else
+ * the script fails on GETBIT key -1 (RBX_E_REDIS). */
+int rbx_bitset_length(rbx_ctx *ctx, rbx_name name, int64_t *out);
+/* the same script over a host string (no context) */
+int rbx_bitset_length_of(const uint8_t *bytes, uint64_t len, int64_t *out);
+/* toByteArray() = GET  :327-334 and set(BitSet) = SET  :457-459: rbx_bloom_export / rbx_bloom_import
+ * with a binary name */
+int rbx_bitset_export_n(rbx_ctx *ctx, rbx_name name, uint8_t *out, uint64_t cap, uint64_t *redis_len);
+int rbx_bitset_import_n(rbx_ctx *ctx, rbx_name name, const uint8_t *bytes, uint64_t len);
+/* rename(newName) = RENAME name newName, `name` alone (M/RedissonObject.java:151-153) */
+int rbx_bitset_rename(rbx_ctx *ctx, rbx_name name, rbx_name new_name);
+
 /* ---- replicas ("replicate the bitmap, split contains keys across GPUs") ---------
  * Redisson serves contains' GETBITs as reads that may go to a replica
  * (M/RedissonBitSet.java:277-279 readAsync, ReadMode.SLAVE M/config/BaseMasterSlaveServersConfig.java:60)

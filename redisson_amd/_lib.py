@@ -70,6 +70,8 @@ RBX_E_NO_SUCH_KEY = -8
 RBX_E_REDIS = -9
 RBX_E_TIMEOUT = -10
 
+RBX_BITOP_AND, RBX_BITOP_OR, RBX_BITOP_XOR, RBX_BITOP_NOT = 0, 1, 2, 3
+
 # name -> (restype, argtypes); every function declared in include/rbx.h
 SIGNATURES = {
     "rbx_abi_version": (C.c_int, []),
@@ -199,6 +201,22 @@ SIGNATURES = {
     "rbx_hll_open_n": (C.c_int, [vp, RbxName, C.c_int, C.POINTER(vp)]),
     "rbx_hll_pack_registers": (C.c_int, [vp, C.POINTER(vp), C.c_uint32, vp, vp]),
     "rbx_hll_unpack_max_registers": (C.c_int, [vp, C.POINTER(vp), C.c_uint32, vp, vp]),
+    # RBitSet over the bitmap keys
+    "rbx_bitset_get": (C.c_int, [vp, RbxName, C.c_uint64, C.POINTER(C.c_int)]),
+    "rbx_bitset_set": (C.c_int, [vp, RbxName, C.c_uint64, C.c_int, C.POINTER(C.c_int)]),
+    "rbx_bitset_set_indexes": (C.c_int, [vp, RbxName, u64p, C.c_uint64, C.c_int]),
+    "rbx_bitset_get_indexes": (C.c_int, [vp, RbxName, u64p, C.c_uint64, u8p]),
+    "rbx_bitset_set_indexes_dev": (C.c_int, [vp, RbxName, vp, C.c_uint64, C.c_int, vp]),
+    "rbx_bitset_get_indexes_dev": (C.c_int, [vp, RbxName, vp, C.c_uint64, vp, vp]),
+    "rbx_bitset_set_range": (C.c_int, [vp, RbxName, C.c_uint64, C.c_uint64, C.c_int]),
+    "rbx_bitset_op": (C.c_int, [vp, C.c_int, RbxName, C.POINTER(RbxName), C.c_uint32, u64p]),
+    "rbx_bitset_cardinality": (C.c_int, [vp, RbxName, u64p]),
+    "rbx_bitset_size": (C.c_int, [vp, RbxName, u64p]),
+    "rbx_bitset_length": (C.c_int, [vp, RbxName, C.POINTER(C.c_int64)]),
+    "rbx_bitset_length_of": (C.c_int, [u8p, C.c_uint64, C.POINTER(C.c_int64)]),
+    "rbx_bitset_export_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64, u64p]),
+    "rbx_bitset_import_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64]),
+    "rbx_bitset_rename": (C.c_int, [vp, RbxName, RbxName]),
     "rbx_bench_gather": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     "rbx_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "rbx_bench_stream_geometry": (C.c_int, [vp, u64p]),

@@ -57,6 +57,10 @@ class RedissonClient:
     def getHyperLogLog(self, name: str, codec: Codec | None = None) -> "RHyperLogLog":
         return RHyperLogLog(self, name, codec or DEFAULT_CODEC)
 
+    def getBitSet(self, name: str) -> "RBitSet":
+        """M/api/RedissonClient.java getBitSet(name)"""
+        return RBitSet(self, name)
+
     def shutdown(self) -> None:
         if self._ctx:
             _check(L.lib().rbx_shutdown(self._ctx))
@@ -70,6 +74,7 @@ class RedissonClient:
 
     get_bloom_filter = getBloomFilter
     get_hyper_log_log = getHyperLogLog
+    get_bit_set = getBitSet
 
     def __enter__(self):
         return self
@@ -303,6 +308,178 @@ class RBloomFilter(_Expirable):
     try_init = tryInit
     get_size = getSize
     get_hash_iterations = getHashIterations
+    is_exists = isExists
+
+
+class RBitSet(_Expirable):
+    """M/RedissonBitSet.java over rbx_bitset_*: the Redis string under `name` as a bit set -- for a
+    Bloom filter's name, the filter's own bits (createBitSet, M/RedissonBloomFilter.java:203-205)."""
+
+    def __init__(self, client: RedissonClient, name: str):
+        self._client = client
+        self._name = name
+
+    def getName(self) -> str:
+        return self._name
+
+    def _n(self, name: str | None = None):
+        """(rbx_name, keep-alive) of this key or another"""
+        return L.name_struct(self._name if name is None else name)
+
+    @staticmethod
+    def _indexes(indexes) -> np.ndarray:
+        a = np.asarray(indexes)
+        if a.size and (a.dtype.kind not in "iu" or (a.dtype.kind == "i" and int(a.min()) < 0)):
+            raise IllegalArgumentException("bit indexes are non-negative integers")
+        return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+
+    # ---- single bits ------------------------------------------------------------------
+    def get(self, bitIndex: int) -> bool:
+        """:277-279 GETBIT"""
+        nm, _keep = self._n()
+        bit = C.c_int()
+        _check(L.lib().rbx_bitset_get(self._client.ctx, nm, int(bitIndex), C.byref(bit)))
+        return bool(bit.value)
+
+    def set(self, bitIndex: int, value: bool = True) -> bool:
+        """:302-305 SETBIT -> the bit before"""
+        nm, _keep = self._n()
+        old = C.c_int()
+        _check(L.lib().rbx_bitset_set(self._client.ctx, nm, int(bitIndex), int(bool(value)), C.byref(old)))
+        return bool(old.value)
+
+    def clearBit(self, bitIndex: int) -> bool:
+        """clear(bitIndex) :487-489"""
+        return self.set(bitIndex, False)
+
+    # ---- ranges and batches ---------------------------------------------------------------
+    def setRange(self, fromIndex: int, toIndex: int, value: bool = True) -> None:
+        """set(fromIndex, toIndex, value) :442-454 -- bits [fromIndex, toIndex)"""
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_set_range(self._client.ctx, nm, int(fromIndex), int(toIndex), int(bool(value))))
+
+    def clearRange(self, fromIndex: int, toIndex: int) -> None:
+        """clear(fromIndex, toIndex) :452-454"""
+        self.setRange(fromIndex, toIndex, False)
+
+    def setIndexes(self, indexes, value: bool = True) -> None:
+        """set(long[] indexArray, value) :312-324"""
+        idx = self._indexes(indexes)
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_set_indexes(self._client.ctx, nm, idx.ctypes.data_as(L.u64p), idx.size,
+                                              int(bool(value))))
+
+    def getIndexes(self, indexes) -> np.ndarray:
+        """One GETBIT per index -- engine extension, like containsEach."""
+        idx = self._indexes(indexes)
+        out = np.zeros(max(idx.size, 1), np.uint8)
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_get_indexes(self._client.ctx, nm, idx.ctypes.data_as(L.u64p), idx.size,
+                                              out.ctypes.data_as(L.u8p)))
+        return out[: idx.size].astype(bool)
+
+    def setIndexesDev(self, d_indexes: int, n: int, value: bool = True, stream: int | None = None) -> None:
+        """setIndexes over a device array of n u64 indexes (rbx_bitset_set_indexes_dev)."""
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_set_indexes_dev(self._client.ctx, nm, d_indexes, int(n), int(bool(value)), stream))
+
+    def getIndexesDev(self, d_indexes: int, n: int, d_out: int, stream: int | None = None) -> None:
+        """getIndexes over device arrays: d_out receives n bytes (rbx_bitset_get_indexes_dev)."""
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_get_indexes_dev(self._client.ctx, nm, d_indexes, int(n), d_out, stream))
+
+    # ---- whole-string reads -----------------------------------------------------------------
+    def cardinality(self) -> int:
+        """:482-484 BITCOUNT"""
+        nm, _keep = self._n()
+        out = C.c_uint64()
+        _check(L.lib().rbx_bitset_cardinality(self._client.ctx, nm, C.byref(out)))
+        return int(out.value)
+
+    def size(self) -> int:
+        """:472-474 STRLEN * 8"""
+        nm, _keep = self._n()
+        out = C.c_uint64()
+        _check(L.lib().rbx_bitset_size(self._client.ctx, nm, C.byref(out)))
+        return int(out.value)
+
+    def length(self) -> int:
+        """:428-439 -- the script's answer (see rbx_bitset_length), not java.util.BitSet.length()"""
+        nm, _keep = self._n()
+        out = C.c_int64()
+        _check(L.lib().rbx_bitset_length(self._client.ctx, nm, C.byref(out)))
+        return int(out.value)
+
+    def toByteArray(self) -> bytes:
+        """:327-334 GET (empty for a missing key)"""
+        nm, _keep = self._n()
+        n = C.c_uint64()
+        _check(L.lib().rbx_bitset_export_n(self._client.ctx, nm, None, 0, C.byref(n)))
+        buf = np.zeros(max(n.value, 1), np.uint8)
+        _check(L.lib().rbx_bitset_export_n(self._client.ctx, nm, buf.ctypes.data_as(L.u8p), n.value, C.byref(n)))
+        return buf[: n.value].tobytes()
+
+    def setBytes(self, data: bytes) -> None:
+        """set(BitSet) :457-459 -- SET name <bytes> (the caller lays the bits out MSB-first)"""
+        buf = np.frombuffer(data, np.uint8) if data else np.zeros(1, np.uint8)
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_import_n(self._client.ctx, nm, buf.ctypes.data_as(L.u8p), len(data)))
+
+    # ---- BITOP ------------------------------------------------------------------------------
+    def _op(self, op: int, names) -> int:
+        """opAsync :381-388 -- BITOP op name name others..; returns the reply (the result's length)"""
+        nm, _keep = self._n()
+        arr, _keep2 = L.names_array([self._name, *names])
+        out = C.c_uint64()
+        _check(L.lib().rbx_bitset_op(self._client.ctx, op, nm, arr, 1 + len(names), C.byref(out)))
+        return int(out.value)
+
+    def or_(self, *bitSetNames: str) -> None:
+        self._op(L.RBX_BITOP_OR, bitSetNames)
+
+    def and_(self, *bitSetNames: str) -> None:
+        self._op(L.RBX_BITOP_AND, bitSetNames)
+
+    def xor(self, *bitSetNames: str) -> None:
+        self._op(L.RBX_BITOP_XOR, bitSetNames)
+
+    def not_(self) -> None:
+        """:462-464 BITOP NOT name name"""
+        self._op(L.RBX_BITOP_NOT, ())
+
+    # ---- RObject / RExpirable ---------------------------------------------------------------
+    def clear(self) -> None:
+        """:492-494 DEL name"""
+        self.delete()
+
+    def delete(self) -> bool:
+        arr, _keep = L.names_array([self._name])
+        n = C.c_int()
+        _check(L.lib().rbx_del_n(self._client.ctx, arr, 1, C.byref(n)))
+        return n.value > 0
+
+    def isExists(self) -> bool:
+        arr, _keep = L.names_array([self._name])
+        n = C.c_int()
+        _check(L.lib().rbx_exists_n(self._client.ctx, arr, 1, C.byref(n)))
+        return n.value > 0
+
+    def rename(self, newName: str) -> None:
+        """M/RedissonObject.java:151-153 RENAME name newName"""
+        nm, _keep = self._n()
+        new, _keep2 = self._n(newName)
+        _check(L.lib().rbx_bitset_rename(self._client.ctx, nm, new))
+        self._name = newName
+
+    def _expire_keys(self):
+        return [self._name]
+
+    clear_bit = clearBit
+    set_range = setRange
+    clear_range = clearRange
+    set_indexes = setIndexes
+    get_indexes = getIndexes
+    to_byte_array = toByteArray
     is_exists = isExists
 
 

@@ -372,6 +372,38 @@ int ks_pexpiretime(Keyspace &ks, const std::string &name, int64_t *out) {
 }
 
 // =====================================================================================
+// RBitSet.length() (M/RedissonBitSet.java:428-439)
+// =====================================================================================
+// The script, in Lua 5.1 (numbers are doubles, `/` is real division, `%` is floored):
+//   local fromBit = redis.call('bitpos', KEYS[1], 1, -1);      -- first set bit of the LAST byte, or -1
+//   local toBit = 8*(fromBit/8 + 1) - fromBit % 8;
+//   for i = toBit, fromBit, -1 do if redis.call('getbit', KEYS[1], i) == 1 then return i+1; end; end;
+//   return fromBit+1
+// fromBit = 8q + r >= 0: toBit = 8(q + r/8 + 1) - r = 8q + 8, one past the last byte (reads 0), and the
+// loop walks the last byte downwards to its highest set bit, which exists: that bit's index + 1.
+// fromBit = -1 (last byte zero, empty or missing string): toBit = 8 * 0.875 - 7 = 0, the loop tests
+// bit 0 -- set only when a longer string's FIRST byte has it: returns 1 -- and then GETBIT key -1,
+// which Redis refuses: the script fails.
+int bitset_length(uint64_t len, uint8_t first, uint8_t last, int64_t *out) {
+    if (len && last) {
+        int low = 0;  // lowest set bit of the byte = the highest MSB-first index
+        while (!((last >> low) & 1)) ++low;
+        *out = (int64_t)((len - 1) * 8 + (uint64_t)(7 - low) + 1);
+        return RBX_OK;
+    }
+    if (len && (first & 0x80)) {
+        *out = 1;
+        return RBX_OK;
+    }
+    return fail(RBX_E_REDIS, kBitOffsetMsg);
+}
+
+int bitset_length_of(const uint8_t *bytes, uint64_t len, int64_t *out) {
+    if (!out || (len && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return bitset_length(len, len ? bytes[0] : 0, len ? bytes[len - 1] : 0, out);
+}
+
+// =====================================================================================
 // CRC16 / slots
 // =====================================================================================
 // XMODEM CRC16 (poly 0x1021, init 0): M/connection/CRC16.java:25-57, table built at load.

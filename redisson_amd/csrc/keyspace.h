@@ -112,6 +112,12 @@ int ks_persist(Keyspace &ks, const std::vector<std::string> &names, int *result)
 int ks_pttl(Keyspace &ks, const std::string &name, int64_t *out);
 int ks_pexpiretime(Keyspace &ks, const std::string &name, int64_t *out);
 
+// ---- RBitSet.length(): the Lua script of lengthAsync (M/RedissonBitSet.java:428-439) -----------
+// over a string of `len` bytes of which only the first and the last matter (len == 0: missing key)
+int bitset_length(uint64_t len, uint8_t first, uint8_t last, int64_t *out);
+int bitset_length_of(const uint8_t *bytes, uint64_t len, int64_t *out);
+constexpr const char *kBitOffsetMsg = "ERR bit offset is not an integer or out of range";
+
 // ---- cluster slots: M/connection/CRC16.java:25-57, M/cluster/ClusterConnectionManager.java:777-830
 uint16_t crc16(const uint8_t *bytes, size_t len);
 int calc_slot(const uint8_t *key, size_t len);

@@ -202,6 +202,7 @@ struct rbx_ctx {
     DevBuf zero_bm;
     DevBuf hll_pack;                                // contiguous registers for the RCCL merge
     DevBuf wide_table;  // first-setter table of |size| > 2^32 adds (bloom_wide_op)
+    DevBuf bits_idx, bitop_srcs;  // RBitSet: uploaded indexes, the BITOP source table
     std::vector<HllSeg> tile_cache;  // content of hll_tiles (valid when tiles_valid)
     bool tiles_valid = false;
     std::vector<FilterDesc> filt_cache;  // content of filt_table
@@ -939,7 +940,8 @@ int rbx_shutdown(rbx_ctx *c) {
                           &c->pa_p1, &c->pa_p2, &c->pa_cnt, &c->pa_bits, &c->pa_ctr, &c->pa_recs, &c->st_adds,
                           &c->st_nadds, &c->zero_bm, &c->hll_pack, &c->slot_bytes[0], &c->slot_bytes[1],
                           &c->slot_offs[0], &c->slot_offs[1], &c->st_t8, &c->fid_table,
-                          &c->hll_zero_ptrs, &c->wide_table, &c->st_fslot, &c->madd_c}) {
+                          &c->hll_zero_ptrs, &c->wide_table, &c->st_fslot, &c->madd_c, &c->bits_idx,
+                          &c->bitop_srcs}) {
             if (b->p) (void)hipFree(b->p);
             b->p = nullptr;
             b->cap = 0;
@@ -1582,8 +1584,7 @@ int rbx_exists_n(rbx_ctx *c, const rbx_name *names, uint32_t n, int *count) {
     return ks_exists(c->ks, v, count);
 }
 
-int rbx_bloom_export(rbx_ctx *c, const char *name, uint8_t *out, uint64_t cap, uint64_t *redis_len) {
-    if (!c || !name) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+static int bitmap_export(rbx_ctx *c, const std::string &name, uint8_t *out, uint64_t cap, uint64_t *redis_len) {
     std::lock_guard<std::recursive_mutex> g(c->ks.mu);
     RBX_TRY(set_device(c));
     ScratchOrder so_(c, c->stream);
@@ -1605,6 +1606,11 @@ int rbx_bloom_export(rbx_ctx *c, const char *name, uint8_t *out, uint64_t cap, u
     return RBX_OK;
 }
 
+int rbx_bloom_export(rbx_ctx *c, const char *name, uint8_t *out, uint64_t cap, uint64_t *redis_len) {
+    if (!c || !name) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return bitmap_export(c, name, out, cap, redis_len);
+}
+
 // bits a bitmap imported under `name` must cover: the string, and the config's |size|
 static uint64_t import_bits(rbx_ctx *c, const std::string &name, uint64_t len) {
     uint64_t bits = len * 8;
@@ -1613,8 +1619,7 @@ static uint64_t import_bits(rbx_ctx *c, const std::string &name, uint64_t len) {
     return std::min<uint64_t>(bits, kEngineMaxSize);
 }
 
-int rbx_bloom_import(rbx_ctx *c, const char *name, const uint8_t *bytes, uint64_t len) {
-    if (!c || !name || (len && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+static int bitmap_import(rbx_ctx *c, const std::string &name, const uint8_t *bytes, uint64_t len) {
     if (len > (1ULL << 29)) return fail(RBX_E_ILLEGAL_ARGUMENT, "string exceeds the 512 MiB Redis limit");
     std::lock_guard<std::recursive_mutex> g(c->ks.mu);
     RBX_TRY(set_device(c));
@@ -1627,6 +1632,11 @@ int rbx_bloom_import(rbx_ctx *c, const char *name, const uint8_t *bytes, uint64_
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->ks.put(name, Entry{KType::Bitmap, nullptr, b, nullptr});
     return RBX_OK;
+}
+
+int rbx_bloom_import(rbx_ctx *c, const char *name, const uint8_t *bytes, uint64_t len) {
+    if (!c || !name || (len && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return bitmap_import(c, name, bytes, len);
 }
 
 // SET name <len bytes from a device buffer> (device-resident snapshot restore)
@@ -1653,6 +1663,319 @@ int rbx_bloom_import_dev(rbx_ctx *c, const char *name, const uint8_t *d_bytes, u
     HIP_TRY(hipStreamSynchronize(st));
     c->ks.put(name, Entry{KType::Bitmap, nullptr, b, nullptr});
     return RBX_OK;
+}
+
+// ---- RBitSet over the bitmap keys (M/RedissonBitSet.java) -----------------------------------
+static constexpr uint64_t kMaxBitOffset = kEngineMaxSize;  // offsets end at 2^32 - 1
+
+static bool bad_name(const rbx_name &n) { return !n.bytes && n.len; }
+
+// the bitmap under `name`; null for a missing key (the empty string)
+static int bitset_find(rbx_ctx *c, const std::string &name, std::shared_ptr<Bitmap> *out) {
+    out->reset();
+    Entry *e = c->ks.find(name);
+    if (!e) return RBX_OK;
+    if (e->type != KType::Bitmap) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    *out = e->bm;
+    return RBX_OK;
+}
+
+// The bitmap a write reaching byte need_bytes - 1 goes to.  The key's own allocation when it
+// suffices: the write is then in place and open rbx_bloom handles keep seeing the key.  Otherwise it
+// grows geometrically (at most 2^32 bits, never below the |size| of an existing {name}:config),
+// which rebinds the entry and bumps the keyspace generation (grow_bitmap); a missing key is created.
+static int bitset_for_write(rbx_ctx *c, const std::string &name, uint64_t need_bytes, hipStream_t st,
+                            std::shared_ptr<Bitmap> *out) {
+    Entry *e = c->ks.find(name);
+    if (e && e->type != KType::Bitmap) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    if (e && e->bm->cap_bytes >= need_bytes) {
+        *out = e->bm;
+        return RBX_OK;
+    }
+    uint64_t bits = import_bits(c, name, need_bytes);
+    if (e) {
+        bits = std::min<uint64_t>(std::max<uint64_t>(bits, e->bm->cap_bytes * 16), kEngineMaxSize);
+        RBX_TRY(grow_bitmap(c, *e->bm, bits, st));
+        *out = e->bm;
+        return RBX_OK;
+    }
+    RBX_TRY(new_bitmap(c, bits, st, out));
+    c->ks.put(name, Entry{KType::Bitmap, nullptr, *out, nullptr});
+    return RBX_OK;
+}
+
+// Redis lengths of bitmaps (null = missing key: 0), eight per trip through the pinned words
+static int bitset_lens(rbx_ctx *c, const std::vector<Bitmap *> &bms, hipStream_t st, std::vector<uint64_t> *lens) {
+    lens->assign(bms.size(), 0);
+    for (size_t i0 = 0; i0 < bms.size(); i0 += 8) {
+        const size_t m = std::min<size_t>(8, bms.size() - i0);
+        for (size_t j = 0; j < m; ++j)
+            if (bms[i0 + j]) HIP_TRY(hipMemcpyAsync(c->pin_word + j, bms[i0 + j]->d_len, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t j = 0; j < m; ++j)
+            if (bms[i0 + j]) (*lens)[i0 + j] = c->pin_word[j];
+    }
+    return RBX_OK;
+}
+
+int rbx_bitset_get(rbx_ctx *c, rbx_name name, uint64_t index, int *bit) {
+    if (!c || bad_name(name) || !bit) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (index >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name_of(name), &bm));
+    *bit = 0;
+    if (!bm || (index >> 3) >= bm->cap_bytes) return RBX_OK;
+    // one byte of the string (zero past its length) into a pinned word
+    uint8_t *pin = (uint8_t *)c->pin_word;
+    HIP_TRY(hipMemcpyAsync(pin, (const uint8_t *)bm->d_words + (index >> 3), 1, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *bit = (pin[0] >> (7 - (index & 7))) & 1;
+    return RBX_OK;
+}
+
+int rbx_bitset_set(rbx_ctx *c, rbx_name name, uint64_t index, int value, int *old) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (index >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_for_write(c, name_of(name), (index >> 3) + 1, c->stream, &bm));
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    launch_bits_set_one(bm->d_words, bm->d_len, index, value != 0, d, c->stream);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    const uint64_t was = read_dev_u64(c, d, &rc);
+    if (old) *old = (int)was;
+    return rc;
+}
+
+static uint64_t max_index(const uint64_t *idx, uint64_t n) {
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; ++i) m = std::max(m, idx[i]);
+    return m;
+}
+
+// the maximum of n device indexes: one wait on `st`
+static int max_index_dev(rbx_ctx *c, const uint64_t *d_idx, uint64_t n, hipStream_t st, uint64_t *out) {
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    HIP_TRY(hipMemsetAsync(d, 0, 8, st));
+    launch_bits_max(d_idx, n, d, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->pin_word, d, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = *c->pin_word;
+    return RBX_OK;
+}
+
+// SETBIT of n device indexes whose maximum is mx
+static int bitset_scatter(rbx_ctx *c, const std::string &name, const uint64_t *d_idx, uint64_t n, uint64_t mx, int value,
+                          hipStream_t st) {
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_for_write(c, name, (mx >> 3) + 1, st, &bm));
+    launch_bits_scatter(bm->d_words, bm->d_len, bm->cap_bytes * 8, d_idx, n, value != 0, (mx >> 3) + 1, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+// GETBIT of n device indexes into device bytes
+static int bitset_gather(rbx_ctx *c, const std::string &name, const uint64_t *d_idx, uint64_t n, uint8_t *d_out,
+                         hipStream_t st) {
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name, &bm));
+    if (!bm) {
+        HIP_TRY(hipMemsetAsync(d_out, 0, n, st));
+        return RBX_OK;
+    }
+    launch_bits_gather(bm->d_words, bm->cap_bytes * 8, d_idx, n, d_out, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+int rbx_bitset_set_indexes(rbx_ctx *c, rbx_name name, const uint64_t *indexes, uint64_t n, int value) {
+    if (!c || bad_name(name) || (n && !indexes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;  // no command is sent
+    const uint64_t mx = max_index(indexes, n);
+    if (mx >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    RBX_TRY(c->bits_idx.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
+    RBX_TRY(bitset_scatter(c, name_of(name), c->bits_idx.as<uint64_t>(), n, mx, value, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+int rbx_bitset_get_indexes(rbx_ctx *c, rbx_name name, const uint64_t *indexes, uint64_t n, uint8_t *out) {
+    if (!c || bad_name(name) || (n && (!indexes || !out))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;
+    if (max_index(indexes, n) >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    RBX_TRY(c->bits_idx.reserve(n * 8));
+    RBX_TRY(c->out_bytes.reserve(n));
+    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
+    RBX_TRY(bitset_gather(c, name_of(name), c->bits_idx.as<uint64_t>(), n, c->out_bytes.as<uint8_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->out_bytes.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+int rbx_bitset_set_indexes_dev(rbx_ctx *c, rbx_name name, const uint64_t *d_indexes, uint64_t n, int value,
+                               void *stream) {
+    if (!c || bad_name(name) || (n && !d_indexes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    hipStream_t st = pick_stream(c, stream);
+    ScratchOrder so_(c, st);
+    uint64_t mx;
+    RBX_TRY(max_index_dev(c, d_indexes, n, st, &mx));
+    if (mx >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    return bitset_scatter(c, name_of(name), d_indexes, n, mx, value, st);
+}
+
+int rbx_bitset_get_indexes_dev(rbx_ctx *c, rbx_name name, const uint64_t *d_indexes, uint64_t n, uint8_t *d_out,
+                               void *stream) {
+    if (!c || bad_name(name) || (n && (!d_indexes || !d_out))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    hipStream_t st = pick_stream(c, stream);
+    ScratchOrder so_(c, st);
+    uint64_t mx;
+    RBX_TRY(max_index_dev(c, d_indexes, n, st, &mx));
+    if (mx >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    return bitset_gather(c, name_of(name), d_indexes, n, d_out, st);
+}
+
+int rbx_bitset_set_range(rbx_ctx *c, rbx_name name, uint64_t from, uint64_t to, int value) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (from >= to) return RBX_OK;  // an empty batch: no command is sent
+    if (from >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    // the batch's SETBITs below the limit run, the others fail: apply [from, 2^32), then report
+    const bool past = to > kMaxBitOffset;
+    if (past) to = kMaxBitOffset;
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_for_write(c, name_of(name), ((to - 1) >> 3) + 1, c->stream, &bm));
+    launch_bits_fill(bm->d_words, bm->d_len, from, to, value != 0, c->stream);
+    HIP_TRY(hipGetLastError());
+    return past ? fail(RBX_E_REDIS, kBitOffsetMsg) : RBX_OK;
+}
+
+int rbx_bitset_op(rbx_ctx *c, int op, rbx_name dest, const rbx_name *srcs, uint32_t nsrc, uint64_t *result_len) {
+    if (!c || bad_name(dest)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (op < RBX_BITOP_AND || op > RBX_BITOP_NOT) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITOP operation");
+    if (nsrc == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "BITOP needs a source key");
+    if (op == RBX_BITOP_NOT && nsrc != 1)
+        return fail(RBX_E_REDIS, "ERR BITOP NOT must be called with a single source key.");
+    std::vector<std::string> sn;
+    RBX_TRY(names_of(srcs, nsrc, &sn));
+    const std::string dn = name_of(dest);
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    hipStream_t st = c->stream;
+    ScratchOrder so_(c, st);
+    // every operand's type first: a wrong one leaves dest untouched
+    std::shared_ptr<Bitmap> db;
+    RBX_TRY(bitset_find(c, dn, &db));
+    std::vector<std::shared_ptr<Bitmap>> sb(nsrc);
+    std::vector<Bitmap *> bms(nsrc + 1);
+    for (uint32_t i = 0; i < nsrc; ++i) {
+        RBX_TRY(bitset_find(c, sn[i], &sb[i]));
+        bms[i] = sb[i].get();
+    }
+    bms[nsrc] = db.get();
+    std::vector<uint64_t> lens;
+    RBX_TRY(bitset_lens(c, bms, st, &lens));
+    const uint64_t out_len = *std::max_element(lens.begin(), lens.begin() + nsrc);
+    if (result_len) *result_len = out_len;
+    if (out_len == 0) {  // the empty result: DEL dest
+        c->ks.erase(dn);
+        return RBX_OK;
+    }
+    RBX_TRY(bitset_for_write(c, dn, out_len, st, &db));
+    // the table after dest has its final allocation: a source that is dest moved with it
+    std::vector<BitopSrc> tab(nsrc);
+    for (uint32_t i = 0; i < nsrc; ++i) tab[i] = BitopSrc{sb[i] ? (const uint8_t *)sb[i]->d_words : nullptr, lens[i]};
+    RBX_TRY(c->bitop_srcs.reserve(nsrc * sizeof(BitopSrc)));
+    // (a pageable source is staged by the runtime before the call returns)
+    HIP_TRY(hipMemcpyAsync(c->bitop_srcs.p, tab.data(), nsrc * sizeof(BitopSrc), hipMemcpyHostToDevice, st));
+    // the sweep also clears what a longer previous dest held past the result
+    const uint64_t span = (std::max(out_len, lens[nsrc]) + 15) & ~15ULL;
+    launch_bitop(op, (uint8_t *)db->d_words, db->d_len, c->bitop_srcs.as<BitopSrc>(), nsrc, out_len, span, st);
+    HIP_TRY(hipGetLastError());
+    if (Entry *e = c->ks.find(dn)) e->expire_at = -1;  // setKey without KEEPTTL
+    return RBX_OK;
+}
+
+int rbx_bitset_cardinality(rbx_ctx *c, rbx_name name, uint64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    return bitcount_locked(c, name_of(name), out);
+}
+
+int rbx_bitset_size(rbx_ctx *c, rbx_name name, uint64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name_of(name), &bm));
+    std::vector<uint64_t> lens;
+    RBX_TRY(bitset_lens(c, {bm.get()}, c->stream, &lens));
+    *out = lens[0] * 8;
+    return RBX_OK;
+}
+
+int rbx_bitset_length(rbx_ctx *c, rbx_name name, int64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name_of(name), &bm));
+    std::vector<uint64_t> lens;
+    RBX_TRY(bitset_lens(c, {bm.get()}, c->stream, &lens));
+    uint8_t *pin = (uint8_t *)c->pin_word;
+    pin[0] = pin[1] = 0;
+    if (lens[0]) {  // the script reads the first and the last byte only
+        const uint8_t *s = (const uint8_t *)bm->d_words;
+        HIP_TRY(hipMemcpyAsync(pin, s, 1, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(pin + 1, s + lens[0] - 1, 1, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return bitset_length(lens[0], pin[0], pin[1], out);
+}
+
+int rbx_bitset_length_of(const uint8_t *bytes, uint64_t len, int64_t *out) { return bitset_length_of(bytes, len, out); }
+
+int rbx_bitset_export_n(rbx_ctx *c, rbx_name name, uint8_t *out, uint64_t cap, uint64_t *redis_len) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return bitmap_export(c, name_of(name), out, cap, redis_len);
+}
+
+int rbx_bitset_import_n(rbx_ctx *c, rbx_name name, const uint8_t *bytes, uint64_t len) {
+    if (!c || bad_name(name) || (len && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return bitmap_import(c, name_of(name), bytes, len);
+}
+
+int rbx_bitset_rename(rbx_ctx *c, rbx_name name, rbx_name new_name) {
+    if (!c || bad_name(name) || bad_name(new_name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    return c->ks.rename(name_of(name), name_of(new_name));
 }
 
 // ---- Bloom: handles / device path ---------------------------------------------------------

@@ -262,6 +262,29 @@ void launch_bloom_wide(const KeysDev &keys, uint64_t m, uint32_t k, uint32_t *bm
                        unsigned long long *table, uint32_t tlog2, bool is_add, uint8_t *out,
                        unsigned long long *count, unsigned long long *oob, hipStream_t st);
 void launch_bitcount(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st);
+// bitset_kernels.hip -- RBitSet over bitmap strings
+struct BitopSrc {
+    const uint8_t *bytes;  // a source string (null when the key is missing)
+    uint64_t len;          // its Redis length: nothing at or past it is read
+};
+// BITOP: dst[0, out_len) := op (RBX_BITOP_* of rbx.h) over the nsrc sources of the device table
+// d_srcs, dst[out_len, span) := 0, *dst_len := out_len.  span: a multiple of 16 within dst's
+// allocation covering out_len and dst's previous length.  dst may be any of the sources.
+void launch_bitop(int op, uint8_t *dst, unsigned long long *dst_len, const BitopSrc *d_srcs, uint32_t nsrc,
+                  uint64_t out_len, uint64_t span, hipStream_t st);
+// bits [from, to) := value, from < to <= 8 * capacity; *len = max(*len, bytes up to `to`)
+void launch_bits_fill(uint32_t *words, unsigned long long *len, uint64_t from, uint64_t to, bool value, hipStream_t st);
+// SETBIT d_idx[i] value for n indexes below cap_bits; *len = max(*len, new_len)
+void launch_bits_scatter(uint32_t *words, unsigned long long *len, uint64_t cap_bits, const uint64_t *d_idx, uint64_t n,
+                         bool value, uint64_t new_len, hipStream_t st);
+// d_out[i] = GETBIT d_idx[i] (0 at or past cap_bits)
+void launch_bits_gather(const uint32_t *words, uint64_t cap_bits, const uint64_t *d_idx, uint64_t n, uint8_t *d_out,
+                        hipStream_t st);
+// *d_out = max(*d_out, max of the n indexes)
+void launch_bits_max(const uint64_t *d_idx, uint64_t n, unsigned long long *d_out, hipStream_t st);
+// SETBIT bit value; *d_old = the bit before
+void launch_bits_set_one(uint32_t *words, unsigned long long *len, uint64_t bit, bool value, unsigned long long *d_old,
+                         hipStream_t st);
 // order-independent digest of a Redis string's bytes (replica comparison); *out += digest
 void launch_digest(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st);
 // region-local gathers: 6 loads per lane inside XCD-assigned regions (partitioned-probe roofline)
