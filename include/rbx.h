@@ -234,8 +234,9 @@ int rbx_bitset_set_range(rbx_ctx *ctx, rbx_name name, uint64_t from, uint64_t to
  * (Redisson passes its own name as the first, :381-388).  *result_len (nullable) = the reply.  A
  * result of length 0 deletes dest; otherwise dest is overwritten and loses its timeout (setKey
  * without KEEPTTL).  NOT takes one source (else RBX_E_REDIS).  A {name}:config hash as dest or
- * source gives RBX_E_WRONGTYPE with dest untouched.  The one divergence from Redis: an HLL key is
- * a string there and a legal BITOP operand; here it is refused with RBX_E_WRONGTYPE. */
+ * source gives RBX_E_WRONGTYPE with dest untouched.  The first of two divergences from Redis (the
+ * second is BITFIELD's offset limit, below): an HLL key is a string there and a legal BITOP
+ * operand; here it is refused with RBX_E_WRONGTYPE. */
 enum { RBX_BITOP_AND = 0, RBX_BITOP_OR = 1, RBX_BITOP_XOR = 2, RBX_BITOP_NOT = 3 };
 int rbx_bitset_op(rbx_ctx *ctx, int op, rbx_name dest, const rbx_name *srcs, uint32_t nsrc, uint64_t *result_len);
 /* cardinality() = BITCOUNT  :482-484;  size() = STRLEN * 8  :472-474 */
@@ -254,6 +255,50 @@ int rbx_bitset_export_n(rbx_ctx *ctx, rbx_name name, uint8_t *out, uint64_t cap,
 int rbx_bitset_import_n(rbx_ctx *ctx, rbx_name name, const uint8_t *bytes, uint64_t len);
 /* rename(newName) = RENAME name newName, `name` alone (M/RedissonObject.java:151-153) */
 int rbx_bitset_rename(rbx_ctx *ctx, rbx_name name, rbx_name new_name);
+/* getSigned / setSigned / incrementAndGetSigned, the Unsigned three, and the Byte / Short / Integer /
+ * Long forms (i8 / i16 / i32 / i64) -- M/RedissonBitSet.java:71-254: each is one
+ * BITFIELD name GET|SET|INCRBY <i|u><size> <offset> [value] with the default OVERFLOW WRAP
+ * ([redis-7.2] bitops.c bitfieldGeneric).
+ *   Layout  the field is `size` bits from bit `offset`, the bit at `offset` its most significant;
+ *           `offset` is a plain bit offset, fields need not be aligned (an i64 at offset 2 covers 9 bytes).
+ *   Types   is_signed: sizes 1..64, else 1..63.  A larger size is RBX_E_ILLEGAL_ARGUMENT ("Size can't
+ *           be greater than 64 bits" / "... 63 bits", Redisson's own checks :72-73, :99-100); size < 1
+ *           reaches Redis and is RBX_E_REDIS ("ERR Invalid bitfield type...").
+ *   GET     bits at or past the string's end, and a missing key, read as zero; nothing is created
+ *           or grown; the reply is sign-extended for i, zero-extended for u.
+ *   SET     the reply is the old value; the field becomes value mod 2^size.
+ *   INCRBY  the field becomes (old + value) mod 2^size -- signed fields wrap in two's complement, a
+ *           negative increment on an unsigned field wraps too; the reply is the new value.
+ *   Growth  SET and INCRBY (even by 0) create a missing key and grow the string to
+ *           ((offset + size - 1) >> 3) + 1 bytes, in place when the allocation suffices; the
+ *           key's timeout stays.
+ *   Limit   offset >= 2^32 is RBX_E_REDIS "ERR bit offset is not an integer or out of range".
+ *           DIVERGENCE (the second, beside BITOP on an HLL key above): so is offset + size > 2^32.
+ *           Redis checks the start offset only; the engine's bitmaps end at 2^32 bits.
+ *   Batch   rbx_bitset_fields is one BITFIELD with n sub-commands of one operation and type.  Every
+ *           sub-command is checked before any runs (an illegal offset fails the call with nothing
+ *           changed or created); then they take effect in array order, exactly as n single calls,
+ *           and replies[i] is what single call i would have returned.  n = 0 sends nothing.
+ *           `values` is ignored for GET (may be NULL); `replies` may be NULL for SET and INCRBY.
+ *           rbx_bitset_set_indexes(idx, v) and a SET of unsigned size-1 fields at idx leave the
+ *           same string.
+ *   Paths   GET: one lane per field.  SET / INCRBY with every offset a multiple of size (fields then
+ *           equal or disjoint): INCRBY without replies and size a divisor of 64 is one atomic
+ *           compare-and-swap loop per element; every other case sorts (slot, position) by slot and
+ *           gives each slot one lane that walks its sub-commands in order.  Any other SET / INCRBY
+ *           batch runs on one lane, serially: partly overlapping fields make the order total.
+ * The _dev form takes device arrays and enqueues on `stream`; like rbx_bitset_set_indexes_dev it
+ * waits once on the stream, for the batch's check result (the largest offset, and whether every
+ * offset is aligned). */
+enum { RBX_FIELD_GET = 0, RBX_FIELD_SET = 1, RBX_FIELD_INCRBY = 2 };
+int rbx_bitset_field(rbx_ctx *ctx, rbx_name name, int op, int is_signed, int size, uint64_t offset, int64_t value,
+                     int64_t *reply);
+int rbx_bitset_fields(rbx_ctx *ctx, rbx_name name, int op, int is_signed, int size, const uint64_t *offsets,
+                      const int64_t *values, uint64_t n, int64_t *replies);
+int rbx_bitset_fields_dev(rbx_ctx *ctx, rbx_name name, int op, int is_signed, int size, const uint64_t *d_offsets,
+                          const int64_t *d_values, uint64_t n, int64_t *d_replies, void *stream);
+/* GET over a host string, no context (as rbx_bitset_length_of) */
+int rbx_bitset_field_of(const uint8_t *bytes, uint64_t len, int is_signed, int size, uint64_t offset, int64_t *out);
 
 /* ---- replicas ("replicate the bitmap, split contains keys across GPUs") ---------
  * Redisson serves contains' GETBITs as reads that may go to a replica

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("RBX_LIB_PATH") or os.path.join(_HERE, "librbx.so")  #
 u8p = C.POINTER(C.c_uint8)
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
+i64p = C.POINTER(C.c_int64)
 ullp = C.POINTER(C.c_ulonglong)
 vp = C.c_void_p
 
@@ -71,6 +72,7 @@ RBX_E_REDIS = -9
 RBX_E_TIMEOUT = -10
 
 RBX_BITOP_AND, RBX_BITOP_OR, RBX_BITOP_XOR, RBX_BITOP_NOT = 0, 1, 2, 3
+RBX_FIELD_GET, RBX_FIELD_SET, RBX_FIELD_INCRBY = 0, 1, 2
 
 # name -> (restype, argtypes); every function declared in include/rbx.h
 SIGNATURES = {
@@ -217,6 +219,10 @@ SIGNATURES = {
     "rbx_bitset_export_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64, u64p]),
     "rbx_bitset_import_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64]),
     "rbx_bitset_rename": (C.c_int, [vp, RbxName, RbxName]),
+    "rbx_bitset_field": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, i64p]),
+    "rbx_bitset_fields": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, u64p, i64p, C.c_uint64, i64p]),
+    "rbx_bitset_fields_dev": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp, vp]),
+    "rbx_bitset_field_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, i64p]),
     "rbx_bench_gather": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     "rbx_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "rbx_bench_stream_geometry": (C.c_int, [vp, u64p]),

@@ -388,6 +388,143 @@ class RBitSet(_Expirable):
         nm, _keep = self._n()
         _check(L.lib().rbx_bitset_get_indexes_dev(self._client.ctx, nm, d_indexes, int(n), d_out, stream))
 
+    # ---- typed fields: BITFIELD GET / SET / INCRBY (:71-254) --------------------------------
+    @staticmethod
+    def _java(value: int, bits: int, what: str) -> int:
+        """a Java argument of a `bits`-wide integral type"""
+        value = int(value)
+        if not -(1 << (bits - 1)) <= value < (1 << (bits - 1)):
+            raise IllegalArgumentException(f"{what} {value} is outside the Java type's range ({bits} bits)")
+        return value
+
+    def _field(self, op: int, signed: bool, size: int, offset: int, value: int = 0) -> int:
+        nm, _keep = self._n()
+        size = self._java(size, 32, "size")
+        offset = self._java(offset, 64, "offset") & 0xFFFFFFFFFFFFFFFF  # a negative long is past the limit too
+        reply = C.c_int64()
+        _check(L.lib().rbx_bitset_field(self._client.ctx, nm, op, int(signed), size, offset,
+                                        self._java(value, 64, "value"), C.byref(reply)))
+        return int(reply.value)
+
+    def getSigned(self, size: int, offset: int) -> int:
+        """:71-77 BITFIELD GET i<size> offset"""
+        return self._field(L.RBX_FIELD_GET, True, size, offset)
+
+    def setSigned(self, size: int, offset: int, value: int) -> int:
+        """:80-86 BITFIELD SET i<size> offset value -> the old value"""
+        return self._field(L.RBX_FIELD_SET, True, size, offset, value)
+
+    def incrementAndGetSigned(self, size: int, offset: int, increment: int) -> int:
+        """:89-95 BITFIELD INCRBY i<size> offset increment -> the new value"""
+        return self._field(L.RBX_FIELD_INCRBY, True, size, offset, increment)
+
+    def getUnsigned(self, size: int, offset: int) -> int:
+        """:98-104 BITFIELD GET u<size> offset"""
+        return self._field(L.RBX_FIELD_GET, False, size, offset)
+
+    def setUnsigned(self, size: int, offset: int, value: int) -> int:
+        """:107-113"""
+        return self._field(L.RBX_FIELD_SET, False, size, offset, value)
+
+    def incrementAndGetUnsigned(self, size: int, offset: int, increment: int) -> int:
+        """:116-122"""
+        return self._field(L.RBX_FIELD_INCRBY, False, size, offset, increment)
+
+    def getByte(self, offset: int) -> int:
+        """:185-200 the i8 forms (Java byte)"""
+        return self._field(L.RBX_FIELD_GET, True, 8, offset)
+
+    def setByte(self, offset: int, value: int) -> int:
+        return self._field(L.RBX_FIELD_SET, True, 8, offset, self._java(value, 8, "value"))
+
+    def incrementAndGetByte(self, offset: int, increment: int) -> int:
+        return self._field(L.RBX_FIELD_INCRBY, True, 8, offset, self._java(increment, 8, "increment"))
+
+    def getShort(self, offset: int) -> int:
+        """:203-218 the i16 forms (Java short)"""
+        return self._field(L.RBX_FIELD_GET, True, 16, offset)
+
+    def setShort(self, offset: int, value: int) -> int:
+        return self._field(L.RBX_FIELD_SET, True, 16, offset, self._java(value, 16, "value"))
+
+    def incrementAndGetShort(self, offset: int, increment: int) -> int:
+        return self._field(L.RBX_FIELD_INCRBY, True, 16, offset, self._java(increment, 16, "increment"))
+
+    def getInteger(self, offset: int) -> int:
+        """:221-236 the i32 forms (Java int)"""
+        return self._field(L.RBX_FIELD_GET, True, 32, offset)
+
+    def setInteger(self, offset: int, value: int) -> int:
+        return self._field(L.RBX_FIELD_SET, True, 32, offset, self._java(value, 32, "value"))
+
+    def incrementAndGetInteger(self, offset: int, increment: int) -> int:
+        return self._field(L.RBX_FIELD_INCRBY, True, 32, offset, self._java(increment, 32, "increment"))
+
+    def getLong(self, offset: int) -> int:
+        """:239-254 the i64 forms (Java long)"""
+        return self._field(L.RBX_FIELD_GET, True, 64, offset)
+
+    def setLong(self, offset: int, value: int) -> int:
+        return self._field(L.RBX_FIELD_SET, True, 64, offset, value)
+
+    def incrementAndGetLong(self, offset: int, increment: int) -> int:
+        return self._field(L.RBX_FIELD_INCRBY, True, 64, offset, increment)
+
+    @staticmethod
+    def _values(values, n: int) -> np.ndarray:
+        a = np.asarray(values)
+        if a.size and (a.dtype.kind not in "iu" or (a.dtype == np.uint64 and int(a.max()) >= 1 << 63)):
+            raise IllegalArgumentException("field values are Java longs")
+        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        if a.size != n:
+            raise IllegalArgumentException("one value per offset")
+        return a
+
+    def _fields(self, op: int, signed: bool, size: int, offsets, values, replies: bool):
+        """one BITFIELD of len(offsets) sub-commands of one operation and type (rbx_bitset_fields)"""
+        offs = self._indexes(offsets)
+        vals = None if values is None else self._values(values, offs.size)
+        out = np.zeros(max(offs.size, 1), np.int64) if replies else None
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_fields(self._client.ctx, nm, op, int(signed), self._java(size, 32, "size"),
+                                         offs.ctypes.data_as(L.u64p),
+                                         None if vals is None else vals.ctypes.data_as(L.i64p), offs.size,
+                                         None if out is None else out.ctypes.data_as(L.i64p)))
+        return None if out is None else out[: offs.size]
+
+    def getFields(self, size: int, offsets, signed: bool = True) -> np.ndarray:
+        """One GET per offset, in one BITFIELD -- engine extension, like getIndexes."""
+        return self._fields(L.RBX_FIELD_GET, signed, size, offsets, None, True)
+
+    def setFields(self, size: int, offsets, values, signed: bool = True, replies: bool = True):
+        """One SET per (offset, value), in array order -> the old values (int64), or None."""
+        return self._fields(L.RBX_FIELD_SET, signed, size, offsets, values, replies)
+
+    def incrementFields(self, size: int, offsets, increments, signed: bool = True, replies: bool = True):
+        """One INCRBY per (offset, increment), in array order -> the new values (int64), or None."""
+        return self._fields(L.RBX_FIELD_INCRBY, signed, size, offsets, increments, replies)
+
+    def _fields_dev(self, op, signed, size, d_offsets, d_values, n, d_replies, stream) -> None:
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_fields_dev(self._client.ctx, nm, op, int(signed), self._java(size, 32, "size"),
+                                             d_offsets, d_values, int(n), d_replies, stream))
+
+    def getFieldsDev(self, size: int, d_offsets: int, n: int, d_replies: int, signed: bool = True,
+                     stream: int | None = None) -> None:
+        """getFields over device arrays: n u64 offsets, n i64 replies (rbx_bitset_fields_dev)."""
+        self._fields_dev(L.RBX_FIELD_GET, signed, size, d_offsets, None, n, d_replies, stream)
+
+    def setFieldsDev(self, size: int, d_offsets: int, d_values: int, n: int, d_replies: int | None = None,
+                     signed: bool = True, stream: int | None = None) -> None:
+        """setFields over device arrays; d_replies (n i64) may be None."""
+        self._fields_dev(L.RBX_FIELD_SET, signed, size, d_offsets, d_values, n, d_replies, stream)
+
+    def incrementFieldsDev(self, size: int, d_offsets: int, d_increments: int, n: int, d_replies: int | None = None,
+                           signed: bool = True, stream: int | None = None) -> None:
+        """incrementFields over device arrays; without d_replies an aligned batch of a size dividing 64
+        is one atomic per element (packed counters)."""
+        self._fields_dev(L.RBX_FIELD_INCRBY, signed, size, d_offsets, d_increments, n, d_replies, stream)
+
     # ---- whole-string reads -----------------------------------------------------------------
     def cardinality(self) -> int:
         """:482-484 BITCOUNT"""
@@ -479,6 +616,30 @@ class RBitSet(_Expirable):
     clear_range = clearRange
     set_indexes = setIndexes
     get_indexes = getIndexes
+    get_signed = getSigned
+    set_signed = setSigned
+    increment_and_get_signed = incrementAndGetSigned
+    get_unsigned = getUnsigned
+    set_unsigned = setUnsigned
+    increment_and_get_unsigned = incrementAndGetUnsigned
+    get_byte = getByte
+    set_byte = setByte
+    increment_and_get_byte = incrementAndGetByte
+    get_short = getShort
+    set_short = setShort
+    increment_and_get_short = incrementAndGetShort
+    get_integer = getInteger
+    set_integer = setInteger
+    increment_and_get_integer = incrementAndGetInteger
+    get_long = getLong
+    set_long = setLong
+    increment_and_get_long = incrementAndGetLong
+    get_fields = getFields
+    set_fields = setFields
+    increment_fields = incrementFields
+    get_fields_dev = getFieldsDev
+    set_fields_dev = setFieldsDev
+    increment_fields_dev = incrementFieldsDev
     to_byte_array = toByteArray
     is_exists = isExists
 

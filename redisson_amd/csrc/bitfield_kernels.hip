@@ -1,0 +1,282 @@
+// bitfield_kernels.hip -- RBitSet's typed fields (M/RedissonBitSet.java:71-254): every call is one
+// Redis `BITFIELD key GET|SET|INCRBY <i|u><size> <offset> [value]` with the default OVERFLOW WRAP
+// ([redis-7.2] bitops.c bitfieldGeneric, restated in DESIGN section 11).  A field is `size` bits of
+// the string from bit `offset`, most significant bit first, at any alignment.
+//
+// The bitmap is addressed here as aligned 64-bit words.  A word's bytes are the string's bytes in
+// order, so the byte-swapped word holds string bit 64q + j at position 63 - j: a field is a run of
+// adjacent bits of at most two byte-swapped words, and integer arithmetic on that run is arithmetic
+// on the field.  The allocation is a multiple of 256 bytes, so an aligned word lies inside it or
+// wholly past it; the kernels keep the bytes from the string's length to the allocation's end zero
+// (they write only inside fields the host sized the string for).
+// M/ = /root/reference/redisson/src/main/java/org/redisson/
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "../../include/rbx.h"
+#include "bloom_common.h"
+#include "rbx_kernels.h"
+
+namespace rbx {
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ u64 field_mask(uint32_t size) { return size >= 64 ? ~0ULL : (1ULL << size) - 1; }
+
+// the reply form of a field's bits: sign-extended for i<size>, as they are for u<size>
+__device__ __forceinline__ int64_t field_extend(u64 v, uint32_t size, uint32_t is_signed) {
+    if (is_signed && size < 64 && ((v >> (size - 1)) & 1)) v |= ~0ULL << size;
+    return (int64_t)v;
+}
+
+// word q of the string in big-endian bit order; zero at or past the allocation
+__device__ __forceinline__ u64 ld_be(const u64 *w, uint64_t q, uint64_t cap_words) {
+    return q < cap_words ? __builtin_bswap64(w[q]) : 0ULL;
+}
+
+// the field's bits, zero-extended
+__device__ __forceinline__ u64 field_load(const u64 *w, uint64_t cap_words, uint64_t off, uint32_t size) {
+    const uint64_t q = off >> 6;
+    const uint32_t sh = (uint32_t)(off & 63);
+    u64 hi = ld_be(w, q, cap_words) << sh;
+    if (sh + size > 64) hi |= ld_be(w, q + 1, cap_words) >> (64 - sh);  // sh >= 1 here
+    return hi >> (64 - size);
+}
+
+// field := v (already below 2^size), the field inside the allocation.  ATOMIC: other lanes write
+// other fields of the same words at the same time, so the bits go out as atomicAnd + atomicOr.
+template <bool ATOMIC> __device__ __forceinline__ void word_put(u64 *p, u64 m, u64 bits) {
+    if (ATOMIC) {
+        atomicAnd(p, __builtin_bswap64(~m));
+        atomicOr(p, __builtin_bswap64(bits));
+    } else {
+        *p = __builtin_bswap64((__builtin_bswap64(*p) & ~m) | bits);
+    }
+}
+
+template <bool ATOMIC> __device__ __forceinline__ void field_store(u64 *w, uint64_t off, uint32_t size, u64 v) {
+    const uint64_t q = off >> 6;
+    const uint32_t sh = (uint32_t)(off & 63);
+    const u64 m = field_mask(size) << (64 - size), top = v << (64 - size);  // the field at a word's top
+    word_put<ATOMIC>(w + q, m >> sh, top >> sh);
+    if (sh + size > 64) word_put<ATOMIC>(w + q + 1, m << (64 - sh), top << (64 - sh));
+}
+
+// one sub-command on the field at `off`: the reply, the field updated in place
+template <bool ATOMIC>
+__device__ __forceinline__ int64_t field_apply(u64 *w, uint64_t cap_words, int op, uint32_t is_signed, uint32_t size,
+                                               uint64_t off, int64_t value) {
+    const u64 old = field_load(w, cap_words, off, size);
+    if (op == RBX_FIELD_GET) return field_extend(old, size, is_signed);
+    const u64 now = (op == RBX_FIELD_SET ? (u64)value : old + (u64)value) & field_mask(size);
+    field_store<ATOMIC>(w, off, size, now);
+    return field_extend(op == RBX_FIELD_SET ? old : now, size, is_signed);
+}
+
+// ---------------------------------------------------------------------------------
+// 1. The batch's check: out[0] = max(out[0], max offset), out[1] |= (some offset % size != 0).
+// The host adds `size` to the maximum (every sub-command has the same type) for the offset
+// limit, the growth and the new length, and picks the path from the alignment word.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fields_check(const uint64_t *__restrict__ offs, uint64_t n, uint32_t size,
+                                                      u64 *out) {
+    __shared__ u64 s_max[4];
+    __shared__ uint32_t s_mis[4];
+    u64 m = 0;
+    uint32_t mis = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const u64 o = offs[i];
+        m = max(m, o);
+        mis |= (uint32_t)(o % size != 0);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        m = max(m, (u64)__shfl_down(m, d, 64));
+        mis |= (uint32_t)__shfl_down((int)mis, d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_max[threadIdx.x >> 6] = m;
+        s_mis[threadIdx.x >> 6] = mis;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicMax(out, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+        if (s_mis[0] | s_mis[1] | s_mis[2] | s_mis[3]) atomicOr(out + 1, 1ULL);
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// 2. GET, one lane per element, any offsets.  Nothing at or past the allocation is read.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fields_get(const u64 *__restrict__ w, uint64_t cap_words,
+                                                    const uint64_t *__restrict__ offs, uint64_t n, uint32_t size,
+                                                    uint32_t is_signed, int64_t *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = field_extend(field_load(w, cap_words, offs[i], size), size, is_signed);
+}
+
+// ---------------------------------------------------------------------------------
+// 3. INCRBY without replies on aligned fields whose size divides 64: such a field lies inside one
+// aligned word, and sums modulo 2^size commute, so the elements run in any order and duplicates
+// need no grouping -- one compare-and-swap loop per element.  The addition is done on the
+// byte-swapped word, in the field's own (big-endian) bit positions.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fields_incr_atomic(u64 *w, u64 *len, uint64_t cap_bits,
+                                                            const uint64_t *__restrict__ offs,
+                                                            const int64_t *__restrict__ incs, uint64_t n, uint32_t size,
+                                                            uint64_t new_len) {
+    const u64 mask = field_mask(size);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t off = offs[i];
+        const u64 inc = (u64)incs[i] & mask;
+        if (inc == 0 || off + size > cap_bits) continue;  // (the host sized the bitmap: the latter is never taken)
+        const uint32_t shift = 64 - (uint32_t)(off & 63) - size;
+        u64 *p = w + (off >> 6);
+        u64 seen = *p, expect;
+        do {
+            expect = seen;
+            const u64 be = __builtin_bswap64(expect);
+            const u64 f = ((be >> shift) + inc) & mask;
+            seen = atomicCAS(p, expect, __builtin_bswap64((be & ~(mask << shift)) | (f << shift)));
+        } while (seen != expect);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(len, (u64)new_len);
+}
+
+// ---------------------------------------------------------------------------------
+// 4. Every other aligned SET / INCRBY: the (slot, position) pairs arrive stably sorted by slot
+// (slot = offset / size), so a run of equal slots lists one field's sub-commands in array order.
+// The lane at a run's head reads the field once, walks the run writing each reply, and stores
+// the final value once.  Fields are pairwise disjoint and each has one writer, but they share
+// words: the store is atomicAnd + atomicOr.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fields_slots(const uint64_t *__restrict__ offs, uint32_t n, uint32_t size,
+                                                      uint32_t *__restrict__ slot, uint32_t *__restrict__ pos) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        slot[i] = (uint32_t)(offs[i] / size);  // offsets are below 2^32
+        pos[i] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fields_runs(u64 *w, u64 *len, uint64_t cap_bits, int op, uint32_t is_signed,
+                                                     uint32_t size, const uint32_t *__restrict__ slot,
+                                                     const uint32_t *__restrict__ pos, uint32_t n,
+                                                     const int64_t *__restrict__ values, int64_t *__restrict__ replies,
+                                                     uint64_t new_len) {
+    const u64 mask = field_mask(size);
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t s = slot[i];
+        if (i > 0 && slot[i - 1] == s) continue;  // not a run's head
+        const uint64_t off = (uint64_t)s * size;
+        if (off + size > cap_bits) continue;  // (the host sized the bitmap: never taken)
+        u64 cur = field_load(w, cap_bits >> 6, off, size);
+        uint32_t j = i;
+        do {
+            const uint32_t p = pos[j];
+            const u64 v = (u64)values[p];
+            if (op == RBX_FIELD_SET) {
+                if (replies) replies[p] = field_extend(cur, size, is_signed);
+                cur = v & mask;
+            } else {
+                cur = (cur + v) & mask;
+                if (replies) replies[p] = field_extend(cur, size, is_signed);
+            }
+            ++j;
+        } while (j < n && slot[j] == s);
+        field_store<true>(w, off, size, cur);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(len, (u64)new_len);
+}
+
+// ---------------------------------------------------------------------------------
+// 5. The exact path: one lane runs the sub-commands in array order.  Unaligned fields may partly
+// overlap, so a sub-command's reply and result depend on every earlier one.  Also the single call.
+// ---------------------------------------------------------------------------------
+__global__ void k_fields_serial(u64 *w, u64 *len, uint64_t cap_bits, int op, uint32_t is_signed, uint32_t size,
+                                const uint64_t *__restrict__ offs, const int64_t *__restrict__ values, uint64_t n,
+                                int64_t *__restrict__ replies, uint64_t new_len) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t off = offs[i];
+        if (off + size > cap_bits) continue;  // (never taken)
+        const int64_t r = field_apply<false>(w, cap_bits >> 6, op, is_signed, size, off, values[i]);
+        if (replies) replies[i] = r;
+    }
+    atomicMax(len, (u64)new_len);
+}
+
+__global__ void k_field_one(u64 *w, u64 *len, uint64_t cap_bits, int op, uint32_t is_signed, uint32_t size,
+                            uint64_t off, int64_t value, int64_t *reply, uint64_t new_len) {
+    if (off + size <= cap_bits) *reply = field_apply<false>(w, cap_bits >> 6, op, is_signed, size, off, value);
+    atomicMax(len, (u64)new_len);
+}
+
+// ---------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------
+void launch_fields_check(const uint64_t *d_offs, uint64_t n, int size, unsigned long long *d_out2, hipStream_t st) {
+    hipLaunchKernelGGL(k_fields_check, dim3(grid_for(n, 512)), dim3(256), 0, st, d_offs, n, (uint32_t)size, d_out2);
+}
+
+void launch_fields_get(const uint32_t *words, uint64_t cap_bytes, const uint64_t *d_offs, uint64_t n, int size,
+                       int is_signed, int64_t *d_out, hipStream_t st) {
+    hipLaunchKernelGGL(k_fields_get, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, (const u64 *)words, cap_bytes / 8,
+                       d_offs, n, (uint32_t)size, is_signed ? 1u : 0u, d_out);
+}
+
+void launch_fields_incr_atomic(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, const uint64_t *d_offs,
+                               const int64_t *d_incs, uint64_t n, int size, uint64_t new_len, hipStream_t st) {
+    hipLaunchKernelGGL(k_fields_incr_atomic, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, (u64 *)words, len,
+                       cap_bytes * 8, d_offs, d_incs, n, (uint32_t)size, new_len);
+}
+
+// the four u32 arrays of a chunk of n elements, then rocPRIM's temporary storage
+static size_t fields_arrays_bytes(uint32_t n) { return (((size_t)n * 4 + 255) & ~(size_t)255) * 4; }
+
+int fields_grouped_scratch_bytes(uint32_t n, int slot_bits, size_t *bytes) {
+    size_t temp = 0;
+    uint32_t *nil = nullptr;
+    const hipError_t e = rocprim::radix_sort_pairs(nullptr, temp, nil, nil, nil, nil, (size_t)n, 0u,
+                                                   (unsigned)slot_bits, (hipStream_t) nullptr);
+    if (e != hipSuccess) return (int)e;
+    *bytes = fields_arrays_bytes(n) + temp;
+    return 0;
+}
+
+int launch_fields_grouped(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed,
+                          int size, const uint64_t *d_offs, const int64_t *d_values, uint32_t n, int64_t *d_replies,
+                          uint64_t new_len, int slot_bits, void *d_scratch, size_t scratch_bytes, hipStream_t st) {
+    const size_t one = fields_arrays_bytes(n) / 4;
+    uint8_t *s = (uint8_t *)d_scratch;
+    uint32_t *slot_in = (uint32_t *)s, *slot_out = (uint32_t *)(s + one);
+    uint32_t *pos_in = (uint32_t *)(s + 2 * one), *pos_out = (uint32_t *)(s + 3 * one);
+    size_t temp = scratch_bytes - 4 * one;
+    hipLaunchKernelGGL(k_fields_slots, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_offs, n, (uint32_t)size,
+                       slot_in, pos_in);
+    // stable, stream-ordered, over the slot's significant bits only
+    const hipError_t e = rocprim::radix_sort_pairs(s + 4 * one, temp, slot_in, slot_out, pos_in, pos_out, (size_t)n,
+                                                   0u, (unsigned)slot_bits, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_fields_runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, (u64 *)words, len, cap_bytes * 8,
+                       op, is_signed ? 1u : 0u, (uint32_t)size, slot_out, pos_out, n, d_values, d_replies, new_len);
+    return 0;
+}
+
+void launch_fields_serial(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
+                          const uint64_t *d_offs, const int64_t *d_values, uint64_t n, int64_t *d_replies,
+                          uint64_t new_len, hipStream_t st) {
+    hipLaunchKernelGGL(k_fields_serial, dim3(1), dim3(1), 0, st, (u64 *)words, len, cap_bytes * 8, op,
+                       is_signed ? 1u : 0u, (uint32_t)size, d_offs, d_values, n, d_replies, new_len);
+}
+
+void launch_field_one(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
+                      uint64_t offset, int64_t value, int64_t *d_reply, uint64_t new_len, hipStream_t st) {
+    hipLaunchKernelGGL(k_field_one, dim3(1), dim3(1), 0, st, (u64 *)words, len, cap_bytes * 8, op, is_signed ? 1u : 0u,
+                       (uint32_t)size, offset, value, d_reply, new_len);
+}
+
+}  // namespace rbx

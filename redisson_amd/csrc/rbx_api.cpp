@@ -203,6 +203,7 @@ struct rbx_ctx {
     DevBuf hll_pack;                                // contiguous registers for the RCCL merge
     DevBuf wide_table;  // first-setter table of |size| > 2^32 adds (bloom_wide_op)
     DevBuf bits_idx, bitop_srcs;  // RBitSet: uploaded indexes, the BITOP source table
+    DevBuf fld_vals, fld_out, fld_sort;  // BITFIELD: uploaded values, replies, the grouped path's sort scratch
     std::vector<HllSeg> tile_cache;  // content of hll_tiles (valid when tiles_valid)
     bool tiles_valid = false;
     std::vector<FilterDesc> filt_cache;  // content of filt_table
@@ -941,7 +942,7 @@ int rbx_shutdown(rbx_ctx *c) {
                           &c->st_nadds, &c->zero_bm, &c->hll_pack, &c->slot_bytes[0], &c->slot_bytes[1],
                           &c->slot_offs[0], &c->slot_offs[1], &c->st_t8, &c->fid_table,
                           &c->hll_zero_ptrs, &c->wide_table, &c->st_fslot, &c->madd_c, &c->bits_idx,
-                          &c->bitop_srcs}) {
+                          &c->bitop_srcs, &c->fld_vals, &c->fld_out, &c->fld_sort}) {
             if (b->p) (void)hipFree(b->p);
             b->p = nullptr;
             b->cap = 0;
@@ -1976,6 +1977,185 @@ int rbx_bitset_rename(rbx_ctx *c, rbx_name name, rbx_name new_name) {
     if (!c || bad_name(name) || bad_name(new_name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
     std::lock_guard<std::recursive_mutex> g(c->ks.mu);
     return c->ks.rename(name_of(name), name_of(new_name));
+}
+
+// ---- RBitSet's typed fields: BITFIELD GET / SET / INCRBY (M/RedissonBitSet.java:71-254) -------
+// the type's checks: Redisson's own (:72-73, :99-100), then the one Redis makes
+static int field_type_check(int op, int is_signed, int size) {
+    if (op < RBX_FIELD_GET || op > RBX_FIELD_INCRBY) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITFIELD operation");
+    if (is_signed && size > 64) return fail(RBX_E_ILLEGAL_ARGUMENT, "Size can't be greater than 64 bits");
+    if (!is_signed && size > 63) return fail(RBX_E_ILLEGAL_ARGUMENT, "Size can't be greater than 63 bits");
+    if (size < 1)
+        return fail(RBX_E_REDIS,
+                    "ERR Invalid bitfield type. Use something like i16 u8. Note that u64 is not supported but i64 is.");
+    return RBX_OK;
+}
+
+// the offset limit for fields of `size` bits whose largest offset is mx: the whole field lies below bit 2^32
+static int field_range_check(uint64_t mx, int size) {
+    if (mx >= kMaxBitOffset || mx + (uint64_t)size > kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    return RBX_OK;
+}
+
+// GET on a host string: the field's bits from the bytes below len, zero past them
+static int64_t field_of_bytes(const uint8_t *bytes, uint64_t len, int is_signed, int size, uint64_t offset) {
+    uint64_t v = 0;
+    for (int j = 0; j < size; ++j) {
+        const uint64_t b = offset + (uint64_t)j;
+        const uint64_t bit = (b >> 3) < len ? (bytes[b >> 3] >> (7 - (b & 7))) & 1 : 0;
+        v = (v << 1) | bit;
+    }
+    if (is_signed && size < 64 && ((v >> (size - 1)) & 1)) v |= ~0ULL << size;
+    return (int64_t)v;
+}
+
+int rbx_bitset_field_of(const uint8_t *bytes, uint64_t len, int is_signed, int size, uint64_t offset, int64_t *out) {
+    if ((len && !bytes) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(field_type_check(RBX_FIELD_GET, is_signed, size));
+    RBX_TRY(field_range_check(offset, size));
+    *out = field_of_bytes(bytes, len, is_signed, size, offset);
+    return RBX_OK;
+}
+
+int rbx_bitset_field(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, uint64_t offset, int64_t value,
+                     int64_t *reply) {
+    if (!c || bad_name(name) || (op == RBX_FIELD_GET && !reply)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(field_type_check(op, is_signed, size));
+    RBX_TRY(field_range_check(offset, size));
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    if (op == RBX_FIELD_GET) {
+        RBX_TRY(bitset_find(c, name_of(name), &bm));
+        // the field's covering bytes inside the allocation (zero past the string's length), at most 9
+        uint8_t *pin = (uint8_t *)c->pin_word;
+        const uint64_t first = offset >> 3, last = (offset + size - 1) >> 3;
+        uint64_t nb = 0;
+        if (bm && first < bm->cap_bytes) {
+            nb = std::min<uint64_t>(last + 1, bm->cap_bytes) - first;
+            HIP_TRY(hipMemcpyAsync(pin, (const uint8_t *)bm->d_words + first, nb, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        *reply = field_of_bytes(pin, nb, is_signed, size, offset & 7);
+        return RBX_OK;
+    }
+    const uint64_t need = ((offset + size - 1) >> 3) + 1;
+    RBX_TRY(bitset_for_write(c, name_of(name), need, c->stream, &bm));
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    launch_field_one(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, offset, value, (int64_t *)d, need,
+                     c->stream);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    const uint64_t r = read_dev_u64(c, d, &rc);
+    if (reply) *reply = (int64_t)r;
+    return rc;
+}
+
+// A checked batch over device arrays: mx = the largest offset, aligned = every offset is a multiple
+// of size.  GET gathers; an unaligned SET / INCRBY runs serially (partly overlapping fields make
+// the order total); an aligned INCRBY without replies whose size divides 64 is one atomic loop per
+// element; every other aligned batch is sorted by slot and walked run by run.
+static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed, int size, const uint64_t *d_offs,
+                      const int64_t *d_values, uint64_t n, int64_t *d_replies, uint64_t mx, bool aligned,
+                      hipStream_t st) {
+    std::shared_ptr<Bitmap> bm;
+    if (op == RBX_FIELD_GET) {
+        RBX_TRY(bitset_find(c, name, &bm));
+        if (!bm) {
+            HIP_TRY(hipMemsetAsync(d_replies, 0, n * 8, st));
+            return RBX_OK;
+        }
+        launch_fields_get(bm->d_words, bm->cap_bytes, d_offs, n, size, is_signed, d_replies, st);
+        HIP_TRY(hipGetLastError());
+        return RBX_OK;
+    }
+    const uint64_t need = ((mx + size - 1) >> 3) + 1;
+    RBX_TRY(bitset_for_write(c, name, need, st, &bm));
+    if (!aligned) {
+        launch_fields_serial(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, d_offs, d_values, n, d_replies,
+                             need, st);
+    } else if (op == RBX_FIELD_INCRBY && !d_replies && 64 % size == 0) {
+        launch_fields_incr_atomic(bm->d_words, bm->d_len, bm->cap_bytes, d_offs, d_values, n, size, need, st);
+    } else {
+        // consecutive chunks of at most 2^30 elements, in order (positions are 32-bit inside a chunk)
+        const uint64_t kChunk = 1ULL << 30;
+        int slot_bits = 1;
+        while (slot_bits < 32 && ((mx / (uint64_t)size) >> slot_bits) != 0) ++slot_bits;
+        size_t scratch = 0;
+        int e = fields_grouped_scratch_bytes((uint32_t)std::min(n, kChunk), slot_bits, &scratch);
+        if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        RBX_TRY(c->fld_sort.reserve(scratch));
+        for (uint64_t i0 = 0; i0 < n; i0 += kChunk) {
+            const uint32_t m = (uint32_t)std::min(kChunk, n - i0);
+            e = launch_fields_grouped(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, d_offs + i0,
+                                      d_values + i0, m, d_replies ? d_replies + i0 : nullptr, need, slot_bits,
+                                      c->fld_sort.p, c->fld_sort.cap, st);
+            if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+static int fields_args_check(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const void *offs,
+                             const void *values, uint64_t n, const void *replies) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(field_type_check(op, is_signed, size));
+    if (n && (!offs || (op != RBX_FIELD_GET && !values) || (op == RBX_FIELD_GET && !replies)))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return RBX_OK;
+}
+
+int rbx_bitset_fields(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const uint64_t *offsets,
+                      const int64_t *values, uint64_t n, int64_t *replies) {
+    RBX_TRY(fields_args_check(c, name, op, is_signed, size, offsets, values, n, replies));
+    if (n == 0) return RBX_OK;  // no command is sent
+    uint64_t mx = 0;
+    bool aligned = true;
+    for (uint64_t i = 0; i < n; ++i) {
+        mx = std::max(mx, offsets[i]);
+        aligned &= offsets[i] % (uint64_t)size == 0;
+    }
+    RBX_TRY(field_range_check(mx, size));
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    ScratchOrder so_(c, c->stream);
+    RBX_TRY(c->bits_idx.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, offsets, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (op != RBX_FIELD_GET) {
+        RBX_TRY(c->fld_vals.reserve(n * 8));
+        HIP_TRY(hipMemcpyAsync(c->fld_vals.p, values, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (replies) RBX_TRY(c->fld_out.reserve(n * 8));
+    RBX_TRY(fields_run(c, name_of(name), op, is_signed, size, c->bits_idx.as<uint64_t>(), c->fld_vals.as<int64_t>(), n,
+                       replies ? c->fld_out.as<int64_t>() : nullptr, mx, aligned, c->stream));
+    if (replies) HIP_TRY(hipMemcpyAsync(replies, c->fld_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+int rbx_bitset_fields_dev(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const uint64_t *d_offsets,
+                          const int64_t *d_values, uint64_t n, int64_t *d_replies, void *stream) {
+    RBX_TRY(fields_args_check(c, name, op, is_signed, size, d_offsets, d_values, n, d_replies));
+    if (n == 0) return RBX_OK;
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    hipStream_t st = pick_stream(c, stream);
+    ScratchOrder so_(c, st);
+    // the batch's check result: the largest offset and whether every offset is aligned (one wait)
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    HIP_TRY(hipMemsetAsync(d, 0, 16, st));
+    launch_fields_check(d_offsets, n, size, d, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->pin_word, d, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t mx = c->pin_word[0];
+    const bool aligned = c->pin_word[1] == 0;
+    RBX_TRY(field_range_check(mx, size));
+    return fields_run(c, name_of(name), op, is_signed, size, d_offsets, d_values, n, d_replies, mx, aligned, st);
 }
 
 // ---- Bloom: handles / device path ---------------------------------------------------------

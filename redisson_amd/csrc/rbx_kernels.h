@@ -285,6 +285,31 @@ void launch_bits_max(const uint64_t *d_idx, uint64_t n, unsigned long long *d_ou
 // SETBIT bit value; *d_old = the bit before
 void launch_bits_set_one(uint32_t *words, unsigned long long *len, uint64_t bit, bool value, unsigned long long *d_old,
                          hipStream_t st);
+// bitfield_kernels.hip -- BITFIELD GET / SET / INCRBY (RBX_FIELD_* of rbx.h) on fields of one type;
+// `words` / cap_bytes: a bitmap's allocation, which already holds every field written
+// d_out2[0] = max(d_out2[0], max offset), d_out2[1] |= 1 when an offset is no multiple of size
+void launch_fields_check(const uint64_t *d_offs, uint64_t n, int size, unsigned long long *d_out2, hipStream_t st);
+// d_out[i] = GET at d_offs[i], any offsets (bits at or past the allocation read as zero)
+void launch_fields_get(const uint32_t *words, uint64_t cap_bytes, const uint64_t *d_offs, uint64_t n, int size,
+                       int is_signed, int64_t *d_out, hipStream_t st);
+// INCRBY without replies; offsets multiples of size, size a divisor of 64; *len = max(*len, new_len)
+void launch_fields_incr_atomic(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, const uint64_t *d_offs,
+                               const int64_t *d_incs, uint64_t n, int size, uint64_t new_len, hipStream_t st);
+// SET / INCRBY in array order on offsets that are multiples of size, n <= 2^30: a stable sort by
+// slot (slot_bits = the significant bits of the largest offset / size), then one lane per slot.
+// d_replies nullable.  The scratch size for n elements comes from fields_grouped_scratch_bytes.
+// Both return 0 or a hipError_t.
+int fields_grouped_scratch_bytes(uint32_t n, int slot_bits, size_t *bytes);
+int launch_fields_grouped(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed,
+                          int size, const uint64_t *d_offs, const int64_t *d_values, uint32_t n, int64_t *d_replies,
+                          uint64_t new_len, int slot_bits, void *d_scratch, size_t scratch_bytes, hipStream_t st);
+// SET / INCRBY in array order at any offsets, one lane (exact for partly overlapping fields)
+void launch_fields_serial(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
+                          const uint64_t *d_offs, const int64_t *d_values, uint64_t n, int64_t *d_replies,
+                          uint64_t new_len, hipStream_t st);
+// one SET / INCRBY; *d_reply = its reply
+void launch_field_one(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
+                      uint64_t offset, int64_t value, int64_t *d_reply, uint64_t new_len, hipStream_t st);
 // order-independent digest of a Redis string's bytes (replica comparison); *out += digest
 void launch_digest(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st);
 // region-local gathers: 6 loads per lane inside XCD-assigned regions (partitioned-probe roofline)
