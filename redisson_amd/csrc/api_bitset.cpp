@@ -1,0 +1,481 @@
+// api_bitset.cpp -- RBitSet over the bitmap keys (M/RedissonBitSet.java): single and batched SETBIT /
+// GETBIT, range fill, BITOP, cardinality / size / length, and the typed fields of BITFIELD.
+#include "rbx_ctx.h"
+
+namespace rbx {
+
+static constexpr uint64_t kMaxBitOffset = kEngineMaxSize;  // offsets end at 2^32 - 1
+
+static bool bad_name(const rbx_name &n) { return !n.bytes && n.len; }
+
+// the bitmap under `name`; null for a missing key (the empty string)
+static int bitset_find(rbx_ctx *c, const std::string &name, std::shared_ptr<Bitmap> *out) {
+    out->reset();
+    Entry *e = c->ks.find(name);
+    if (!e) return RBX_OK;
+    if (e->type != KType::Bitmap) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    *out = e->bm;
+    return RBX_OK;
+}
+
+// The bitmap a write reaching byte need_bytes - 1 goes to.  The key's own allocation when it
+// suffices: the write is then in place and open rbx_bloom handles keep seeing the key.  Otherwise it
+// grows geometrically (at most 2^32 bits, never below the |size| of an existing {name}:config),
+// which rebinds the entry and bumps the keyspace generation (grow_bitmap); a missing key is created.
+static int bitset_for_write(rbx_ctx *c, const std::string &name, uint64_t need_bytes, hipStream_t st,
+                            std::shared_ptr<Bitmap> *out) {
+    Entry *e = c->ks.find(name);
+    if (e && e->type != KType::Bitmap) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    if (e && e->bm->cap_bytes >= need_bytes) {
+        *out = e->bm;
+        return RBX_OK;
+    }
+    uint64_t bits = import_bits(c, name, need_bytes);
+    if (e) {
+        bits = std::min<uint64_t>(std::max<uint64_t>(bits, e->bm->cap_bytes * 16), kEngineMaxSize);
+        RBX_TRY(grow_bitmap(c, *e->bm, bits, st));
+        *out = e->bm;
+        return RBX_OK;
+    }
+    RBX_TRY(new_bitmap(c, bits, st, out));
+    c->ks.put(name, Entry{KType::Bitmap, nullptr, *out, nullptr});
+    return RBX_OK;
+}
+
+// Redis lengths of bitmaps (null = missing key: 0), eight per trip through the pinned words
+static int bitset_lens(rbx_ctx *c, const std::vector<Bitmap *> &bms, hipStream_t st, std::vector<uint64_t> *lens) {
+    lens->assign(bms.size(), 0);
+    for (size_t i0 = 0; i0 < bms.size(); i0 += 8) {
+        const size_t m = std::min<size_t>(8, bms.size() - i0);
+        for (size_t j = 0; j < m; ++j)
+            if (bms[i0 + j]) HIP_TRY(hipMemcpyAsync(c->pin_word + j, bms[i0 + j]->d_len, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t j = 0; j < m; ++j)
+            if (bms[i0 + j]) (*lens)[i0 + j] = c->pin_word[j];
+    }
+    return RBX_OK;
+}
+
+// the bitmap under `name` (null for a missing key) and its Redis length, inside the caller's scope
+static int bitset_len(rbx_ctx *c, rbx_name name, std::shared_ptr<Bitmap> *bm, uint64_t *len) {
+    RBX_TRY(bitset_find(c, name_of(name), bm));
+    std::vector<uint64_t> lens;
+    RBX_TRY(bitset_lens(c, {bm->get()}, c->stream, &lens));
+    *len = lens[0];
+    return RBX_OK;
+}
+
+static uint64_t max_index(const uint64_t *idx, uint64_t n) {
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; ++i) m = std::max(m, idx[i]);
+    return m;
+}
+
+// the maximum of n device indexes (one wait on `st`), which must be a Redis bit offset
+static int max_index_dev(rbx_ctx *c, const uint64_t *d_idx, uint64_t n, hipStream_t st, uint64_t *out) {
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    HIP_TRY(hipMemsetAsync(d, 0, 8, st));
+    launch_bits_max(d_idx, n, d, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->pin_word, d, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = *c->pin_word;
+    return *out >= kMaxBitOffset ? fail(RBX_E_REDIS, kBitOffsetMsg) : RBX_OK;
+}
+
+// SETBIT of n device indexes whose maximum is mx
+static int bitset_scatter(rbx_ctx *c, const std::string &name, const uint64_t *d_idx, uint64_t n, uint64_t mx, int value,
+                          hipStream_t st) {
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_for_write(c, name, (mx >> 3) + 1, st, &bm));
+    launch_bits_scatter(bm->d_words, bm->d_len, bm->cap_bytes * 8, d_idx, n, value != 0, (mx >> 3) + 1, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+// GETBIT of n device indexes into device bytes
+static int bitset_gather(rbx_ctx *c, const std::string &name, const uint64_t *d_idx, uint64_t n, uint8_t *d_out,
+                         hipStream_t st) {
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name, &bm));
+    if (!bm) {
+        HIP_TRY(hipMemsetAsync(d_out, 0, n, st));
+        return RBX_OK;
+    }
+    launch_bits_gather(bm->d_words, bm->cap_bytes * 8, d_idx, n, d_out, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+// ---- RBitSet's typed fields: BITFIELD GET / SET / INCRBY (M/RedissonBitSet.java:71-254) -------
+// the type's checks: Redisson's own (:72-73, :99-100), then the one Redis makes
+static int field_type_check(int op, int is_signed, int size) {
+    if (op < RBX_FIELD_GET || op > RBX_FIELD_INCRBY) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITFIELD operation");
+    if (is_signed && size > 64) return fail(RBX_E_ILLEGAL_ARGUMENT, "Size can't be greater than 64 bits");
+    if (!is_signed && size > 63) return fail(RBX_E_ILLEGAL_ARGUMENT, "Size can't be greater than 63 bits");
+    if (size < 1)
+        return fail(RBX_E_REDIS,
+                    "ERR Invalid bitfield type. Use something like i16 u8. Note that u64 is not supported but i64 is.");
+    return RBX_OK;
+}
+
+// the offset limit for fields of `size` bits whose largest offset is mx: the whole field lies below bit 2^32
+static int field_range_check(uint64_t mx, int size) {
+    if (mx >= kMaxBitOffset || mx + (uint64_t)size > kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    return RBX_OK;
+}
+
+// GET on a host string: the field's bits from the bytes below len, zero past them
+static int64_t field_of_bytes(const uint8_t *bytes, uint64_t len, int is_signed, int size, uint64_t offset) {
+    uint64_t v = 0;
+    for (int j = 0; j < size; ++j) {
+        const uint64_t b = offset + (uint64_t)j;
+        const uint64_t bit = (b >> 3) < len ? (bytes[b >> 3] >> (7 - (b & 7))) & 1 : 0;
+        v = (v << 1) | bit;
+    }
+    if (is_signed && size < 64 && ((v >> (size - 1)) & 1)) v |= ~0ULL << size;
+    return (int64_t)v;
+}
+
+// A checked batch over device arrays: mx = the largest offset, aligned = every offset is a multiple
+// of size.  GET gathers; an unaligned SET / INCRBY runs serially (partly overlapping fields make
+// the order total); an aligned INCRBY without replies whose size divides 64 is one atomic loop per
+// element; every other aligned batch is sorted by slot and walked run by run.
+static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed, int size, const uint64_t *d_offs,
+                      const int64_t *d_values, uint64_t n, int64_t *d_replies, uint64_t mx, bool aligned,
+                      hipStream_t st) {
+    std::shared_ptr<Bitmap> bm;
+    if (op == RBX_FIELD_GET) {
+        RBX_TRY(bitset_find(c, name, &bm));
+        if (!bm) {
+            HIP_TRY(hipMemsetAsync(d_replies, 0, n * 8, st));
+            return RBX_OK;
+        }
+        launch_fields_get(bm->d_words, bm->cap_bytes, d_offs, n, size, is_signed, d_replies, st);
+        HIP_TRY(hipGetLastError());
+        return RBX_OK;
+    }
+    const uint64_t need = ((mx + size - 1) >> 3) + 1;
+    RBX_TRY(bitset_for_write(c, name, need, st, &bm));
+    if (!aligned) {
+        launch_fields_serial(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, d_offs, d_values, n, d_replies,
+                             need, st);
+    } else if (op == RBX_FIELD_INCRBY && !d_replies && 64 % size == 0) {
+        launch_fields_incr_atomic(bm->d_words, bm->d_len, bm->cap_bytes, d_offs, d_values, n, size, need, st);
+    } else {
+        // consecutive chunks of at most 2^30 elements, in order (positions are 32-bit inside a chunk)
+        const uint64_t kChunk = 1ULL << 30;
+        int slot_bits = 1;
+        while (slot_bits < 32 && ((mx / (uint64_t)size) >> slot_bits) != 0) ++slot_bits;
+        size_t scratch = 0;
+        int e = fields_grouped_scratch_bytes((uint32_t)std::min(n, kChunk), slot_bits, &scratch);
+        if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        RBX_TRY(c->fld_sort.reserve(scratch));
+        for (uint64_t i0 = 0; i0 < n; i0 += kChunk) {
+            const uint32_t m = (uint32_t)std::min(kChunk, n - i0);
+            e = launch_fields_grouped(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, d_offs + i0,
+                                      d_values + i0, m, d_replies ? d_replies + i0 : nullptr, need, slot_bits,
+                                      c->fld_sort.p, c->fld_sort.cap, st);
+            if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+static int fields_args_check(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const void *offs,
+                             const void *values, uint64_t n, const void *replies) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(field_type_check(op, is_signed, size));
+    if (n && (!offs || (op != RBX_FIELD_GET && !values) || (op == RBX_FIELD_GET && !replies)))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return RBX_OK;
+}
+
+}  // namespace rbx
+
+using namespace rbx;
+
+extern "C" {
+
+int rbx_bitset_get(rbx_ctx *c, rbx_name name, uint64_t index, int *bit) {
+    if (!c || bad_name(name) || !bit) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (index >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name_of(name), &bm));
+    *bit = 0;
+    if (!bm || (index >> 3) >= bm->cap_bytes) return RBX_OK;
+    // one byte of the string (zero past its length) into a pinned word
+    uint8_t *pin = (uint8_t *)c->pin_word;
+    HIP_TRY(hipMemcpyAsync(pin, (const uint8_t *)bm->d_words + (index >> 3), 1, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *bit = (pin[0] >> (7 - (index & 7))) & 1;
+    return RBX_OK;
+}
+
+int rbx_bitset_set(rbx_ctx *c, rbx_name name, uint64_t index, int value, int *old) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (index >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_for_write(c, name_of(name), (index >> 3) + 1, c->stream, &bm));
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    launch_bits_set_one(bm->d_words, bm->d_len, index, value != 0, d, c->stream);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    const uint64_t was = read_dev_u64(c, d, &rc);
+    if (old) *old = (int)was;
+    return rc;
+}
+
+int rbx_bitset_set_indexes(rbx_ctx *c, rbx_name name, const uint64_t *indexes, uint64_t n, int value) {
+    if (!c || bad_name(name) || (n && !indexes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;  // no command is sent
+    const uint64_t mx = max_index(indexes, n);
+    if (mx >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    RBX_ENTER(c, c->stream);
+    RBX_TRY(c->bits_idx.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
+    RBX_TRY(bitset_scatter(c, name_of(name), c->bits_idx.as<uint64_t>(), n, mx, value, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+int rbx_bitset_get_indexes(rbx_ctx *c, rbx_name name, const uint64_t *indexes, uint64_t n, uint8_t *out) {
+    if (!c || bad_name(name) || (n && (!indexes || !out))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;
+    if (max_index(indexes, n) >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    RBX_ENTER(c, c->stream);
+    RBX_TRY(c->bits_idx.reserve(n * 8));
+    RBX_TRY(c->out_bytes.reserve(n));
+    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
+    RBX_TRY(bitset_gather(c, name_of(name), c->bits_idx.as<uint64_t>(), n, c->out_bytes.as<uint8_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->out_bytes.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+int rbx_bitset_set_indexes_dev(rbx_ctx *c, rbx_name name, const uint64_t *d_indexes, uint64_t n, int value,
+                               void *stream) {
+    if (!c || bad_name(name) || (n && !d_indexes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    uint64_t mx;
+    RBX_TRY(max_index_dev(c, d_indexes, n, st, &mx));
+    return bitset_scatter(c, name_of(name), d_indexes, n, mx, value, st);
+}
+
+int rbx_bitset_get_indexes_dev(rbx_ctx *c, rbx_name name, const uint64_t *d_indexes, uint64_t n, uint8_t *d_out,
+                               void *stream) {
+    if (!c || bad_name(name) || (n && (!d_indexes || !d_out))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    uint64_t mx;
+    RBX_TRY(max_index_dev(c, d_indexes, n, st, &mx));
+    return bitset_gather(c, name_of(name), d_indexes, n, d_out, st);
+}
+
+int rbx_bitset_set_range(rbx_ctx *c, rbx_name name, uint64_t from, uint64_t to, int value) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (from >= to) return RBX_OK;  // an empty batch: no command is sent
+    if (from >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
+    // the batch's SETBITs below the limit run, the others fail: apply [from, 2^32), then report
+    const bool past = to > kMaxBitOffset;
+    if (past) to = kMaxBitOffset;
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_for_write(c, name_of(name), ((to - 1) >> 3) + 1, c->stream, &bm));
+    launch_bits_fill(bm->d_words, bm->d_len, from, to, value != 0, c->stream);
+    HIP_TRY(hipGetLastError());
+    return past ? fail(RBX_E_REDIS, kBitOffsetMsg) : RBX_OK;
+}
+
+int rbx_bitset_op(rbx_ctx *c, int op, rbx_name dest, const rbx_name *srcs, uint32_t nsrc, uint64_t *result_len) {
+    if (!c || bad_name(dest)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (op < RBX_BITOP_AND || op > RBX_BITOP_NOT) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITOP operation");
+    if (nsrc == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "BITOP needs a source key");
+    if (op == RBX_BITOP_NOT && nsrc != 1)
+        return fail(RBX_E_REDIS, "ERR BITOP NOT must be called with a single source key.");
+    std::vector<std::string> sn;
+    RBX_TRY(names_of(srcs, nsrc, &sn));
+    const std::string dn = name_of(dest);
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    // every operand's type first: a wrong one leaves dest untouched
+    std::shared_ptr<Bitmap> db;
+    RBX_TRY(bitset_find(c, dn, &db));
+    std::vector<std::shared_ptr<Bitmap>> sb(nsrc);
+    std::vector<Bitmap *> bms(nsrc + 1);
+    for (uint32_t i = 0; i < nsrc; ++i) {
+        RBX_TRY(bitset_find(c, sn[i], &sb[i]));
+        bms[i] = sb[i].get();
+    }
+    bms[nsrc] = db.get();
+    std::vector<uint64_t> lens;
+    RBX_TRY(bitset_lens(c, bms, st, &lens));
+    const uint64_t out_len = *std::max_element(lens.begin(), lens.begin() + nsrc);
+    if (result_len) *result_len = out_len;
+    if (out_len == 0) {  // the empty result: DEL dest
+        c->ks.erase(dn);
+        return RBX_OK;
+    }
+    RBX_TRY(bitset_for_write(c, dn, out_len, st, &db));
+    // the table after dest has its final allocation: a source that is dest moved with it
+    std::vector<BitopSrc> tab(nsrc);
+    for (uint32_t i = 0; i < nsrc; ++i) tab[i] = BitopSrc{sb[i] ? (const uint8_t *)sb[i]->d_words : nullptr, lens[i]};
+    RBX_TRY(c->bitop_srcs.reserve(nsrc * sizeof(BitopSrc)));
+    // (a pageable source is staged by the runtime before the call returns)
+    HIP_TRY(hipMemcpyAsync(c->bitop_srcs.p, tab.data(), nsrc * sizeof(BitopSrc), hipMemcpyHostToDevice, st));
+    // the sweep also clears what a longer previous dest held past the result
+    const uint64_t span = (std::max(out_len, lens[nsrc]) + 15) & ~15ULL;
+    launch_bitop(op, (uint8_t *)db->d_words, db->d_len, c->bitop_srcs.as<BitopSrc>(), nsrc, out_len, span, st);
+    HIP_TRY(hipGetLastError());
+    if (Entry *e = c->ks.find(dn)) e->expire_at = -1;  // setKey without KEEPTTL
+    return RBX_OK;
+}
+
+int rbx_bitset_cardinality(rbx_ctx *c, rbx_name name, uint64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    return bitcount_locked(c, name_of(name), out);
+}
+
+int rbx_bitset_size(rbx_ctx *c, rbx_name name, uint64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t len;
+    RBX_TRY(bitset_len(c, name, &bm, &len));
+    *out = len * 8;
+    return RBX_OK;
+}
+
+int rbx_bitset_length(rbx_ctx *c, rbx_name name, int64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t len;
+    RBX_TRY(bitset_len(c, name, &bm, &len));
+    uint8_t *pin = (uint8_t *)c->pin_word;
+    pin[0] = pin[1] = 0;
+    if (len) {  // the script reads the first and the last byte only
+        const uint8_t *s = (const uint8_t *)bm->d_words;
+        HIP_TRY(hipMemcpyAsync(pin, s, 1, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(pin + 1, s + len - 1, 1, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return bitset_length(len, pin[0], pin[1], out);
+}
+
+int rbx_bitset_length_of(const uint8_t *bytes, uint64_t len, int64_t *out) { return bitset_length_of(bytes, len, out); }
+
+int rbx_bitset_export_n(rbx_ctx *c, rbx_name name, uint8_t *out, uint64_t cap, uint64_t *redis_len) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return bitmap_export(c, name_of(name), out, cap, redis_len);
+}
+
+int rbx_bitset_import_n(rbx_ctx *c, rbx_name name, const uint8_t *bytes, uint64_t len) {
+    if (!c || bad_name(name) || (len && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return bitmap_import(c, name_of(name), bytes, len);
+}
+
+int rbx_bitset_rename(rbx_ctx *c, rbx_name name, rbx_name new_name) {
+    if (!c || bad_name(name) || bad_name(new_name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    return c->ks.rename(name_of(name), name_of(new_name));
+}
+
+int rbx_bitset_field_of(const uint8_t *bytes, uint64_t len, int is_signed, int size, uint64_t offset, int64_t *out) {
+    if ((len && !bytes) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(field_type_check(RBX_FIELD_GET, is_signed, size));
+    RBX_TRY(field_range_check(offset, size));
+    *out = field_of_bytes(bytes, len, is_signed, size, offset);
+    return RBX_OK;
+}
+
+int rbx_bitset_field(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, uint64_t offset, int64_t value,
+                     int64_t *reply) {
+    if (!c || bad_name(name) || (op == RBX_FIELD_GET && !reply)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(field_type_check(op, is_signed, size));
+    RBX_TRY(field_range_check(offset, size));
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    if (op == RBX_FIELD_GET) {
+        RBX_TRY(bitset_find(c, name_of(name), &bm));
+        // the field's covering bytes inside the allocation (zero past the string's length), at most 9
+        uint8_t *pin = (uint8_t *)c->pin_word;
+        const uint64_t first = offset >> 3, last = (offset + size - 1) >> 3;
+        uint64_t nb = 0;
+        if (bm && first < bm->cap_bytes) {
+            nb = std::min<uint64_t>(last + 1, bm->cap_bytes) - first;
+            HIP_TRY(hipMemcpyAsync(pin, (const uint8_t *)bm->d_words + first, nb, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        *reply = field_of_bytes(pin, nb, is_signed, size, offset & 7);
+        return RBX_OK;
+    }
+    const uint64_t need = ((offset + size - 1) >> 3) + 1;
+    RBX_TRY(bitset_for_write(c, name_of(name), need, c->stream, &bm));
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    launch_field_one(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, offset, value, (int64_t *)d, need,
+                     c->stream);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    const uint64_t r = read_dev_u64(c, d, &rc);
+    if (reply) *reply = (int64_t)r;
+    return rc;
+}
+
+int rbx_bitset_fields(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const uint64_t *offsets,
+                      const int64_t *values, uint64_t n, int64_t *replies) {
+    RBX_TRY(fields_args_check(c, name, op, is_signed, size, offsets, values, n, replies));
+    if (n == 0) return RBX_OK;  // no command is sent
+    uint64_t mx = 0;
+    bool aligned = true;
+    for (uint64_t i = 0; i < n; ++i) {
+        mx = std::max(mx, offsets[i]);
+        aligned &= offsets[i] % (uint64_t)size == 0;
+    }
+    RBX_TRY(field_range_check(mx, size));
+    RBX_ENTER(c, c->stream);
+    RBX_TRY(c->bits_idx.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, offsets, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (op != RBX_FIELD_GET) {
+        RBX_TRY(c->fld_vals.reserve(n * 8));
+        HIP_TRY(hipMemcpyAsync(c->fld_vals.p, values, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (replies) RBX_TRY(c->fld_out.reserve(n * 8));
+    RBX_TRY(fields_run(c, name_of(name), op, is_signed, size, c->bits_idx.as<uint64_t>(), c->fld_vals.as<int64_t>(), n,
+                       replies ? c->fld_out.as<int64_t>() : nullptr, mx, aligned, c->stream));
+    if (replies) HIP_TRY(hipMemcpyAsync(replies, c->fld_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+int rbx_bitset_fields_dev(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const uint64_t *d_offsets,
+                          const int64_t *d_values, uint64_t n, int64_t *d_replies, void *stream) {
+    RBX_TRY(fields_args_check(c, name, op, is_signed, size, d_offsets, d_values, n, d_replies));
+    if (n == 0) return RBX_OK;
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    // the batch's check result: the largest offset and whether every offset is aligned (one wait)
+    RBX_TRY(c->counters.reserve(64));
+    auto *d = c->counters.as<unsigned long long>() + 1;
+    HIP_TRY(hipMemsetAsync(d, 0, 16, st));
+    launch_fields_check(d_offsets, n, size, d, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->pin_word, d, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t mx = c->pin_word[0];
+    const bool aligned = c->pin_word[1] == 0;
+    RBX_TRY(field_range_check(mx, size));
+    return fields_run(c, name_of(name), op, is_signed, size, d_offsets, d_values, n, d_replies, mx, aligned, st);
+}
+
+}  // extern "C"

@@ -1,0 +1,975 @@
+// api_hll.cpp -- HyperLogLog: the register pool, PFADD / PFCOUNT / PFMERGE with Redis' sparse and dense
+// encodings, export / import, handles, register packing, the RCCL merge, copies between contexts.
+#include <cmath>
+#include <cstring>
+#include <unordered_map>
+
+#include "api_staging.h"
+#include "tunables.h"
+
+namespace rbx {
+
+rbx::HllState::~HllState() {
+    if (d_regs && owner) {
+        {
+            std::lock_guard<std::recursive_mutex> g(owner->ks.mu);
+            if (!owner->shut) owner->hll_dirty.push_back({d_regs, d_promoted, d_slot_ops});
+        }
+        if (d_big_ops) (void)hipFree(d_big_ops);  // its own allocation: released also after a shutdown
+        ctx_release(owner);
+    }
+}
+
+// room for `nops` opcodes in h's list (the caller then overwrites the list)
+static int hll_ops_reserve(HllState *h, uint64_t nops) {
+    if (nops <= kHllSlotOps || h->d_big_ops) {
+        if (nops > kHllMaxOps) return fail(RBX_E_WRONGTYPE, "a sparse HLL string holds at most 16384 opcodes");
+        if (h->d_big_ops) h->d_sp_ops = h->d_big_ops;
+        return RBX_OK;
+    }
+    if (nops > kHllMaxOps) return fail(RBX_E_WRONGTYPE, "a sparse HLL string holds at most 16384 opcodes");
+    HIP_TRY(hipMalloc(&h->d_big_ops, kHllMaxOps * 2));
+    h->d_sp_ops = h->d_big_ops;
+    return RBX_OK;
+}
+
+// A fresh zeroed HLL register block; the fill runs on `st` (see SlabPool).
+static int hll_alloc(rbx_ctx *c, hipStream_t st, std::shared_ptr<HllState> *out) {
+    if (c->hll_free.empty() && !c->hll_dirty.empty()) {
+        // the deleted HLLs' slots, zeroed in one launch on the caller's stream (creating 10k HLLs
+        // cost 20k small fills, ~10 ms of enqueueing, when each slot was zeroed on its own)
+        const size_t n = c->hll_dirty.size();
+        std::vector<void *> ptrs(2 * n);
+        for (size_t i = 0; i < n; ++i) {
+            ptrs[i] = c->hll_dirty[i].regs;
+            ptrs[n + i] = c->hll_dirty[i].state;
+        }
+        RBX_TRY(c->hll_zero_ptrs.reserve(ptrs.size() * sizeof(void *)));
+        HIP_TRY(hipMemcpyAsync(c->hll_zero_ptrs.p, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, st));
+        uint8_t *const *d_regs = c->hll_zero_ptrs.as<uint8_t *>();
+        launch_hll_zero(d_regs, (uint32_t *const *)(d_regs + n), (uint32_t)n, st);
+        HIP_TRY(hipGetLastError());
+        // handed out last-deleted first, as before
+        c->hll_free.insert(c->hll_free.end(), c->hll_dirty.begin(), c->hll_dirty.end());
+        c->hll_dirty.clear();
+    }
+    if (c->hll_free.empty()) {
+        // registers of kHllPerChunk HLLs, then their state words, then their sparse opcode lists
+        uint8_t *chunk = nullptr;
+        HIP_TRY(hipMalloc(&chunk, (kHllBytes + kHllStateWords * 4 + kHllOpsBytes) * kHllPerChunk));
+        c->hll_chunks.push_back(chunk);
+        uint32_t *words = (uint32_t *)(chunk + kHllBytes * kHllPerChunk);
+        uint16_t *ops = (uint16_t *)(words + kHllStateWords * kHllPerChunk);
+        // registers and state words of the whole chunk zeroed at once: creating 10k HLLs cost
+        // 20k small fills (~10 ms of enqueueing) when each slot was zeroed on its own
+        HIP_TRY(hipMemsetAsync(chunk, 0, (kHllBytes + kHllStateWords * 4) * kHllPerChunk, st));
+        // hand out in reverse so that successive allocations are ascending
+        for (size_t i = kHllPerChunk; i-- > 0;)
+            c->hll_free.push_back({chunk + i * kHllBytes, words + i * kHllStateWords, ops + i * (kHllOpsBytes / 2)});
+    }
+    auto h = std::make_shared<HllState>();
+    const auto slot = c->hll_free.back();
+    h->d_regs = slot.regs;
+    h->d_promoted = slot.state;
+    h->d_sp_ops = h->d_slot_ops = slot.ops;
+    c->hll_free.pop_back();
+    h->owner = c;
+    c->refs.fetch_add(1);
+    // every slot in hll_free is zero: registers 0, state 0 (not promoted, the createHLLObject
+    // sparse string: one XZERO)
+    *out = h;
+    return RBX_OK;
+}
+
+// ---- HyperLogLog ------------------------------------------------------------------------------
+static constexpr uint64_t kTileElems = 65536;  // elements per PFADD workgroup
+constexpr uint64_t kHllSparseMaxBytes = 3000;  // redis.conf hll-sparse-max-bytes (default)
+
+static const char *kHllWrongType = "WRONGTYPE Key is not a valid HyperLogLog string value.";
+
+// The HLL under `name`; with create, PFADD's createHLLObject (registers zero-filled on `st`).
+static int hll_get(rbx_ctx *c, const std::string &name, bool create, hipStream_t st, std::shared_ptr<HllState> *out,
+                   bool *created) {
+    if (created) *created = false;
+    Entry *e = c->ks.find(name);
+    if (e) {
+        if (e->type != KType::Hll) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+        *out = e->hll;
+        return RBX_OK;
+    }
+    if (!create) {
+        out->reset();
+        return RBX_OK;
+    }
+    std::shared_ptr<HllState> h;
+    RBX_TRY(hll_alloc(c, st, &h));
+    h->card = 0;  // createHLLObject: cached cardinality 0, valid
+    c->ks.put(name, Entry{KType::Hll, nullptr, nullptr, h});
+    c->ks.generation++;
+    *out = h;
+    if (created) *created = true;
+    return RBX_OK;
+}
+
+// HLL handles follow the name too; PFADD on a missing key creates it (createHLLObject), PFCOUNT
+// reads it as empty (h->st = null) without creating it
+static int hll_bind(rbx_ctx *c, rbx_hll *h, bool create, hipStream_t st) {
+    c->ks.sweep();
+    if (h->ctx != c) return fail(RBX_E_ILLEGAL_ARGUMENT, "the handle belongs to another context");
+    if (h->gen == c->ks.generation && h->st) return RBX_OK;
+    std::shared_ptr<HllState> s;
+    RBX_TRY(hll_get(c, h->name, create, st, &s, nullptr));
+    h->st = s;
+    if (s) h->gen = c->ks.generation;
+    return RBX_OK;
+}
+
+// Redis keeps a PFADD-created HLL sparse until an update would store a value > 32 or grow the
+// string past hll-sparse-max-bytes, then promotes it to dense for good ([redis-7.2]
+// hyperloglog.c hllSparseSet), and the sparse bytes depend on the order of the updates.
+// k_hll_sparse_replay applies each command's updates, in order, to the sparse HLLs' strings on
+// the device (the registers are updated by the PFADD / merge kernels as for dense keys) and sets
+// the sticky promotion word at the first promotion.  `items` = one per sparse HLL of a round.
+static int replay_sparse(rbx_ctx *c, std::vector<HllReplay> &items, const KeysDev &dk, int fl, hipStream_t st,
+                         TinyArena *ta = nullptr) {
+    if (items.empty()) return RBX_OK;
+    if (const void *d = ta ? ta->put(items.data(), items.size() * sizeof(HllReplay)) : nullptr) {  // tiny call
+        launch_hll_sparse_replay(dk, fl, (const HllReplay *)d, (uint32_t)items.size(), kHllSparseMaxBytes, st);
+        HIP_TRY(hipGetLastError());
+        return RBX_OK;
+    }
+    const bool same = c->check_cache.size() == items.size() &&
+                      memcmp(c->check_cache.data(), items.data(), items.size() * sizeof(HllReplay)) == 0;
+    if (!same) {
+        RBX_TRY(c->hll_checks.reserve(items.size() * sizeof(HllReplay)));
+        HIP_TRY(hipMemcpyAsync(c->hll_checks.p, items.data(), items.size() * sizeof(HllReplay), hipMemcpyHostToDevice, st));
+        c->check_cache = items;
+    }
+    launch_hll_sparse_replay(dk, fl, c->hll_checks.as<HllReplay>(), (uint32_t)items.size(), kHllSparseMaxBytes, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+// PFMERGE-style write-back (ascending registers) of the sparse HLLs among hl; their registers
+// already hold the merged maxima
+static int replay_merge(rbx_ctx *c, const std::vector<HllState *> &hl, hipStream_t st) {
+    std::vector<HllReplay> items;
+    std::unordered_map<HllState *, int> seen;
+    for (HllState *h : hl)
+        if (h && !h->dense && !seen.count(h)) {
+            seen[h] = 1;
+            items.push_back(HllReplay{h->d_sp_ops, h->d_promoted, h->d_regs, 0, 0, h->d_regs});
+        }
+    return replay_sparse(c, items, KeysDev{}, 0, st);
+}
+
+// host view of the promotion word (the caller holds a CallScope on c->stream)
+static int resolve_dense(rbx_ctx *c, HllState *h) {
+    if (h->dense) return RBX_OK;
+    uint32_t w = 0;
+    HIP_TRY(hipMemcpyAsync(&w, h->d_promoted, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (w) h->dense = true;
+    return RBX_OK;
+}
+
+// PFADD batch: device elements, commands in order.  Commands naming the same HLL are
+// split into successive launches so each reply sees the previous commands' effect.
+static int pfadd_run(rbx_ctx *c, const std::vector<HllState *> &hl, const uint64_t *h_seg, const KeysDev &dk,
+                     uint32_t *d_changed, hipStream_t st, TinyArena *ta = nullptr) {
+    const uint32_t nseg = (uint32_t)hl.size();
+    std::vector<HllSeg> tiles;
+    uint32_t s0 = 0;
+    const int fl = fast_len_hll(dk);
+    while (s0 < nseg) {
+        // a round: maximal run of commands with distinct HLLs
+        std::unordered_map<HllState *, int> seen;
+        uint32_t s1 = s0;
+        while (s1 < nseg && !seen.count(hl[s1])) seen[hl[s1++]] = 1;
+        tiles.clear();
+        for (uint32_t s = s0; s < s1; ++s) {
+            for (uint64_t b = h_seg[s]; b < h_seg[s + 1]; b += kTileElems)
+                tiles.push_back(HllSeg{hl[s]->d_regs, b, std::min(h_seg[s + 1], b + kTileElems), s, 0});
+        }
+        if (!tiles.empty()) {
+            // a tiny call's tile list is read from the coherent block (each round its own copy)
+            const HllSeg *d_tiles = ta ? (const HllSeg *)ta->put(tiles.data(), tiles.size() * sizeof(HllSeg)) : nullptr;
+            if (!d_tiles) {
+                // the tile table is cached by content (a steady PFADD pipeline re-sends the same one)
+                const bool single_round = s0 == 0 && s1 == nseg;
+                const bool same = single_round && c->tiles_valid && c->tile_cache.size() == tiles.size() &&
+                                  memcmp(c->tile_cache.data(), tiles.data(), tiles.size() * sizeof(HllSeg)) == 0;
+                if (!same) {
+                    RBX_TRY(c->hll_tiles.reserve(tiles.size() * sizeof(HllSeg)));
+                    // pageable source: staged by the runtime before the call returns; stream order
+                    // keeps the previous round's kernel ahead of this overwrite
+                    HIP_TRY(hipMemcpyAsync(c->hll_tiles.p, tiles.data(), tiles.size() * sizeof(HllSeg), hipMemcpyHostToDevice, st));
+                    c->tiles_valid = single_round;
+                    if (single_round) c->tile_cache = tiles;
+                }
+                d_tiles = c->hll_tiles.as<HllSeg>();
+            }
+            launch_hll_pfadd(dk, fl, d_tiles, (uint32_t)tiles.size(), d_changed, st);
+            HIP_TRY(hipGetLastError());
+            std::vector<HllReplay> items;  // the round's HLLs are distinct
+            for (uint32_t s = s0; s < s1; ++s)
+                if (!hl[s]->dense && h_seg[s + 1] > h_seg[s])
+                    items.push_back(HllReplay{hl[s]->d_sp_ops, hl[s]->d_promoted, nullptr, h_seg[s], h_seg[s + 1],
+                                              hl[s]->d_regs});
+            RBX_TRY(replay_sparse(c, items, dk, fl, st, ta));
+        }
+        s0 = s1;
+    }
+    return RBX_OK;
+}
+
+int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint64_t *seg_offsets,
+                  const rbx_keys *elements, uint8_t *out_changed) {
+    const uint32_t nseg = (uint32_t)names.size();
+    RBX_TRY(validate_keys(elements));
+    if (nseg == 0) return RBX_OK;
+    if (seg_offsets[0] != 0 || seg_offsets[nseg] != elements->n)
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "segment offsets must span [0, n]");
+    for (uint32_t s = 0; s < nseg; ++s)
+        if (seg_offsets[s + 1] < seg_offsets[s]) return fail(RBX_E_ILLEGAL_ARGUMENT, "segment offsets must be ascending");
+    RBX_ENTER(c, c->stream);
+    std::vector<HllState *> hl(nseg);
+    std::vector<std::shared_ptr<HllState>> keep(nseg);
+    std::vector<uint8_t> created(nseg, 0);
+    for (uint32_t s = 0; s < nseg; ++s) {
+        bool cr;
+        RBX_TRY(hll_get(c, names[s], true, c->stream, &keep[s], &cr));
+        hl[s] = keep[s].get();
+        created[s] = cr;
+    }
+    std::vector<uint32_t> ch(nseg);  // each tier's changed words end up here
+    auto reply = [&]() {
+        for (uint32_t s = 0; s < nseg; ++s) {
+            if (ch[s]) hl[s]->card |= 1ULL << 63;  // HLL_INVALIDATE_CACHE
+            if (out_changed) out_changed[s] = ch[s] || created[s];
+        }
+        return RBX_OK;
+    };
+    if (nseg <= kSegMaxKeys && bloom_tiny_fits(c, elements)) {
+        // elements, changed words, tile list and replay items in coherent pinned memory (bloom_host_tiny)
+        auto *ch_h = (uint32_t *)(c->pin_tiny + kTinySegAt);
+        memset(ch_h, 0, (size_t)nseg * 4);
+        const KeysDev dk = tiny_stage(c, elements);
+        TinyArena ta{c->pin_tiny + kTinyArenaAt, c->pin_tiny_dev + kTinyArenaAt, kTinyArenaBytes, 0};
+        RBX_TRY(tiny_done(c, pfadd_run(c, hl, seg_offsets, dk, (uint32_t *)(c->pin_tiny_dev + kTinySegAt), c->stream,
+                                       &ta),
+                          g_tune.tiny_spin));
+        memcpy(ch.data(), ch_h, (size_t)nseg * 4);
+        return reply();
+    }
+    if (nseg <= kSmallHead / 4 && bloom_small_fits(c, elements)) {
+        // one transfer for the elements and the zeroed changed words, one readback (bloom_host_small)
+        SmallStage sm;
+        RBX_TRY(small_stage(c, elements, nseg * 4, &sm));
+        const int rc = pfadd_run(c, hl, seg_offsets, sm.dk, (uint32_t *)sm.dp, c->stream);
+        (void)hipEventRecord(c->ev_done[0], c->stream);
+        if (rc != RBX_OK) return small_fail(c, rc);
+        HIP_TRY(hipMemcpyAsync(sm.hp, sm.dp, nseg * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        memcpy(ch.data(), sm.hp, nseg * 4);
+        return reply();
+    }
+    RBX_TRY(c->misc.reserve(nseg * 4));
+    auto *d_changed = c->misc.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_changed, 0, nseg * 4, c->stream));
+    auto span_bytes = [&](uint64_t e0, uint64_t e1) {
+        return elements->offsets ? elements->offsets[e1] - elements->offsets[e0] : (e1 - e0) * elements->stride;
+    };
+    const uint64_t budget = 256ull << 20;
+    for (uint32_t s0 = 0; s0 < nseg;) {
+        // commands [s0, s1) whose elements fit one staging upload (at least one command)
+        uint32_t s1 = s0 + 1;
+        while (s1 < nseg && span_bytes(seg_offsets[s0], seg_offsets[s1 + 1]) <= budget) ++s1;
+        const uint64_t e0 = seg_offsets[s0], e1 = seg_offsets[s1];
+        KeysDev dk{};
+        if (e1 > e0) RBX_TRY(upload_keys(c, elements, e0, e1, &dk));
+        std::vector<uint64_t> reb(s1 - s0 + 1);
+        for (uint32_t s = s0; s <= s1; ++s) reb[s - s0] = seg_offsets[s] - e0;
+        std::vector<HllState *> grp(hl.begin() + s0, hl.begin() + s1);
+        RBX_TRY(pfadd_run(c, grp, reb.data(), dk, d_changed + s0, c->stream));
+        s0 = s1;
+    }
+    HIP_TRY(hipMemcpyAsync(ch.data(), d_changed, nseg * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return reply();
+}
+
+// glibc-side hllTau fallback and the full estimator from a histogram (redis hllCount)
+static double hll_tau_host(double x) {
+    if (x == 0. || x == 1.) return 0.;
+    double zPrime;
+    double y = 1.0;
+    double z = 1 - x;
+    do {
+        x = std::sqrt(x);
+        zPrime = z;
+        y *= 0.5;
+        z -= std::pow(1 - x, 2) * y;
+    } while (zPrime != z);
+    return z / 3;
+}
+
+static double hll_sigma_host(double x) {
+    if (x == 1.) return INFINITY;
+    double zPrime;
+    double y = 1;
+    double z = x;
+    do {
+        x *= x;
+        zPrime = z;
+        z += x * y;
+        y += y;
+    } while (zPrime != z);
+    return z;
+}
+
+static uint64_t hll_count_from_histo(const int *reghisto) {
+    double m = 16384;
+    double z = m * hll_tau_host((m - reghisto[51]) / (double)m);
+    for (int j = 50; j >= 1; --j) {
+        z += reghisto[j];
+        z *= 0.5;
+    }
+    z += m * hll_sigma_host(reghisto[0] / (double)m);
+    double E = (double)llroundl(0.721347520444481703680 * m * m / z);
+    return (uint64_t)E;
+}
+
+// Computes counts for raw register arrays (device pointers) -> host out.
+static int count_regs(rbx_ctx *c, const std::vector<uint8_t *> &regs, uint64_t *out) {
+    uint32_t n = (uint32_t)regs.size();
+    if (!n) return RBX_OK;
+    RBX_TRY(c->ptrs.reserve(n * sizeof(uint8_t *)));
+    RBX_TRY(c->histo.reserve((size_t)n * 64 * sizeof(int)));
+    RBX_TRY(c->misc.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(c->ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    launch_hll_count(c->ptrs.as<uint8_t *>(), n, c->histo.as<int>(), c->misc.as<unsigned long long>(), c->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> res(n);
+    HIP_TRY(hipMemcpyAsync(res.data(), c->misc.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int> h;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (res[i] == ~0ULL) {  // tau branch: histogram to host, glibc pow
+            if (h.empty()) {
+                h.resize((size_t)n * 64);
+                HIP_TRY(hipMemcpy(h.data(), c->histo.p, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+            }
+            res[i] = hll_count_from_histo(&h[(size_t)i * 64]);
+        }
+        out[i] = res[i];
+    }
+    return RBX_OK;
+}
+
+// single-key PFCOUNT with the header cache (valid cache -> cached value; else compute+store)
+static int pfcount_each(rbx_ctx *c, const std::vector<HllState *> &hl, uint64_t *out) {
+    std::vector<uint8_t *> regs;
+    std::vector<uint32_t> idx;
+    for (uint32_t i = 0; i < hl.size(); ++i) {
+        if (!hl[i]) {
+            out[i] = 0;
+            continue;
+        }
+        if (!(hl[i]->card >> 63)) {
+            out[i] = hl[i]->card;
+            continue;
+        }
+        regs.push_back(hl[i]->d_regs);
+        idx.push_back(i);
+    }
+    std::vector<uint64_t> r(regs.size());
+    RBX_TRY(count_regs(c, regs, r.data()));
+    for (size_t j = 0; j < idx.size(); ++j) {
+        out[idx[j]] = r[j];
+        hl[idx[j]]->card = r[j];  // store the (valid) cached cardinality
+    }
+    return RBX_OK;
+}
+
+static int hll_count_each(rbx_ctx *c, const std::vector<std::string> &names, uint64_t *out) {
+    RBX_ENTER(c, c->stream);
+    const uint32_t n = (uint32_t)names.size();
+    std::vector<HllState *> hl(n);
+    std::vector<std::shared_ptr<HllState>> keep(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        RBX_TRY(hll_get(c, names[i], false, c->stream, &keep[i], nullptr));
+        hl[i] = keep[i].get();
+    }
+    return pfcount_each(c, hl, out);
+}
+
+// PFCOUNT k1..kn: one key = the cached single-key count; several = count of the union
+int hll_count(rbx_ctx *c, const std::vector<std::string> &names, uint64_t *out) {
+    if (names.size() == 1) return hll_count_each(c, names, out);
+    RBX_ENTER(c, c->stream);
+    std::vector<std::shared_ptr<HllState>> keep;
+    std::vector<uint8_t *> srcs;
+    for (const auto &nm : names) {
+        std::shared_ptr<HllState> h;
+        RBX_TRY(hll_get(c, nm, false, c->stream, &h, nullptr));
+        if (h) {
+            srcs.push_back(h->d_regs);
+            keep.push_back(h);
+        }
+    }
+    if (srcs.empty()) {
+        *out = 0;
+        return RBX_OK;
+    }
+    RBX_TRY(c->ptrs.reserve(srcs.size() * sizeof(uint8_t *)));
+    RBX_TRY(c->out_bytes.reserve(kHllBytes));
+    HIP_TRY(hipMemcpyAsync(c->ptrs.p, srcs.data(), srcs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    launch_hll_union(c->ptrs.as<uint8_t *>(), (uint32_t)srcs.size(), c->out_bytes.as<uint8_t>(), c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<uint8_t *> u{c->out_bytes.as<uint8_t>()};
+    return count_regs(c, u, out);
+}
+
+// PFMERGE dest src1..srcn (dest's own registers included)
+int hll_merge(rbx_ctx *c, const std::string &dest, const std::vector<std::string> &srcs) {
+    RBX_ENTER(c, c->stream);
+    std::vector<std::shared_ptr<HllState>> keep;
+    std::vector<uint8_t *> sp;
+    for (const auto &s : srcs) {  // type-check every source first (isHLLObjectOrReply)
+        std::shared_ptr<HllState> h;
+        RBX_TRY(hll_get(c, s, false, c->stream, &h, nullptr));
+        if (h) {
+            sp.push_back(h->d_regs);
+            keep.push_back(h);
+        }
+    }
+    std::shared_ptr<HllState> d;
+    RBX_TRY(hll_get(c, dest, true, c->stream, &d, nullptr));
+    RBX_TRY(resolve_dense(c, d.get()));
+    for (auto &h : keep) {
+        RBX_TRY(resolve_dense(c, h.get()));
+        d->dense = d->dense || h->dense;  // pfmergeCommand: use_dense if any input is
+    }
+    if (!sp.empty()) {
+        RBX_TRY(c->ptrs.reserve(sp.size() * sizeof(uint8_t *)));
+        HIP_TRY(hipMemcpyAsync(c->ptrs.p, sp.data(), sp.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+        launch_hll_merge(d->d_regs, c->ptrs.as<uint8_t *>(), (uint32_t)sp.size(), c->stream);
+        HIP_TRY(hipGetLastError());
+        RBX_TRY(replay_merge(c, {d.get()}, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    d->card |= 1ULL << 63;  // HLL_INVALIDATE_CACHE
+    return RBX_OK;
+}
+
+// Redis HLL strings: 16-byte header ("HYLL", encoding, 3 unused, 8 cached-cardinality bytes)
+// + dense registers (HLL_DENSE_SET_REGISTER layout, 6 bits each, LSB-first) or sparse opcodes.
+constexpr uint64_t kHllDenseLen = 16 + 12288;
+
+static void hll_header(uint8_t *s, int sparse, uint64_t card) {
+    memcpy(s, "HYLL", 4);
+    s[4] = (uint8_t)sparse;  // HLL_DENSE 0 / HLL_SPARSE 1
+    s[5] = s[6] = s[7] = 0;
+    for (int i = 0; i < 8; ++i) s[8 + i] = (uint8_t)(card >> (8 * i));
+}
+
+static void hll_encode_dense(const uint8_t *regs, uint8_t *p) {
+    memset(p, 0, 12288);
+    for (unsigned long r = 0; r < 16384; ++r) {
+        const unsigned long byte = r * 6 / 8, fb = r * 6 & 7, fb8 = 8 - fb, v = regs[r];
+        p[byte] |= (uint8_t)(v << fb);
+        if (byte + 1 < 12288) p[byte + 1] |= (uint8_t)(v >> fb8);
+    }
+}
+
+// Sparse opcodes with the fewest bytes: zero runs as ZERO (<= 64) or XZERO (65..16384), equal
+// values as VAL runs of <= 4 (value 1..32).  Returns false when a register exceeds 32 (the
+// sparse format cannot hold it).  Used for RBX_HLL_SPARSE exports of keys Redis holds dense
+// (a sparse key exports the string it was built as, see hll_sparse_string).
+static bool hll_encode_sparse(const uint8_t *regs, std::vector<uint8_t> &out) {
+    out.clear();
+    for (uint32_t i = 0; i < 16384;) {
+        const uint8_t v = regs[i];
+        uint32_t j = i + 1;
+        while (j < 16384 && regs[j] == v) ++j;
+        uint32_t run = j - i;
+        if (v == 0) {
+            if (run > 64) {
+                out.push_back((uint8_t)(0x40 | ((run - 1) >> 8)));
+                out.push_back((uint8_t)((run - 1) & 0xff));
+            } else {
+                out.push_back((uint8_t)(run - 1));
+            }
+        } else {
+            if (v > 32) return false;
+            for (; run; run -= std::min<uint32_t>(run, 4))
+                out.push_back((uint8_t)(0x80 | ((v - 1) << 2) | (std::min<uint32_t>(run, 4) - 1)));
+        }
+        i = j;
+    }
+    return true;
+}
+
+// The sparse string of a key Redis holds sparse, as it was built (k_hll_sparse_replay's list):
+// an XZERO opcode is two bytes, ZERO / VAL one.  The caller holds a CallScope on c->stream.
+static int hll_sparse_string(rbx_ctx *c, HllState *h, std::vector<uint8_t> &out) {
+    uint32_t st[kHllStateWords];
+    HIP_TRY(hipMemcpyAsync(st, h->d_promoted, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out.clear();
+    if (st[1] == 0) {  // createHLLObject
+        out = {0x7f, 0xff};
+        return RBX_OK;
+    }
+    std::vector<uint16_t> ops(st[1]);
+    HIP_TRY(hipMemcpy(ops.data(), h->d_sp_ops, ops.size() * 2, hipMemcpyDeviceToHost));
+    for (uint16_t op : ops) {
+        if (op >= 0x100) out.push_back((uint8_t)(op >> 8));
+        out.push_back((uint8_t)op);
+    }
+    if (out.size() != st[2]) return fail(RBX_E_DEVICE, "sparse HLL string length mismatch");
+    return RBX_OK;
+}
+
+static int hll_export_enc(rbx_ctx *c, const std::string &name, int encoding, uint8_t *out, uint64_t cap,
+                          uint64_t *len) {
+    if (encoding < RBX_HLL_DENSE || encoding > RBX_HLL_AS_STORED)
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "encoding must be RBX_HLL_DENSE, RBX_HLL_SPARSE or RBX_HLL_AS_STORED");
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<HllState> h;
+    RBX_TRY(hll_get(c, name, false, c->stream, &h, nullptr));
+    if (!h) {
+        if (len) *len = 0;
+        return RBX_OK;
+    }
+    if (encoding != RBX_HLL_DENSE) RBX_TRY(resolve_dense(c, h.get()));
+    std::vector<uint8_t> s;
+    bool sparse = false;
+    if (encoding != RBX_HLL_DENSE && !h->dense) {
+        std::vector<uint8_t> ops;
+        RBX_TRY(hll_sparse_string(c, h.get(), ops));
+        s.resize(16 + ops.size());
+        memcpy(s.data() + 16, ops.data(), ops.size());
+        sparse = true;
+    } else {
+        std::vector<uint8_t> regs(kHllBytes);
+        HIP_TRY(hipMemcpyAsync(regs.data(), h->d_regs, kHllBytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (encoding == RBX_HLL_SPARSE) {
+            std::vector<uint8_t> ops;
+            if (!hll_encode_sparse(regs.data(), ops))
+                return fail(RBX_E_ILLEGAL_ARGUMENT, "a register exceeds 32: not representable in the sparse encoding");
+            s.resize(16 + ops.size());
+            memcpy(s.data() + 16, ops.data(), ops.size());
+            sparse = true;
+        } else {
+            s.resize(kHllDenseLen);
+            hll_encode_dense(regs.data(), s.data() + 16);
+        }
+    }
+    hll_header(s.data(), sparse, h->card);
+    if (len) *len = s.size();
+    if (out) memcpy(out, s.data(), std::min<uint64_t>(cap, s.size()));
+    return RBX_OK;
+}
+
+// accepts the Redis dense and sparse encodings (isHLLObjectOrReply validation)
+static int hll_import(rbx_ctx *c, const std::string &name, const uint8_t *bytes, uint64_t len) {
+    if (len < 16 || memcmp(bytes, "HYLL", 4) != 0 || bytes[4] > 1) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+    std::vector<uint8_t> regs(kHllBytes, 0);
+    std::vector<uint16_t> ops;  // sparse: the opcodes as stored (SET keeps the string)
+    if (bytes[4] == 0) {
+        if (len != kHllDenseLen) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+        const uint8_t *p = bytes + 16;
+        for (unsigned long r = 0; r < 16384; ++r) {
+            unsigned long byte = r * 6 / 8, fb = r * 6 & 7, fb8 = 8 - fb;
+            unsigned long b0 = p[byte], b1 = byte + 1 < 12288 ? p[byte + 1] : 0;
+            regs[r] = (uint8_t)(((b0 >> fb) | (b1 << fb8)) & 63);
+        }
+    } else {
+        const uint8_t *p = bytes + 16, *end = bytes + len;
+        uint64_t idx = 0;
+        while (p < end) {
+            uint8_t b = *p;
+            uint64_t run;
+            if ((b & 0xc0) == 0) {  // ZERO
+                run = (b & 0x3f) + 1;
+                ops.push_back(b);
+                p++;
+            } else if ((b & 0xc0) == 0x40) {  // XZERO
+                if (p + 1 >= end) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+                run = (((uint64_t)(b & 0x3f) << 8) | p[1]) + 1;
+                ops.push_back((uint16_t)(b << 8 | p[1]));
+                p += 2;
+            } else {  // VAL
+                ops.push_back(b);
+                run = (b & 3) + 1;
+                uint8_t v = ((b >> 2) & 0x1f) + 1;
+                if (idx + run > 16384) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+                for (uint64_t j = 0; j < run; ++j) regs[idx + j] = v;
+                p++;
+            }
+            idx += run;
+            if (idx > 16384) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+        }
+        if (idx != 16384) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+    }
+    RBX_ENTER(c, c->stream);
+    Entry *ex = c->ks.find(name);
+    std::shared_ptr<HllState> h;
+    if (ex && ex->type == KType::Hll) {
+        h = ex->hll;
+        ex->expire_at = -1;  // SET discards the timeout
+    } else {
+        c->ks.generation++;
+        RBX_TRY(hll_alloc(c, c->stream, &h));
+        c->ks.put(name, Entry{KType::Hll, nullptr, nullptr, h});
+    }
+    uint64_t card = 0;
+    for (int i = 0; i < 8; ++i) card |= (uint64_t)bytes[8 + i] << (8 * i);
+    h->card = card;
+    h->dense = bytes[4] == 0;  // SET keeps the string's encoding
+    RBX_TRY(hll_ops_reserve(h.get(), ops.size()));
+    // state: not promoted, the stored opcodes (a sparse string covers 16384 registers: >= 1)
+    const uint32_t st[kHllStateWords] = {0u, (uint32_t)ops.size(), (uint32_t)(len - 16), 0u};
+    HIP_TRY(hipMemcpyAsync(h->d_promoted, st, sizeof(st), hipMemcpyHostToDevice, c->stream));
+    if (!ops.empty())
+        HIP_TRY(hipMemcpyAsync(h->d_sp_ops, ops.data(), ops.size() * 2, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_regs, regs.data(), kHllBytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+static int hll_open(rbx_ctx *c, const std::string &name, int create, rbx_hll **out) {
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<HllState> h;
+    RBX_TRY(hll_get(c, name, create != 0, c->stream, &h, nullptr));
+    if (!h) return fail(RBX_E_NO_SUCH_KEY, "ERR no such key");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = new rbx_hll{c, name, h, c->ks.generation};
+    c->refs.fetch_add(1);
+    return RBX_OK;
+}
+
+// ---- register packing (the exchange step of an element-partitioned HLL set) ------------------
+// hlls[i]'s 16384 registers <-> d_buf[i*16384, (i+1)*16384), on `st` (both enqueue only).
+static int hll_handles_regs(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, hipStream_t st,
+                            std::vector<uint8_t *> *regs) {
+    regs->resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!hlls[i]) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL hll handle");
+        RBX_TRY(hll_bind(c, hlls[i], true, st));
+        (*regs)[i] = hlls[i]->st->d_regs;
+    }
+    return RBX_OK;
+}
+
+static int hll_pack_locked(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, uint8_t *d_buf, bool unpack_max,
+                           hipStream_t st) {
+    std::vector<uint8_t *> regs;
+    RBX_TRY(hll_handles_regs(c, hlls, n, st, &regs));
+    if (!n) return RBX_OK;
+    RBX_TRY(c->ptrs.reserve(n * sizeof(uint8_t *)));
+    HIP_TRY(hipMemcpyAsync(c->ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, st));
+    launch_hll_pack(c->ptrs.as<uint8_t *>(), n, d_buf, unpack_max, st);
+    HIP_TRY(hipGetLastError());
+    if (unpack_max) {
+        // the exchange merges the other ranks' registers in: a sparse HLL's string takes them
+        // as PFMERGE's write-back would (ascending registers, promotion by the same rules)
+        std::vector<HllState *> hs(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            hlls[i]->st->card |= 1ULL << 63;  // HLL_INVALIDATE_CACHE
+            hs[i] = hlls[i]->st.get();
+        }
+        RBX_TRY(replay_merge(c, hs, st));
+    }
+    // `regs` is a pageable host vector: the runtime has staged it when hipMemcpyAsync returns
+    return RBX_OK;
+}
+
+static int hll_pack(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, uint8_t *d_buf, bool unpack_max, void *stream) {
+    if (!c || (n && (!hlls || !d_buf))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    return hll_pack_locked(c, hlls, n, d_buf, unpack_max, st);
+}
+
+}  // namespace rbx
+
+using namespace rbx;
+
+extern "C" {
+
+int rbx_hll_add_multi(rbx_ctx *c, const char *const *names, uint32_t nseg, const uint64_t *seg_offsets,
+                      const rbx_keys *elements, uint8_t *out_changed) {
+    if (!c || !names || !seg_offsets) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::vector<std::string> v;
+    RBX_TRY(cstr_names(names, nseg, &v));
+    return hll_add_multi(c, v, seg_offsets, elements, out_changed);
+}
+
+int rbx_hll_add_multi_n(rbx_ctx *c, const rbx_name *names, uint32_t nseg, const uint64_t *seg_offsets,
+                        const rbx_keys *elements, uint8_t *out_changed) {
+    if (!c || !names || !seg_offsets) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::vector<std::string> v;
+    RBX_TRY(names_of(names, nseg, &v));
+    return hll_add_multi(c, v, seg_offsets, elements, out_changed);
+}
+
+int rbx_hll_add(rbx_ctx *c, const char *name, const rbx_keys *elements, int *changed) {
+    if (!c || !name || !elements) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    uint64_t seg[2] = {0, elements->n};
+    uint8_t ch = 0;
+    RBX_TRY(hll_add_multi(c, {std::string(name)}, seg, elements, &ch));
+    if (changed) *changed = ch;
+    return RBX_OK;
+}
+
+int rbx_hll_count_each(rbx_ctx *c, const char *const *names, uint32_t n, uint64_t *out) {
+    if (!c || (n && (!names || !out))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::vector<std::string> v;
+    RBX_TRY(cstr_names(names, n, &v));
+    return hll_count_each(c, v, out);
+}
+
+int rbx_hll_count(rbx_ctx *c, const char *const *names, uint32_t n, uint64_t *out) {
+    if (!c || !names || !out || n == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL/empty argument");
+    std::vector<std::string> v;
+    RBX_TRY(cstr_names(names, n, &v));
+    return hll_count(c, v, out);
+}
+
+int rbx_hll_count_n(rbx_ctx *c, const rbx_name *names, uint32_t n, uint64_t *out) {
+    if (!c || !names || !out || n == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL/empty argument");
+    std::vector<std::string> v;
+    RBX_TRY(names_of(names, n, &v));
+    return hll_count(c, v, out);
+}
+
+int rbx_hll_merge(rbx_ctx *c, const char *dest, const char *const *srcs, uint32_t nsrc) {
+    if (!c || !dest || (nsrc && !srcs)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::vector<std::string> v;
+    RBX_TRY(cstr_names(srcs, nsrc, &v));
+    return hll_merge(c, dest, v);
+}
+
+int rbx_hll_merge_n(rbx_ctx *c, rbx_name dest, const rbx_name *srcs, uint32_t nsrc) {
+    if (!c || (!dest.bytes && dest.len) || (nsrc && !srcs)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::vector<std::string> v;
+    RBX_TRY(names_of(srcs, nsrc, &v));
+    return hll_merge(c, name_of(dest), v);
+}
+
+int rbx_hll_export_enc(rbx_ctx *c, const char *name, int encoding, uint8_t *out, uint64_t cap, uint64_t *len) {
+    if (!c || !name) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return hll_export_enc(c, name, encoding, out, cap, len);
+}
+
+int rbx_hll_export_enc_n(rbx_ctx *c, rbx_name name, int encoding, uint8_t *out, uint64_t cap, uint64_t *len) {
+    if (!c || (!name.bytes && name.len)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return hll_export_enc(c, name_of(name), encoding, out, cap, len);
+}
+
+int rbx_hll_export(rbx_ctx *c, const char *name, uint8_t *out, uint64_t cap, uint64_t *len) {
+    return rbx_hll_export_enc(c, name, RBX_HLL_DENSE, out, cap, len);
+}
+
+int rbx_hll_import(rbx_ctx *c, const char *name, const uint8_t *bytes, uint64_t len) {
+    if (!c || !name || !bytes) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return hll_import(c, name, bytes, len);
+}
+
+int rbx_hll_import_n(rbx_ctx *c, rbx_name name, const uint8_t *bytes, uint64_t len) {
+    if (!c || (!name.bytes && name.len) || !bytes) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return hll_import(c, name_of(name), bytes, len);
+}
+
+int rbx_hll_delete(rbx_ctx *c, const char *name, int *deleted) {
+    if (!c || !name) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return ks_del(c->ks, {std::string(name)}, deleted);
+}
+
+int rbx_hll_exists(rbx_ctx *c, const char *name, int *exists) {
+    if (!c || !name || !exists) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return ks_exists(c->ks, {std::string(name)}, exists);
+}
+
+int rbx_hll_open(rbx_ctx *c, const char *name, int create, rbx_hll **out) {
+    if (!c || !name || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return hll_open(c, name, create, out);
+}
+
+int rbx_hll_open_n(rbx_ctx *c, rbx_name name, int create, rbx_hll **out) {
+    if (!c || (!name.bytes && name.len) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return hll_open(c, name_of(name), create, out);
+}
+
+int rbx_hll_close(rbx_hll *h) {
+    if (!h) return RBX_OK;
+    rbx_ctx *c = h->ctx;
+    {
+        std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+        delete h;
+    }
+    ctx_release(c);
+    return RBX_OK;
+}
+
+int rbx_hll_registers_dev(rbx_hll *h, void **d_regs) {
+    if (!h || !d_regs) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    rbx_ctx *c = h->ctx;
+    RBX_ENTER(c, c->stream);
+    RBX_TRY(hll_bind(c, h, true, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // a re-created HLL's zero fill lands first
+    *d_regs = h->st->d_regs;
+    return RBX_OK;
+}
+
+int rbx_hll_add_multi_dev(rbx_ctx *c, rbx_hll *const *hlls, uint32_t nseg, const uint64_t *d_seg_offsets,
+                          const uint64_t *h_seg_offsets, const rbx_keys *d_elements, uint32_t *d_changed,
+                          void *stream) {
+    (void)d_seg_offsets;
+    if (!c || !hlls || !h_seg_offsets || !d_changed) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(validate_keys(d_elements));
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    std::vector<HllState *> hl(nseg);
+    for (uint32_t s = 0; s < nseg; ++s) {
+        if (!hlls[s]) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL hll handle");
+        RBX_TRY(hll_bind(c, hlls[s], true, st));
+        hl[s] = hlls[s]->st.get();
+        hl[s]->card |= 1ULL << 63;  // conservatively invalidate (the flags are device-side)
+    }
+    return pfadd_run(c, hl, h_seg_offsets, keys_dev(d_elements), d_changed, st);
+}
+
+int rbx_hll_count_each_handles(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, uint64_t *out) {
+    if (!c || (n && (!hlls || !out))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    std::vector<HllState *> hl(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (hlls[i]) RBX_TRY(hll_bind(c, hlls[i], false, c->stream));
+        hl[i] = hlls[i] ? hlls[i]->st.get() : nullptr;
+    }
+    return pfcount_each(c, hl, out);
+}
+
+int rbx_hll_pack_registers(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, void *d_buf, void *stream) {
+    return hll_pack(c, hlls, n, (uint8_t *)d_buf, false, stream);
+}
+
+int rbx_hll_unpack_max_registers(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, const void *d_buf, void *stream) {
+    return hll_pack(c, hlls, n, (uint8_t *)d_buf, true, stream);
+}
+
+// ---- RCCL -----------------------------------------------------------------------------------
+int rbx_rccl_unique_id(uint8_t out[128]) {
+    if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    ncclUniqueId id;
+    ncclResult_t r = ncclGetUniqueId(&id);
+    if (r != ncclSuccess) return fail(RBX_E_DEVICE, ncclGetErrorString(r));
+    memcpy(out, id.internal, 128);
+    return RBX_OK;
+}
+
+int rbx_rccl_init(rbx_ctx *c, const uint8_t id[128], int nranks, int rank) {
+    if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks) return fail(RBX_E_ILLEGAL_ARGUMENT, "bad argument");
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    RBX_TRY(set_device(c));
+    if (c->comm) return fail(RBX_E_ILLEGAL_STATE, "rbx_rccl_init has already been called");
+    ncclUniqueId u;
+    memcpy(u.internal, id, 128);
+    ncclResult_t r = ncclCommInitRank(&c->comm, nranks, u, rank);
+    if (r != ncclSuccess) return fail(RBX_E_DEVICE, ncclGetErrorString(r));
+    c->nranks = nranks;
+    c->rank = rank;
+    return RBX_OK;
+}
+
+// the communicator as RCCL sees it (ncclCommCount / ncclCommUserRank)
+int rbx_rccl_info(rbx_ctx *c, int *nranks, int *rank) {
+    if (!c) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(c->ks.mu);
+    if (!c->comm) return fail(RBX_E_ILLEGAL_STATE, "rbx_rccl_init has not been called");
+    int n = 0, r = 0;
+    ncclResult_t e = ncclCommCount(c->comm, &n);
+    if (e == ncclSuccess) e = ncclCommUserRank(c->comm, &r);
+    if (e != ncclSuccess) return fail(RBX_E_DEVICE, ncclGetErrorString(e));
+    if (nranks) *nranks = n;
+    if (rank) *rank = r;
+    return RBX_OK;
+}
+
+// Every rank issues exactly ONE ncclAllReduce of n x 16384 bytes whatever its register pool
+// layout: the registers are packed in the caller's (name) order into one contiguous buffer,
+// max-reduced in place, and max-merged back.  (Coalescing "adjacent" pool blocks would make the
+// number and sizes of the collectives depend on each rank's allocation history, and RCCL would
+// pair mismatched calls.)  The pack/unpack kernels move 2 x 2 x n x 16 KiB of HBM (~0.1 ms for
+// the 163.84 MB of C4), next to the all-reduce itself.
+int rbx_hll_allreduce_max(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n) {
+    if (!c || (n && !hlls)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    if (!c->comm) return fail(RBX_E_ILLEGAL_STATE, "rbx_rccl_init has not been called");
+    const size_t bytes = (size_t)n * kHllBytes;
+    RBX_TRY(c->hll_pack.reserve(std::max<size_t>(bytes, 16)));
+    uint8_t *buf = c->hll_pack.as<uint8_t>();
+    RBX_TRY(hll_pack_locked(c, hlls, n, buf, false, c->stream));
+    ncclResult_t r = ncclAllReduce(buf, buf, bytes, ncclUint8, ncclMax, c->comm, c->stream);
+    if (r != ncclSuccess) return fail(RBX_E_DEVICE, ncclGetErrorString(r));
+    return hll_pack_locked(c, hlls, n, buf, true, c->stream);
+}
+
+// PFMERGE's input from another GPU: dst_name on dst := src_name on src (registers, encoding,
+// cached cardinality and promotion word), device to device.  A missing source deletes dst_name.
+int rbx_hll_copy_to(rbx_ctx *src, rbx_name src_name, rbx_ctx *dst, rbx_name dst_name) {
+    if (!src || !dst || (!src_name.bytes && src_name.len) || (!dst_name.bytes && dst_name.len))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    const std::string sn = name_of(src_name), dn = name_of(dst_name);
+    if (src == dst && sn == dn) return RBX_OK;
+    std::unique_lock<std::recursive_mutex> l1(src->ks.mu, std::defer_lock), l2(dst->ks.mu, std::defer_lock);
+    if (src == dst) l1.lock();
+    else std::lock(l1, l2);
+    RBX_TRY(set_device(src));
+    if (dst->shut) return fail(RBX_E_ILLEGAL_STATE, "the context has been shut down");
+    Entry *e = src->ks.find(sn);
+    if (e && e->type != KType::Hll) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+    if (!e) {
+        dst->ks.erase(dn);
+        return RBX_OK;
+    }
+    std::shared_ptr<HllState> sh = e->hll;
+    RBX_TRY(quiesce(src));
+    RBX_ENTER(dst, dst->stream);  // its lock is held already (recursive): the device and the scratch order
+    Entry *de = dst->ks.find(dn);
+    if (de && de->type != KType::Hll) {
+        dst->ks.erase(dn);
+        de = nullptr;
+    }
+    std::shared_ptr<HllState> h;
+    if (de) {
+        h = de->hll;
+        de->expire_at = -1;  // SET semantics
+    } else {
+        RBX_TRY(hll_alloc(dst, dst->stream, &h));
+        dst->ks.put(dn, Entry{KType::Hll, nullptr, nullptr, h});
+        dst->ks.generation++;
+    }
+    h->card = sh->card;
+    h->dense = sh->dense;
+    // the source's opcode count (its state word [1]) sizes the copy and the destination's list
+    uint32_t sst[kHllStateWords];
+    HIP_TRY(hipSetDevice(src->device));
+    HIP_TRY(hipMemcpy(sst, sh->d_promoted, sizeof(sst), hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(dst->device));
+    RBX_TRY(hll_ops_reserve(h.get(), sst[1]));
+    HIP_TRY(hipMemcpyPeerAsync(h->d_regs, dst->device, sh->d_regs, src->device, kHllBytes, dst->stream));
+    HIP_TRY(hipMemcpyPeerAsync(h->d_promoted, dst->device, sh->d_promoted, src->device, kHllStateWords * 4, dst->stream));
+    if (sst[1])
+        HIP_TRY(hipMemcpyPeerAsync(h->d_sp_ops, dst->device, sh->d_sp_ops, src->device, (size_t)sst[1] * 2, dst->stream));
+    HIP_TRY(hipStreamSynchronize(dst->stream));
+    return RBX_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,76 @@
+// tunables.h -- every host-side knob of rbx_tune (include/rbx_bench.h documents the keys); the kernels' own
+// are behind the set_* functions of rbx_kernels.h.  One instance, g_tune, defined in rbx_api.cpp beside
+// rbx_tune's table.  rbx_tune may run on another thread: a call that uses a knob twice reads it ONCE.
+#pragma once
+#include <atomic>
+#include <cstdint>
+
+namespace rbx {
+
+struct Tunables {
+    // ---- single-filter add (api_bloom.cpp) ----
+    // "add_partition": the partitioned add for one large filter, 0 never, 1 whenever k <= 16, 2 (default)
+    // by bitmap and batch size (use_add_partitioned has the thresholds and the measured crossovers)
+    std::atomic<int> add_partition_mode{2};
+    // "add_partition_diag" (profiling build only): 4 = the region kernel emits no records, 8 = it loads only
+    // its first two regions' pairs, 16 = it only loads, 64 = phase stamps (rbx_bench_add_stamps)
+    std::atomic<int> add_partition_diag{0};
+    // "add_records": how the add's region kernel reports which keys are new (add_partitioned.hip k_ba_mode): 0
+    // owner bits, 1 non-owner counters, 3 owner records, 2 (default) chosen from the sampled fill.  All exact.
+    std::atomic<int> add_record_policy{2};
+    // "add_single_seg_keys": adds of <= this many keys (k <= 16) run the per-segment kernel (run_add); 0 = off
+    std::atomic<uint64_t> seg_single_keys{256};
+    // "add_one_key": 1 = a 1-key add takes k_bloom_add_one
+    std::atomic<int> add_one{1};
+
+    // ---- single-filter contains (api_bloom.cpp) ----
+    // "contains_partition": the partitioned contains for one large filter, 0 never, 1 whenever k in
+    // [2, 16], 2 (default) when the bitmap is >= 256 MiB and the batch >= 4M keys (use_partitioned)
+    std::atomic<int> partition_mode{2};
+    // "contains_partition_flags" (profiling build only): 4 = stage 1 emits no pairs, 8 = the probe records
+    // no misses, 16 = one atomicOr per clear bit, 32 = no bit-0 gather, 64 = phase stamps
+    std::atomic<int> partition_flags{0};
+
+    // "wide_subchunk": bloom_wide_op's keys per sub-chunk cap (0 = default 2^29 / k; tests split small batches)
+    std::atomic<uint64_t> wide_subchunk{0};
+
+    // ---- host staging tiers (api_staging.cpp) ----
+    // "host_small_batches": 0 = every host batch on the pipelined path
+    std::atomic<int> small_host{1};
+    // "host_small_bytes": the small tier's byte limit (keys <= limit / 4)
+    std::atomic<uint64_t> small_bytes{4 << 20};
+    // "host_tiny_keys": the tiny tier's key limit; 0 = off
+    std::atomic<uint64_t> tiny_keys{16384};
+    // "host_tiny_spin": 1 (default) = a tiny call spins on its completion word (tiny_wait), 0 = stream sync
+    std::atomic<int> tiny_spin{1};
+
+    // ---- multi-tenant and stream (api_bloom_multi.cpp) ----
+    // "contains_multi_slots": the per-lane slot kernel 0 never, 1 always, 2 (default) past kSlotsMinBytes
+    std::atomic<int> multi_slots{2};
+    // "stream_chunk": caps a chunk of the ordered stream and of the 8-byte multi-tenant add at n commands
+    // (tests: many chunks on small batches); 0 = no cap
+    std::atomic<uint64_t> stream_chunk{0};
+    // "add_multi_table8": multi-tenant adds whenever (filter id, bit) fits 41 bits and k <= 32:
+    // 2 (default) optimistic SETBITs with conflict repair (k_maddx_*, r05), 0 the r03 16-byte table path
+    // (the fallback past 41 bits or k > 32; tests).  (1, the 8-byte first-setter table with the walk
+    // commit, measured 74.5 vs 53.3 ms at C3 and was removed in r06.)
+    std::atomic<int> add_multi_t8{2};
+    // "add_multi_conflict_log2": entries of the conflict table C, log2 (default 17: 1 MiB, L2-
+    // resident; tests use small ones to run the overflow path)
+    std::atomic<uint32_t> maddx_lgc{17};
+    // "add_multi_segment": 1 (default) a batch whose filters are all distinct runs its segments of
+    // <= add_multi_segmax keys one workgroup each (k_madd_seg: LDS first setters, plain word stores, no
+    // memory-side atomics), longer segments on the chunked path; 0 everything on the chunked path
+    std::atomic<int> madd_seg{1};
+    std::atomic<uint64_t> madd_segmax{16384};  // "add_multi_segmax"
+    // "add_multi_seg_grid": the per-segment kernel's workgroups, grid-stride over the segments
+    // (8192: C3 add 28.5 ms; 4096 28.9, 2048 29.9, 1024 31.1, 512 32.7; profiles/r06/r06d_*)
+    std::atomic<uint32_t> madd_seg_grid{8192};
+    // "stream_table8": 1 (default) the 8-byte first-setter table + walk commit (r04) when (fid, bit) fits
+    // 41 bits, 0 the r03 16-byte epoch-tagged table (the fallback past 41 bits; tests)
+    std::atomic<int> stream_table8{1};
+};
+
+extern Tunables g_tune;
+
+}  // namespace rbx

@@ -170,7 +170,7 @@ static void test_expiry() {
     CHECK(g_live_bitmaps.load() == 0);
 }
 
-// A "handle": remembers the object it resolved and the generation it saw (rbx_api.cpp bloom_bind).
+// A "handle": remembers the object it resolved and the generation it saw (api_bloom.cpp bloom_bind).
 struct FakeHandle {
     std::string name;
     std::shared_ptr<Bitmap> bm;
