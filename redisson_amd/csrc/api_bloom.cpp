@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "api_staging.h"
+#include "bucket_common.h"
 #include "tunables.h"
 
 namespace rbx {
@@ -252,35 +253,33 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
                                     unsigned long long *d_count, hipStream_t st) {
     const uint32_t k = f.k;
     const uint64_t size = f.mp.size;
-    const uint32_t nregions = (uint32_t)((size + (1ULL << kBkRegionBits) - 1) >> kBkRegionBits);
-    uint32_t lg = 0;
-    while ((1ULL << lg) < nregions) ++lg;
-    const uint32_t fb = lg > 6 ? lg - 6 : 0;
-    const uint32_t ncoarse = (nregions + (1u << fb) - 1) >> fb;
-    // keys per chunk: key ids fit 27 bits (6-byte region pairs) and a chunk's pairs stay <= 2^30
+    const uint32_t nb = (uint32_t)((size + (1ULL << kBkBucketBits) - 1) >> kBkBucketBits);
+    // keys per chunk: key ids fit 27 bits and a chunk's pairs stay <= 2^30
     uint64_t chunk = std::min<uint64_t>(1ULL << 27, (1ULL << 30) / (k - 1));
     const uint64_t nch = (keys.n + chunk - 1) / chunk;
     chunk = (keys.n + nch - 1) / nch;
     chunk = (chunk + 1023) / 1024 * 1024;
     const uint64_t ngroups = (chunk + 63) / 64;
-    // capacities assume every key survives stage 1; pairs spread uniformly over [0, size)
-    const double pairs_max = (double)chunk * (k - 1);
-    const double frac1 = std::min(1.0, (double)(1ULL << (kBkRegionBits + fb)) / (double)size);
-    const double frac2 = std::min(1.0, (double)(1ULL << kBkRegionBits) / (double)size);
-    uint64_t cap1 = (uint64_t)(pairs_max * frac1 / kBkSub * 1.15) + 8192;
-    uint64_t cap2 = (uint64_t)(pairs_max * frac2 * 1.2) + 4096;
-    cap1 = (cap1 + 8191) / 8192 * 8192;
-    cap2 = (cap2 + 63) / 64 * 64;
+    // Segment capacity.  Stage-1 block blk owns one segment per region.  With every key surviving
+    // stage 1 and the pairs spread uniformly over [0, size), a segment's fill is Poisson with mean
+    //   lambda = (keys per block) * (k - 1) * min(1, 2^22 / size).
+    // Chernoff: P(X >= lambda + x) <= exp(-x^2 / (2 (lambda + x/3))); x = 7 sqrt(lambda) + 24 keeps
+    // that below 1e-9 per segment for every lambda, i.e. below 1e-3 over the <= 2^19 segments of a
+    // chunk.  A pair past the capacity is probed directly (bk_direct): capacity never changes answers.
+    const uint32_t tile = bk_tile_keys(k);
+    const uint64_t ntiles0 = (chunk + tile - 1) / tile;
+    const uint64_t g0 = std::min<uint64_t>(ntiles0, kBkMaxGrid1);
+    const double lambda = (double)((ntiles0 + g0 - 1) / g0 * tile) * (k - 1) *
+                          std::min(1.0, (double)(1ULL << kBkBucketBits) / (double)size);
+    const uint64_t capS = ((uint64_t)(lambda + 7.0 * std::sqrt(lambda) + 24.0) + kBkLine - 1) / kBkLine * kBkLine;
     RBX_TRY(c->pc_bits.reserve(ngroups * 16));
     const uint32_t nmranges = (uint32_t)((chunk + (1ULL << kBkMissRangeBits) - 1) >> kBkMissRangeBits);
     // miss records: sized for 2 per key (C2-like batches hold ~0.2); beyond that the probe falls
     // back to a direct atomicOr per clear bit, so the answer never depends on the capacity
     const uint64_t capm = 2ULL << kBkMissRangeBits;
     RBX_TRY(c->pc_mrec.reserve((uint64_t)nmranges * capm * 4));
-    const uint64_t ncnt = 64 * kBkSub + (uint64_t)nregions + 256;  // cnt1 (padded), cnt2, mcnt
-    RBX_TRY(c->pc_cnt.reserve(ncnt * 4));
-    RBX_TRY(c->pc_pairs1.reserve((uint64_t)ncoarse * kBkSub * cap1 * 8));
-    RBX_TRY(c->pc_pairs2.reserve((uint64_t)nregions * cap2 * 6));  // 6-byte region pairs (lo u32 + hi u16)
+    RBX_TRY(c->pc_cnt.reserve((256 + (uint64_t)nb * g0) * 4));  // mcnt, segment counts
+    RBX_TRY(c->pc_pairs.reserve((uint64_t)nb * g0 * capS * 8));
     const int fl = fast_len(keys);
     for (uint64_t base = 0; base < keys.n; base += chunk) {
         PcArgs a{};
@@ -290,22 +289,16 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
         a.bm = f.bm;
         a.mp = f.mp;
         a.k = k;
-        a.nregions = nregions;
-        a.fb = fb;
-        a.cshift = kBkRegionBits + fb;
-        a.ncoarse = ncoarse;
-        a.cap1 = cap1;
-        a.cap2 = cap2;
+        a.nb = nb;
+        a.grid1 = (uint32_t)std::min<uint64_t>((a.nchunk + tile - 1) / tile, kBkMaxGrid1);  // <= g0
+        a.capS = capS;
         a.nwords4 = (size + 127) / 128 * 4;
         a.alive = c->pc_bits.as<unsigned long long>();
         a.miss = a.alive + ngroups;
-        a.cnt1 = c->pc_cnt.as<uint32_t>();
-        a.cnt2 = a.cnt1 + 64 * kBkSub;
-        a.pairs1 = c->pc_pairs1.as<unsigned long long>();
-        a.p2lo = c->pc_pairs2.as<uint32_t>();
-        a.p2hi = (uint16_t *)(a.p2lo + (uint64_t)nregions * cap2);
+        a.mcnt = c->pc_cnt.as<uint32_t>();
+        a.segcnt = a.mcnt + 256;
+        a.pairs = c->pc_pairs.as<unsigned long long>();
         a.mrec = c->pc_mrec.as<uint32_t>();
-        a.mcnt = a.cnt2 + nregions;
         a.capm = capm;
         a.nmranges = (uint32_t)((a.nchunk + (1ULL << kBkMissRangeBits) - 1) >> kBkMissRangeBits);
         a.out = d_out;
@@ -313,7 +306,7 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
         a.flags = (uint32_t)g_tune.partition_flags;
         if (a.flags & 64) RBX_TRY(phase_stamps(c, st, &a.stamps));
         HIP_TRY(hipMemsetAsync(a.miss, 0, ngroups * 8, st));
-        HIP_TRY(hipMemsetAsync(a.cnt1, 0, ncnt * 4, st));
+        HIP_TRY(hipMemsetAsync(a.mcnt, 0, 256 * 4, st));
         launch_contains_partitioned_chunk(a, fl, st);
         HIP_TRY(hipGetLastError());
     }

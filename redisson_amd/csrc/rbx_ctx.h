@@ -168,7 +168,7 @@ struct rbx_ctx {
     // staging for host-buffer calls
     DevBuf keys_bytes, keys_offs, out_bytes, seg_offs, counters, filt_table, ptrs, histo, misc, tile_segs, hll_tiles;
     DevBuf probe_table;  // ProbeDesc per entry of filt_table
-    DevBuf pc_bits, pc_cnt, pc_pairs1, pc_pairs2, pc_mrec;  // partitioned contains
+    DevBuf pc_bits, pc_cnt, pc_pairs, pc_mrec;  // partitioned contains
     DevBuf pa_p1, pa_p2, pa_cnt, pa_bits, pa_ctr, pa_recs;  // partitioned add
     DevBuf pa_stamps;  // add_partition_diag & 64: region-pass phase times (rbx_bench_add_stamps)
     DevBuf st_adds, st_nadds;    // ordered stream: add list, one add counter per chunk

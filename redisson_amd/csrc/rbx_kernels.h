@@ -73,10 +73,6 @@ struct AddChunkArgs {
 
 // partitioned contains (contains_partitioned.hip): one chunk of keys against one filter
 constexpr int kBkRegionBits = 19;  // 2^19 bits = 64 KiB bitmap region = one LDS image
-#ifndef RBX_BK_SUB
-#define RBX_BK_SUB 16
-#endif
-constexpr uint32_t kBkSub = RBX_BK_SUB;  // sub-partitions (own counters) per coarse bucket
 #ifndef RBX_BA_SUB
 #define RBX_BA_SUB 8
 #endif
@@ -88,28 +84,28 @@ struct PcArgs {
     const uint32_t *bm;
     ModParams mp;
     uint32_t k;
-    uint32_t nregions;      // ceil(size / 2^kBkRegionBits)
-    uint32_t fb;            // regions per coarse bucket = 2^fb
-    uint32_t cshift;        // kBkRegionBits + fb
-    uint32_t ncoarse;       // <= 64
-    uint64_t cap1, cap2;    // pair capacity per coarse sub-partition / per region
+    uint32_t nb;            // regions (stage-1 buckets) = ceil(size / 2^22) <= 1024
+    uint32_t grid1;         // stage-1 blocks G = min(tiles of the chunk, 512); every block owns a segment per bucket
+    uint64_t capS;          // pair capacity of one segment, a multiple of 8
     uint64_t nwords4;       // bitmap words rounded up to a multiple of 4
-    uint32_t *cnt1;         // ncoarse * kBkSub, zeroed
-    uint32_t *cnt2;         // nregions, zeroed
+    unsigned long long *pairs;  // nb * G segments of capS pairs (bit index << 32 | key id): segment (b, blk) at (blk*nb + b) * capS
+    uint32_t *segcnt;       // nb * G pair counts, all written by stage 1
     unsigned long long *alive;  // ceil(nchunk/64)
     unsigned long long *miss;   // ceil(nchunk/64), zeroed
     uint32_t *mrec;         // nmranges * capm: key ids of the probe's clear bits, by 2^19-key range
     uint32_t *mcnt;         // nmranges, zeroed
     uint64_t capm;
     uint32_t nmranges;      // ceil(nchunk / 2^kBkMissRangeBits) <= 256
-    unsigned long long *pairs1; // ncoarse * kBkSub * cap1
-    uint32_t *p2lo;         // nregions * cap2: region offset << 13 | key bits 0-12
-    uint16_t *p2hi;         // nregions * cap2: key bits 13-26
     uint8_t *out;
     unsigned long long *count;
     uint32_t flags;  // diagnostics only (rbx_tune "contains_partition_flags"); 0 in normal operation
-    unsigned long long *stamps;  // flags & 64: emit2 / probe phase times (rbx_bench_add_stamps), else null
+    unsigned long long *stamps;  // flags & 64: probe phase times (rbx_bench_add_stamps), else null
 };
+// keys per stage-1 tile: 512 threads, one key each (RBX_BK_PER8=2, two keys each at k <= 8: an A/B build)
+#ifndef RBX_BK_PER8
+#define RBX_BK_PER8 1
+#endif
+inline uint32_t bk_tile_keys(uint32_t k) { return k <= 8 ? 512u * RBX_BK_PER8 : 512u; }
 // k_bk_final's blocks: each adds its count to ONE counter, and same-address atomics serialise at the
 // kernel's end, so 512 blocks (grid-stride) rather than 2048 (r05, cf. k_stream_final8)
 inline unsigned grid_for_pc(uint64_t n) {
@@ -130,7 +126,7 @@ struct BaArgs {
     KeysDev keys;
     uint64_t base, nchunk;
     FilterDesc f;                 // bm, redis_len, mp, k
-    uint32_t ncoarse;             // level-1 buckets (<= 256, each kBkSub sub-partitions)
+    uint32_t ncoarse;             // level-1 buckets (<= 256, each kBaSub sub-partitions)
     uint32_t s1, s3;              // level-1 bucket = idx >> s1, region = idx >> s3 (s3 = kBaRegionBits)
     uint32_t f3;                  // fan-out bits of the rebucket (level 1 -> regions), <= 8
     uint32_t nregions;

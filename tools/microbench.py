@@ -416,8 +416,8 @@ def main():
 
     if "pcstamp" in a.what:
         # partitioned contains phase times (contains_partition_flags 64, exact results), C2 contains
-        # of n keys against a 2^32-bit filter holding n/2: emit2 (count, scan/reserve, place, store)
-        # and probe (top wait, probe loop, miss records) shares of block time
+        # of n keys against a 2^32-bit filter holding n/2: the probe's (top wait, probe loop, miss
+        # records) shares of block time
         import ctypes as C
 
         cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
@@ -433,12 +433,8 @@ def main():
             cnt[2:].zero_()
             ms = timed(stream, lambda: h.contains_dev(dk, cnt.data_ptr() + 16, stream=sp), 1)
             assert L.lib().rbx_bench_add_stamps(client.ctx, buf, 16) == 0
-            etot = sum(buf[:4])
             ptot = sum(buf[8:11])
             print(json.dumps({"bench": "pcstamp", "flags": fl, "ms": ms, "present": int(cnt[2].item()),
-                              "emit2_share": {nm: buf[i] / max(etot, 1) for i, nm in
-                                              enumerate(["count", "scan_reserve", "place", "store"])},
-                              "emit2_ticks_per_cu": etot / 256,
                               "probe_share": {nm: buf[8 + i] / max(ptot, 1) for i, nm in
                                               enumerate(["top_wait", "probe", "miss_records"])},
                               "probe_ticks_per_cu": ptot / 256}), flush=True)
