@@ -230,6 +230,7 @@ SIGNATURES = {
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "rbx_selftest_hash128": (None, [u8p, C.c_uint64, u64p]),
+    "rbx_selftest_bloom_indexes": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
     "rbx_selftest_plain_string": (C.c_int, [C.c_double, C.c_char_p, C.c_int]),
 }
 

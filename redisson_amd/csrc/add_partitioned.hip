@@ -103,13 +103,13 @@ __global__ __launch_bounds__(kBaS1Threads) void k_ba_stage1(KeysDev keys, uint64
             if constexpr (KP) {
                 if (t < nchunk) hh128_regs<(KLEN > 0 ? KLEN : 16)>(kx[q], h1, h2);
             } else {
-                if (t < nchunk) bk_hash<KLEN>(keys, base + t, h1, h2);
+                if (t < nchunk) hash_key<KLEN>(keys, base + t, h1, h2);
             }
-            uint64_t h = h1;
+            uint64_t h = h1;  // registers of its own: a BloomSeq here reorders the KMAX 8 code
 #pragma unroll
             for (int j = 0; j < KMAX; ++j) {
-                if ((uint32_t)j < f.k) idx[q][j] = mod63(h & 0x7fffffffffffffffULL, f.mp);
-                h += (j & 1) ? h1 : h2;
+                if ((uint32_t)j < f.k) idx[q][j] = BloomSeq::index_of(h, f.mp);
+                h += BloomSeq::step(j, h1, h2);
             }
         }
         if constexpr (KP) {
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kBaS1Threads) void k_ba_stage1(KeysDev keys, uint64
         }
         __syncthreads();
         uint32_t gb = 0;
-        if (threadIdx.x < 64) bk_scan256(s_cnt, ncoarse, s_start, s_pos);
+        if (threadIdx.x < 64) bk_scan<4>(s_cnt, ncoarse, s_start, s_pos);
         else if (threadIdx.x >= 256 && threadIdx.x - 256 < ncoarse) {
             const uint32_t b = threadIdx.x - 256;
             if (s_cnt[b]) gb = atomicAdd(&cnt1[b * kBaSub + sub], s_cnt[b]);
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kBaRbThreads) void k_ba_rebucket(const unsigned lon
         __syncthreads();
         ps.mark(0);
         uint32_t gb = 0;
-        if (threadIdx.x < 64) bk_scan256(s_cnt, nf, s_start, s_pos);
+        if (threadIdx.x < 64) bk_scan<4>(s_cnt, nf, s_start, s_pos);
         else if (threadIdx.x >= 256 && threadIdx.x - 256 < nf) {
             const uint32_t f = threadIdx.x - 256;
             const uint32_t r = (parent << fo) + f;
@@ -386,13 +386,7 @@ __global__ __launch_bounds__(1024) void k_ba_mode(const uint32_t *__restrict__ b
 // take another round; every round resolves at least one bit, so the loop ends.
 constexpr uint32_t kBaRegionThreads = 1024;
 constexpr uint32_t kBaPer = kBaMaxRegionPairs / kBaRegionThreads;  // pairs per thread
-constexpr uint32_t kBaTableBits = 10;                               // 1024 collision slots
 static_assert(kBaPer <= 32, "pair masks are 32-bit");
-
-__device__ __forceinline__ uint32_t ba_slot(uint32_t off, uint32_t t) {
-    return ((off * 2654435761u) >> (32 - kBaTableBits)) + t & ((1u << kBaTableBits) - 1);
-}
-
 
 // C (6-byte pairs, pipelined) -----------------------------------------------------------
 // The region pass (the resolution of the r02 k_ba_region, removed in r06), with the next region's inputs in flight while the current
@@ -697,7 +691,7 @@ __global__ __launch_bounds__(kBaRegionThreads) __attribute__((amdgpu_waves_per_e
                     uint32_t gb = 0;
                     const uint32_t q = tid - 128;
                     const bool reserver = tid >= 128 && q < nranges;
-                    if (tid < 64) bk_scan128(s_rc, nranges, s_rst, s_rpos, lane);
+                    if (tid < 64) bk_scan<2>(s_rc, nranges, s_rst, s_rpos, lane);
                     else if (reserver && s_rc[q]) gb = atomicAdd(&rec_cnt[q], s_rc[q]);
                     ba_bar();  // the scan, and the write-back's reads of s_bm, before s_rec is written
 #pragma unroll
@@ -896,19 +890,10 @@ static void ba_chunk(const BaArgs &a, hipStream_t st) {
                        a.mode);
 }
 
-template <int KLEN>
-static void ba_chunk_len(const BaArgs &a, hipStream_t st) {
-    if (a.f.k <= 8) ba_chunk<KLEN, 8>(a, st);
-    else ba_chunk<KLEN, 16>(a, st);
-}
-
 void launch_add_partitioned_chunk(const BaArgs &a, int klen_fast, hipStream_t st) {
-    switch (klen_fast) {
-    case 16: ba_chunk_len<16>(a, st); break;
-    case 32: ba_chunk_len<32>(a, st); break;
-    case 64: ba_chunk_len<64>(a, st); break;
-    default: ba_chunk_len<0>(a, st); break;
-    }
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<16, 16>(a.f.k, [&](auto kmax) { ba_chunk<decltype(klen)::value, decltype(kmax)::value>(a, st); });
+    });
 }
 
 }  // namespace rbx

@@ -266,7 +266,7 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
     // Chernoff: P(X >= lambda + x) <= exp(-x^2 / (2 (lambda + x/3))); x = 7 sqrt(lambda) + 24 keeps
     // that below 1e-9 per segment for every lambda, i.e. below 1e-3 over the <= 2^19 segments of a
     // chunk.  A pair past the capacity is probed directly (bk_direct): capacity never changes answers.
-    const uint32_t tile = bk_tile_keys(k);
+    const uint32_t tile = kBkTileKeys;
     const uint64_t ntiles0 = (chunk + tile - 1) / tile;
     const uint64_t g0 = std::min<uint64_t>(ntiles0, kBkMaxGrid1);
     const double lambda = (double)((ntiles0 + g0 - 1) / g0 * tile) * (k - 1) *

@@ -27,6 +27,9 @@ __device__ __forceinline__ void hash_key(const KeysDev &keys, uint64_t i, uint64
     }
 }
 
+// block_add_u64 and block_store_u64 differ in their last line only and stay two functions: every shared
+// form tried (a returned total, a callback, a flag, a template) moves an instruction in each kernel that
+// ends with one of them.
 __device__ __forceinline__ void block_add_u64(uint64_t v, unsigned long long *dst) {
     // wave reduce, then one atomic per wave-leader through LDS
     __shared__ unsigned long long s_part[8];
@@ -111,6 +114,17 @@ __device__ __forceinline__ uint32_t seg_from(const uint64_t *__restrict__ off, u
     while (s + 1 < nseg && off[s + 1] <= i) ++s;
     return s;
 }
+
+// There is no shared "gather the k words, build the zero mask" helper.  The block -- fill idxs[] and
+// word[] from a BloomSeq with every load issued before any is used, track maxidx, then the
+// `zm |= 1u << j` loop -- stays written out in k_bloom_add_probe, k_bloom_add_probe8, k_stream_probe,
+// k_stream_probe8 and k_maddx_gather.  Every helper form built (cursor by value, by reference, made
+// inside; the filter by reference or by value; word[] inside the helper or owned by the caller; one
+// function or two) compiles to other code in all five, and to other VGPR counts: at key length 16,
+// k_stream_probe8<.., 8> 84 -> 82 and <.., 32> 187 -> 199, k_bloom_add_probe8<.., 32> 122 -> 155,
+// k_bloom_add_probe<.., 8> 78 -> 70, k_stream_probe<.., 8> 80 -> 78, k_maddx_gather<.., 8> 76 -> 68.
+// The loops of an inlined function are unrolled before it is inlined, those of the hand form inside the
+// kernel's grid-stride loop.  A change of occupancy needs a measurement of its own.
 
 // ---------------------------------------------------------------------------------
 // add: first-setter table

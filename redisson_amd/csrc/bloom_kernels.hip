@@ -29,16 +29,16 @@ namespace rbx {
 // Loads bits [J0, J1) of the key (h already advanced to hash J0) and returns their AND.
 template <int J0, int J1>
 __device__ __forceinline__ bool probe_range(const uint32_t *__restrict__ bm, const ModParams &mp, uint32_t k,
-                                            uint64_t &h, uint64_t h1, uint64_t h2) {
+                                            BloomSeq &seq) {
     uint32_t word[J1 - J0], mask[J1 - J0];
 #pragma unroll
     for (int j = J0; j < J1; ++j) {
         if ((uint32_t)j < k) {
-            const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, mp);
+            const uint32_t idx = seq.index(mp);
             word[j - J0] = bm[idx >> 5];
             mask[j - J0] = bit_in_word(idx);
         }
-        h += (j & 1) ? h1 : h2;
+        seq.advance(j);
     }
     bool all = true;
 #pragma unroll
@@ -58,44 +58,44 @@ template <int KMAX, int SCHED = 0>
 __device__ __forceinline__ bool probe_all_set(const uint32_t *__restrict__ bm, const ModParams &mp,
                                               uint32_t k, uint64_t h1, uint64_t h2) {
     if constexpr (KMAX > 0) {
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
         if constexpr (SCHED == 0 || KMAX <= 1) {
-            return probe_range<0, KMAX>(bm, mp, k, h, h1, h2);
+            return probe_range<0, KMAX>(bm, mp, k, seq);
         } else if constexpr (SCHED >= 1 && SCHED <= 3) {
             constexpr int S = SCHED < KMAX ? SCHED : KMAX;
-            if (!probe_range<0, S>(bm, mp, k, h, h1, h2)) return false;
+            if (!probe_range<0, S>(bm, mp, k, seq)) return false;
             if (k <= (uint32_t)S) return true;
-            return probe_range<S, KMAX>(bm, mp, k, h, h1, h2);
+            return probe_range<S, KMAX>(bm, mp, k, seq);
         } else {  // doubling
-            if (!probe_range<0, 1>(bm, mp, k, h, h1, h2)) return false;
+            if (!probe_range<0, 1>(bm, mp, k, seq)) return false;
             if (k <= 1) return true;
             if constexpr (KMAX > 1) {
                 constexpr int E2 = KMAX < 3 ? KMAX : 3;
-                if (!probe_range<1, E2>(bm, mp, k, h, h1, h2)) return false;
+                if (!probe_range<1, E2>(bm, mp, k, seq)) return false;
                 if (k <= (uint32_t)E2) return true;
             }
             if constexpr (KMAX > 3) {
                 constexpr int E3 = KMAX < 7 ? KMAX : 7;
-                if (!probe_range<3, E3>(bm, mp, k, h, h1, h2)) return false;
+                if (!probe_range<3, E3>(bm, mp, k, seq)) return false;
                 if (k <= (uint32_t)E3) return true;
             }
-            if constexpr (KMAX > 7) return probe_range<7, KMAX>(bm, mp, k, h, h1, h2);
+            if constexpr (KMAX > 7) return probe_range<7, KMAX>(bm, mp, k, seq);
             return true;
         }
     } else {
         // any k: 8 loads in flight per round, stop after the first round with a zero bit
         bool all = true;
-        uint64_t h = h1;
+        uint64_t h = h1;  // registers of its own: the advance sits inside the j < k test
         for (uint32_t j0 = 0; j0 < k && all; j0 += 8) {
             uint32_t word[8], mask[8];
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const uint32_t j = j0 + t;
                 if (j < k) {
-                    const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, mp);
+                    const uint32_t idx = BloomSeq::index_of(h, mp);
                     word[t] = bm[idx >> 5];
                     mask[t] = bit_in_word(idx);
-                    h += (j & 1) ? h1 : h2;
+                    h += BloomSeq::step(j, h1, h2);
                 }
             }
 #pragma unroll
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void k_bloom_contains_q(KeysDev keys, const Fi
                     mp = filt[lo].mp;
                     e.bm = filt[lo].bm;
                 }
-                e.idx0 = mod63(e.h1 & 0x7fffffffffffffffULL, mp);
+                e.idx0 = BloomSeq::index_of(e.h1, mp);
                 qb[b * RANGE + pos] = e;
             }
         }
@@ -316,8 +316,8 @@ __global__ __launch_bounds__(256) void k_bloom_contains_q(KeysDev keys, const Fi
                 } else if (((++sjk[s]) & 0xffffu) >= (sjk[s] >> 16)) {
                     fin = fin_p = true;
                 } else {
-                    sidx[s] = mod63c(sh[s] & 0x7fffffffffffffffULL, MULTI ? smp[s] : single_mc);
-                    sh[s] += (sjk[s] & 1) ? sh1[s] : sh2[s];
+                    sidx[s] = BloomSeq::index_of(sh[s], MULTI ? smp[s] : single_mc);
+                    sh[s] += BloomSeq::step(sjk[s], sh1[s], sh2[s]);
                 }
                 if (fin) {
                     act[s] = false;
@@ -357,16 +357,16 @@ __global__ __launch_bounds__(256) void k_bloom_add_probe(KeysDev keys, uint64_t 
         hash_key<KLEN>(keys, i, h1, h2);
         uint32_t word[KMAX], idxs[KMAX];
         uint32_t maxidx = 0;
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if ((uint32_t)j < f.k) {
-                const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                const uint32_t idx = seq.index(f.mp);
                 idxs[j] = idx;
                 word[j] = f.bm[idx >> 5];
                 maxidx = idx > maxidx ? idx : maxidx;
             }
-            h += (j & 1) ? h1 : h2;
+            seq.advance(j);
         }
         uint32_t zm = 0;
 #pragma unroll
@@ -407,17 +407,17 @@ __global__ __launch_bounds__(256) void k_bloom_add_commit(KeysDev keys, uint64_t
             }
             uint64_t h1, h2;
             hash_key<KLEN>(keys, i, h1, h2);
-            uint64_t h = h1;
+            BloomSeq seq(h1, h2);
 #pragma unroll
             for (int j = 0; j < KMAX; ++j) {
                 if ((zm >> j) & 1u) {
-                    const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                    const uint32_t idx = seq.index(f.mp);
                     if (ht_owner(T, log2cap, epoch, ((uint64_t)f.fid << 32) | idx) == (uint32_t)t) {
                         isnew = true;
                         atomicOr(&f.bm[idx >> 5], bit_in_word(idx));
                     }
                 }
-                h += (j & 1) ? h1 : h2;
+                seq.advance(j);
             }
             if (isnew && seg_counts) atomicAdd(&seg_counts[seg], 1ULL);
         }
@@ -469,16 +469,16 @@ __global__ __launch_bounds__(256) void k_bloom_add_probe8(KeysDev keys, uint64_t
         uint64_t h1, h2;
         hash_key<KLEN>(keys, base + t, h1, h2);
         uint32_t word[KMAX], idxs[KMAX];
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if ((uint32_t)j < f.k) {
-                const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                const uint32_t idx = seq.index(f.mp);
                 idxs[j] = idx;
                 word[j] = f.bm[idx >> 5];
                 maxidx = idx > maxidx ? idx : maxidx;
             }
-            h += (j & 1) ? h1 : h2;
+            seq.advance(j);
         }
         uint32_t zm = 0;
 #pragma unroll
@@ -509,17 +509,17 @@ __global__ __launch_bounds__(256) void k_bloom_add_commit8(KeysDev keys, uint64_
         if (zm) {
             uint64_t h1, h2;
             hash_key<KLEN>(keys, base + t, h1, h2);
-            uint64_t h = h1;
+            BloomSeq seq(h1, h2);
 #pragma unroll
             for (int j = 0; j < KMAX; ++j) {
                 if ((zm >> j) & 1u) {
-                    const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                    const uint32_t idx = seq.index(f.mp);
                     if (ht8_owner(T, log2cap, idx) == (uint32_t)t) {
                         isnew = true;
                         atomicOr(&f.bm[idx >> 5], bit_in_word(idx));
                     }
                 }
-                h += (j & 1) ? h1 : h2;
+                seq.advance(j);
             }
         }
         if (out_new) out_new[base + t] = isnew;
@@ -544,15 +544,15 @@ __global__ __launch_bounds__(256) void k_bloom_add_probe_anyk(KeysDev keys, uint
         if (filt) f = filt[seg_from(seg_off, nseg, tile_seg0[i >> 8], i)];
         uint64_t h1, h2;
         hash_key<KLEN>(keys, i, h1, h2);
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
         uint32_t maxidx = 0;
         for (uint32_t j = 0; j < f.k; ++j) {
-            const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+            const uint32_t idx = seq.index(f.mp);
             maxidx = idx > maxidx ? idx : maxidx;
             const bool z = (f.bm[idx >> 5] & bit_in_word(idx)) == 0u;
             zflag[t * kstride + j] = z;
             if (z) ht_insert(T, log2cap, epoch, ((uint64_t)f.fid << 32) | idx, (uint32_t)t);
-            h += (j & 1) ? h1 : h2;
+            seq.advance(j);
         }
         raise_redis_len(f.redis_len, (unsigned long long)(maxidx >> 3) + 1ULL);
     }
@@ -581,17 +581,17 @@ __global__ __launch_bounds__(256) void k_bloom_add_commit_anyk(KeysDev keys, uin
         }
         uint64_t h1, h2;
         hash_key<KLEN>(keys, i, h1, h2);
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
         bool isnew = false;
         for (uint32_t j = 0; j < f.k; ++j) {
             if (zflag[t * kstride + j]) {
-                const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                const uint32_t idx = seq.index(f.mp);
                 if (ht_owner(T, log2cap, epoch, ((uint64_t)f.fid << 32) | idx) == (uint32_t)t) {
                     isnew = true;
                     atomicOr(&f.bm[idx >> 5], bit_in_word(idx));
                 }
             }
-            h += (j & 1) ? h1 : h2;
+            seq.advance(j);
         }
         if (isnew && seg_counts) atomicAdd(&seg_counts[seg], 1ULL);
         if (out_new) out_new[i] = isnew;
@@ -694,43 +694,16 @@ static void launch_contains_km(const KeysDev &keys, const uint32_t *bm, const Mo
     }
 }
 
-template <int KLEN>
-static void launch_contains_k(const KeysDev &keys, const uint32_t *bm, const ModParams &mp, uint32_t k,
-                              uint8_t *out, unsigned long long *count, hipStream_t st, unsigned grid) {
-    if (k <= 8) launch_contains_km<KLEN, 8>(keys, bm, mp, k, out, count, st, grid);
-    else if (k <= 16) launch_contains_km<KLEN, 16>(keys, bm, mp, k, out, count, st, grid);
-    else launch_contains_s<KLEN, 0, 0>(keys, bm, mp, k, out, count, st, grid);
-}
-
 void launch_bloom_contains(const KeysDev &keys, int klen_fast, const uint32_t *bm, const ModParams &mp,
                            uint32_t k, uint8_t *out, unsigned long long *count, hipStream_t st) {
     const unsigned grid = grid_for(keys.n, kMaxGrid);
-    switch (klen_fast) {
-    case 16: launch_contains_k<16>(keys, bm, mp, k, out, count, st, grid); break;
-    case 32: launch_contains_k<32>(keys, bm, mp, k, out, count, st, grid); break;
-    case 64: launch_contains_k<64>(keys, bm, mp, k, out, count, st, grid); break;
-    default: launch_contains_k<0>(keys, bm, mp, k, out, count, st, grid); break;
-    }
-}
-
-template <int KLEN>
-static void launch_contains_multi_k(const KeysDev &keys, const FilterDesc *filt, const uint64_t *seg_off,
-                                    uint32_t nseg, const uint32_t *tile_seg0, uint32_t kmax, uint8_t *out,
-                                    unsigned long long *counts, hipStream_t st, unsigned grid, bool slots) {
-    const int stage1 = g_stage1.load();  // read once per call
-    const bool dbl = stage1 == 4;
-    if ((slots || stage1 == 5) && keys.n < (1ULL << 32)) {  // slot kernel: u32 key indexes
-        launch_contains_q<KLEN, true>(keys, filt, seg_off, nseg, tile_seg0, FilterDesc{}, out, counts, st, grid);
-        return;
-    }
-    if (kmax <= 8) {
-        if (dbl) hipLaunchKernelGGL((k_bloom_contains_multi<KLEN, 8, 4>), dim3(grid), dim3(256), 0, st, keys, filt, seg_off, nseg, tile_seg0, out, counts);
-        else hipLaunchKernelGGL((k_bloom_contains_multi<KLEN, 8, 1>), dim3(grid), dim3(256), 0, st, keys, filt, seg_off, nseg, tile_seg0, out, counts);
-    } else if (kmax <= 16) {
-        if (dbl) hipLaunchKernelGGL((k_bloom_contains_multi<KLEN, 16, 4>), dim3(grid), dim3(256), 0, st, keys, filt, seg_off, nseg, tile_seg0, out, counts);
-        else hipLaunchKernelGGL((k_bloom_contains_multi<KLEN, 16, 1>), dim3(grid), dim3(256), 0, st, keys, filt, seg_off, nseg, tile_seg0, out, counts);
-    }
-    else hipLaunchKernelGGL((k_bloom_contains_multi<KLEN, 0, 0>), dim3(grid), dim3(256), 0, st, keys, filt, seg_off, nseg, tile_seg0, out, counts);
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<16>(k, [&](auto kmax) {
+            constexpr int KLEN = decltype(klen)::value, KMAX = decltype(kmax)::value;
+            if constexpr (KMAX > 0) launch_contains_km<KLEN, KMAX>(keys, bm, mp, k, out, count, st, grid);
+            else launch_contains_s<KLEN, 0, 0>(keys, bm, mp, k, out, count, st, grid);  // any k: one schedule
+        });
+    });
 }
 
 void launch_tile_seg0(const uint64_t *seg_off, uint32_t nseg, uint64_t nkeys, uint32_t *tile_seg0,
@@ -745,12 +718,24 @@ void launch_bloom_contains_multi(const KeysDev &keys, int klen_fast, const Filte
                                  const uint64_t *seg_off, uint32_t nseg, const uint32_t *tile_seg0, uint32_t kmax,
                                  uint8_t *out, unsigned long long *counts, hipStream_t st, bool slots) {
     const unsigned grid = grid_for(keys.n, kMaxGrid);
-    switch (klen_fast) {
-    case 16: launch_contains_multi_k<16>(keys, filt, seg_off, nseg, tile_seg0, kmax, out, counts, st, grid, slots); break;
-    case 32: launch_contains_multi_k<32>(keys, filt, seg_off, nseg, tile_seg0, kmax, out, counts, st, grid, slots); break;
-    case 64: launch_contains_multi_k<64>(keys, filt, seg_off, nseg, tile_seg0, kmax, out, counts, st, grid, slots); break;
-    default: launch_contains_multi_k<0>(keys, filt, seg_off, nseg, tile_seg0, kmax, out, counts, st, grid, slots); break;
-    }
+    const int stage1 = g_stage1.load();  // read once per call
+    with_klen(klen_fast, [&](auto klen) {
+        constexpr int KLEN = decltype(klen)::value;
+        if ((slots || stage1 == 5) && keys.n < (1ULL << 32)) {  // slot kernel: u32 key indexes
+            launch_contains_q<KLEN, true>(keys, filt, seg_off, nseg, tile_seg0, FilterDesc{}, out, counts, st, grid);
+            return;
+        }
+        with_kmax<16>(kmax, [&](auto km) {
+            constexpr int KMAX = decltype(km)::value;
+            auto go = [&](auto s1) {
+                hipLaunchKernelGGL((k_bloom_contains_multi<KLEN, KMAX, decltype(s1)::value>), dim3(grid), dim3(256), 0, st,
+                                   keys, filt, seg_off, nseg, tile_seg0, out, counts);
+            };
+            if constexpr (KMAX == 0) go(std::integral_constant<int, 0>{});  // any k: one schedule
+            else if (stage1 == 4) go(std::integral_constant<int, 4>{});
+            else go(std::integral_constant<int, 1>{});
+        });
+    });
 }
 
 template <int KLEN, int KMAX>
@@ -771,29 +756,25 @@ static void launch_add_chunk_k(const AddChunkArgs &a, hipStream_t st) {
                        a.count, a.seg_counts);
 }
 
+// generic k (k > 32)
 template <int KLEN>
-static void launch_add_chunk_len(const AddChunkArgs &a, hipStream_t st) {
-    if (a.kmax <= 8) launch_add_chunk_k<KLEN, 8>(a, st);
-    else if (a.kmax <= 16) launch_add_chunk_k<KLEN, 16>(a, st);
-    else if (a.kmax <= 32) launch_add_chunk_k<KLEN, 32>(a, st);
-    else {
-        const unsigned grid = grid_for(a.nchunk, kMaxGrid);
-        hipLaunchKernelGGL((k_bloom_add_probe_anyk<KLEN>), dim3(grid), dim3(256), 0, st, a.keys, a.base, a.nchunk,
-                           a.filt, a.seg_off, a.nseg, a.tile_seg0, a.single, a.table, a.log2cap, a.epoch,
-                           (uint8_t *)a.zmask, a.kmax);
-        hipLaunchKernelGGL((k_bloom_add_commit_anyk<KLEN>), dim3(grid), dim3(256), 0, st, a.keys, a.base,
-                           a.nchunk, a.filt, a.seg_off, a.nseg, a.tile_seg0, a.single, a.table, a.log2cap, a.epoch,
-                           (const uint8_t *)a.zmask, a.kmax, a.out_new, a.count, a.seg_counts);
-    }
+static void launch_add_chunk_anyk(const AddChunkArgs &a, hipStream_t st) {
+    const unsigned grid = grid_for(a.nchunk, kMaxGrid);
+    hipLaunchKernelGGL((k_bloom_add_probe_anyk<KLEN>), dim3(grid), dim3(256), 0, st, a.keys, a.base, a.nchunk, a.filt,
+                       a.seg_off, a.nseg, a.tile_seg0, a.single, a.table, a.log2cap, a.epoch, (uint8_t *)a.zmask, a.kmax);
+    hipLaunchKernelGGL((k_bloom_add_commit_anyk<KLEN>), dim3(grid), dim3(256), 0, st, a.keys, a.base, a.nchunk, a.filt,
+                       a.seg_off, a.nseg, a.tile_seg0, a.single, a.table, a.log2cap, a.epoch, (const uint8_t *)a.zmask,
+                       a.kmax, a.out_new, a.count, a.seg_counts);
 }
 
 void launch_bloom_add_chunk(const AddChunkArgs &a, int klen_fast, hipStream_t st) {
-    switch (klen_fast) {
-    case 16: launch_add_chunk_len<16>(a, st); break;
-    case 32: launch_add_chunk_len<32>(a, st); break;
-    case 64: launch_add_chunk_len<64>(a, st); break;
-    default: launch_add_chunk_len<0>(a, st); break;
-    }
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<32>(a.kmax, [&](auto kmax) {
+            constexpr int KLEN = decltype(klen)::value, KMAX = decltype(kmax)::value;
+            if constexpr (KMAX > 0) launch_add_chunk_k<KLEN, KMAX>(a, st);
+            else launch_add_chunk_anyk<KLEN>(a, st);
+        });
+    });
 }
 
 // add(T) (M/RedissonBloomFilter.java:99-102): SETBIT of the key's k bits, new iff one of them was 0.  One
@@ -812,16 +793,16 @@ __global__ __launch_bounds__(64) void k_bloom_add_one(KeysDev keys, FilterDesc f
     uint64_t h1, h2;
     hash_key<KLEN>(keys, 0, h1, h2);
     uint32_t idxs[KMAX], word[KMAX], maxidx = 0;
-    uint64_t h = h1;
+    BloomSeq bs(h1, h2);
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) {
         if ((uint32_t)j < f.k) {
-            const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+            const uint32_t idx = bs.index(f.mp);
             idxs[j] = idx;
             word[j] = f.bm[idx >> 5];
             maxidx = idx > maxidx ? idx : maxidx;
         }
-        h += (j & 1) ? h1 : h2;
+        bs.advance(j);
     }
     bool isnew = false;
 #pragma unroll
@@ -847,14 +828,14 @@ __global__ __launch_bounds__(64) void k_bloom_contains_one(KeysDev keys, const u
     uint64_t h1, h2;
     hash_key<KLEN>(keys, 0, h1, h2);
     uint32_t idxs[KMAX], word[KMAX];
-    uint64_t h = h1;
+    BloomSeq bs(h1, h2);
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) {
         if ((uint32_t)j < k) {
-            idxs[j] = mod63(h & 0x7fffffffffffffffULL, mp);
+            idxs[j] = bs.index(mp);
             word[j] = bm[idxs[j] >> 5];
         }
-        h += (j & 1) ? h1 : h2;
+        bs.advance(j);
     }
     bool all = true;
 #pragma unroll
@@ -864,27 +845,18 @@ __global__ __launch_bounds__(64) void k_bloom_contains_one(KeysDev keys, const u
     if (done) __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <int KLEN>
-static void launch_one_len(bool add, const KeysDev &keys, const FilterDesc &f, uint8_t *out, unsigned long long *count,
-                           uint32_t *done, uint32_t seq, hipStream_t st) {
-    if (add && f.k <= 8)
-        hipLaunchKernelGGL((k_bloom_add_one<KLEN, 8>), dim3(1), dim3(64), 0, st, keys, f, out, count, done, seq);
-    else if (add)
-        hipLaunchKernelGGL((k_bloom_add_one<KLEN, 16>), dim3(1), dim3(64), 0, st, keys, f, out, count, done, seq);
-    else if (f.k <= 8)
-        hipLaunchKernelGGL((k_bloom_contains_one<KLEN, 8>), dim3(1), dim3(64), 0, st, keys, f.bm, f.mp, f.k, out, done, seq);
-    else
-        hipLaunchKernelGGL((k_bloom_contains_one<KLEN, 16>), dim3(1), dim3(64), 0, st, keys, f.bm, f.mp, f.k, out, done, seq);
-}
-
 void launch_bloom_one(bool add, const KeysDev &keys, int klen_fast, const FilterDesc &f, uint8_t *out,
                       unsigned long long *count, uint32_t *done, uint32_t seq, hipStream_t st) {
-    switch (klen_fast) {
-    case 16: launch_one_len<16>(add, keys, f, out, count, done, seq, st); break;
-    case 32: launch_one_len<32>(add, keys, f, out, count, done, seq, st); break;
-    case 64: launch_one_len<64>(add, keys, f, out, count, done, seq, st); break;
-    default: launch_one_len<0>(add, keys, f, out, count, done, seq, st); break;
-    }
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<16, 16>(f.k, [&](auto kmax) {
+            constexpr int KLEN = decltype(klen)::value, KMAX = decltype(kmax)::value;
+            if (add)
+                hipLaunchKernelGGL((k_bloom_add_one<KLEN, KMAX>), dim3(1), dim3(64), 0, st, keys, f, out, count, done, seq);
+            else
+                hipLaunchKernelGGL((k_bloom_contains_one<KLEN, KMAX>), dim3(1), dim3(64), 0, st, keys, f.bm, f.mp, f.k, out,
+                                   done, seq);
+        });
+    });
 }
 
 // the completion word of a tiny host call whose work is several kernels or workgroups: stream order puts it
@@ -905,194 +877,6 @@ void launch_bitcount(const uint8_t *bytes, uint64_t nbytes, unsigned long long *
 void launch_digest(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st) {
     const unsigned grid = grid_for((nbytes + 15) / 16, 4096);
     hipLaunchKernelGGL(k_digest, dim3(grid), dim3(256), 0, st, bytes, nbytes, out);
-}
-
-}  // namespace rbx
-
-// ---------------------------------------------------------------------------------
-// Random-gather roofline probe: the contains kernel's memory pattern with the hashing
-// removed.  Each lane issues k independent 4-byte loads at pseudo-random word offsets
-// of a `nwords`-word table (same MLP structure as k_bloom_contains), XOR-reduced to a
-// sink so nothing is dead-code eliminated.
-// ---------------------------------------------------------------------------------
-namespace rbx {
-template <int K>
-__global__ __launch_bounds__(256) void k_gather_probe(const uint32_t *__restrict__ tbl, uint64_t nwords,
-                                                      uint64_t nkeys, uint64_t seed, uint32_t *__restrict__ sink) {
-    uint32_t acc = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nkeys; i += stride) {
-        uint64_t z = (seed + i) * 0x9E3779B97F4A7C15ULL;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-        z ^= z >> 27;
-        uint32_t w[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const uint32_t r = (uint32_t)(z >> (j & 1 ? 32 : 0)) ^ (uint32_t)(j * 0x9E3779B9u);
-            z += 0x632BE59BD9B4E019ULL;
-            w[j] = tbl[(uint64_t)r * nwords >> 32];
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) acc ^= w[j];
-    }
-    if (acc == 0x9E3779B9u) sink[0] = acc;  // practically never taken; keeps the loads live
-}
-
-void launch_gather_probe(const uint32_t *tbl, uint64_t nwords, uint64_t nkeys, uint32_t k, uint32_t *sink,
-                         hipStream_t st) {
-    const unsigned grid = grid_for(nkeys, kMaxGrid);
-    switch (k) {
-    case 10: hipLaunchKernelGGL(k_gather_probe<10>, dim3(grid), dim3(256), 0, st, tbl, nwords, nkeys, 0x5EEDull, sink); break;
-    default: hipLaunchKernelGGL(k_gather_probe<7>, dim3(grid), dim3(256), 0, st, tbl, nwords, nkeys, 0x5EEDull, sink); break;
-    }
-}
-}  // namespace rbx
-
-// ---------------------------------------------------------------------------------
-// Region-local gather probe: the table is cut into regions of `region_words`; workgroup b
-// works on regions b%8, b%8+8, ... in order (blocks b and b+8 share an XCD under the
-// observed round-robin placement -- speed only), each lane doing k random loads inside the
-// current region.  Measures the L2-resident gather rate a region-bucketed probe can reach.
-// ---------------------------------------------------------------------------------
-namespace rbx {
-__global__ __launch_bounds__(256) void k_gather_regions(const uint32_t *__restrict__ tbl, uint64_t nregions,
-                                                        uint64_t region_words, uint64_t per_region,
-                                                        uint32_t *__restrict__ sink) {
-    const uint32_t xcd = blockIdx.x & 7, local = blockIdx.x >> 3, nlocal = gridDim.x >> 3;
-    uint32_t acc = 0;
-    for (uint64_t r = xcd; r < nregions; r += 8) {
-        const uint32_t *base = tbl + r * region_words;
-        for (uint64_t i = (uint64_t)local * blockDim.x + threadIdx.x; i < per_region; i += (uint64_t)nlocal * blockDim.x) {
-            uint64_t z = (r * 0x9E3779B97F4A7C15ULL) ^ (i * 0xBF58476D1CE4E5B9ULL);
-            z ^= z >> 31;
-            z *= 0x94D049BB133111EBULL;
-            uint32_t w[6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                w[j] = base[(uint64_t)(uint32_t)(z >> (j & 1 ? 32 : 0) ^ (j * 0x9E3779B9u)) * region_words >> 32];
-                z += 0x632BE59BD9B4E019ULL;
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) acc ^= w[j];
-        }
-    }
-    if (acc == 0x9E3779B9u) sink[0] = acc;
-}
-
-// Segment-local gather probe (the locality of a multi-tenant batch, BASELINE C3): key i belongs
-// to segment i / keys_per_seg, segments are consecutive slices of seg_words words (wrapping over
-// the table), and every key does K random 4-byte loads inside its own segment.
-template <int K>
-__global__ __launch_bounds__(256) void k_gather_segments(const uint32_t *__restrict__ tbl, uint64_t nwords,
-                                                         uint64_t seg_words, uint64_t keys_per_seg, uint64_t nkeys,
-                                                         uint32_t *__restrict__ sink) {
-    uint32_t acc = 0;
-    const uint64_t nseg_tbl = nwords / seg_words;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nkeys; i += stride) {
-        const uint32_t *base = tbl + ((i / keys_per_seg) % nseg_tbl) * seg_words;
-        uint64_t z = (i + 0x5EEDull) * 0x9E3779B97F4A7C15ULL;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-        z ^= z >> 27;
-        uint32_t w[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const uint32_t r = (uint32_t)(z >> (j & 1 ? 32 : 0)) ^ (uint32_t)(j * 0x9E3779B9u);
-            z += 0x632BE59BD9B4E019ULL;
-            w[j] = base[(uint64_t)r * seg_words >> 32];
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) acc ^= w[j];
-    }
-    if (acc == 0x9E3779B9u) sink[0] = acc;
-}
-
-void launch_gather_segments(const uint32_t *tbl, uint64_t nwords, uint64_t seg_words, uint64_t keys_per_seg,
-                            uint64_t nkeys, uint32_t *sink, hipStream_t st) {
-    const unsigned grid = grid_for(nkeys, kMaxGrid);
-    hipLaunchKernelGGL(k_gather_segments<4>, dim3(grid), dim3(256), 0, st, tbl, nwords, seg_words, keys_per_seg,
-                       nkeys, sink);
-}
-
-// Streaming-read roofline probe: 16-byte loads of a whole buffer, 4 in flight per lane.
-__global__ __launch_bounds__(256) void k_stream_read(const u32x4 *__restrict__ src, uint64_t n16,
-                                                     uint32_t *__restrict__ sink) {
-    uint32_t acc = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {
-        u32x4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(src + i + u * stride);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc ^= v[u].x ^ v[u].y ^ v[u].z ^ v[u].w;
-    }
-    for (; i < n16; i += stride) {
-        const u32x4 v = src[i];
-        acc ^= v.x ^ v.y ^ v.z ^ v.w;
-    }
-    if (acc == 0x9E3779B9u) sink[0] = acc;
-}
-
-void launch_stream_read(const void *buf, uint64_t bytes, uint32_t *sink, hipStream_t st) {
-    hipLaunchKernelGGL(k_stream_read, dim3(4096), dim3(256), 0, st, (const u32x4 *)buf, bytes / 16, sink);
-}
-
-// Streaming-write roofline probe: 16-byte nontemporal stores over a whole buffer (whole 64-byte
-// write requests, the form the partition passes' runs take).
-__global__ __launch_bounds__(256) void k_stream_write(u32x4 *__restrict__ dst, uint64_t n16, uint32_t seed) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) {
-        const uint32_t x = (uint32_t)i ^ seed;
-        __builtin_nontemporal_store(u32x4{x, x + 1u, x + 2u, x + 3u}, dst + i);
-    }
-}
-
-void launch_stream_write(void *buf, uint64_t bytes, hipStream_t st) {
-    hipLaunchKernelGGL(k_stream_write, dim3(4096), dim3(256), 0, st, (u32x4 *)buf, bytes / 16, 0x9E3779B9u);
-}
-
-// Slice-probe roofline: the bitmap is cut into nbuckets slices of 2^slice_log2 bytes; bucket b's
-// entries (8 bytes: word offset in the slice, payload) are streamed and each tests one word of
-// slice b.  Workgroup w takes the buckets w % 8, w % 8 + 8, ... (blocks b and b + 8 share an XCD
-// under the observed round-robin placement: speed only), so one XCD's workgroups gather inside
-// one slice at a time and the slice can stay in that XCD's L2.
-__global__ __launch_bounds__(256) void k_bench_slice_probe(const u32x2 *__restrict__ ent, uint64_t per_bucket,
-                                                           uint32_t nbuckets, const uint32_t *__restrict__ bm,
-                                                           uint32_t slice_words_log2, uint32_t *__restrict__ sink) {
-    const uint32_t x = blockIdx.x & 7, local = blockIdx.x >> 3, nlocal = gridDim.x >> 3;
-    uint32_t acc = 0;
-    for (uint32_t b = x; b < nbuckets; b += 8) {
-        const u32x2 *e = ent + (uint64_t)b * per_bucket;
-        const uint32_t *slice = bm + ((uint64_t)b << slice_words_log2);
-        const uint64_t step = (uint64_t)nlocal * 256;
-        uint64_t i = (uint64_t)local * 256 + threadIdx.x;
-        for (; i + 3 * step < per_bucket; i += 4 * step) {
-            u32x2 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(e + i + u * step);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc ^= slice[v[u].x & ((1u << slice_words_log2) - 1)] ^ v[u].y;
-        }
-        for (; i < per_bucket; i += step) {
-            const u32x2 v = e[i];
-            acc ^= slice[v.x & ((1u << slice_words_log2) - 1)] ^ v.y;
-        }
-    }
-    if (acc == 0x9E3779B9u) sink[0] = acc;
-}
-
-void launch_bench_slice_probe(const void *ent, uint64_t per_bucket, uint32_t nbuckets, const uint32_t *bm,
-                              uint32_t slice_words_log2, unsigned grid, uint32_t *sink, hipStream_t st) {
-    hipLaunchKernelGGL(k_bench_slice_probe, dim3(grid), dim3(256), 0, st, (const u32x2 *)ent, per_bucket, nbuckets, bm,
-                       slice_words_log2, sink);
-}
-
-void launch_gather_regions(const uint32_t *tbl, uint64_t nwords, uint64_t region_words, uint64_t total_lanes,
-                           uint32_t *sink, hipStream_t st, unsigned grid) {
-    const uint64_t nregions = nwords / region_words;
-    hipLaunchKernelGGL(k_gather_regions, dim3(grid), dim3(256), 0, st, tbl, nregions, region_words,
-                       total_lanes / nregions, sink);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1118,10 +902,10 @@ __global__ __launch_bounds__(256) void k_wide_claim(KeysDev keys, uint64_t m, ui
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < keys.n; i += (uint64_t)gridDim.x * 256) {
         uint64_t h1, h2;
         hash_key<0>(keys, i, h1, h2);
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
         for (uint32_t j = 0; j < k; ++j) {
-            const uint64_t idx = (h & 0x7fffffffffffffffULL) % m;
-            h += (j & 1) ? h1 : h2;
+            const uint64_t idx = BloomSeq::positive(seq.h) % m;
+            seq.advance(j);
             if (idx > kMaxOffset || (bm[idx >> 5] & bit_in_word((uint32_t)idx))) continue;
             const unsigned long long e = (unsigned long long)idx << 32 | i;
             for (uint32_t s = wide_slot(idx, tlog2);; s = (s + 1u) & mask) {
@@ -1147,11 +931,11 @@ __global__ __launch_bounds__(256) void k_wide_resolve(KeysDev keys, uint64_t m, 
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < keys.n; i += (uint64_t)gridDim.x * 256) {
         uint64_t h1, h2;
         hash_key<0>(keys, i, h1, h2);
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
         bool fresh = false, bad = false;
         for (uint32_t j = 0; j < k; ++j) {
-            const uint64_t idx = (h & 0x7fffffffffffffffULL) % m;
-            h += (j & 1) ? h1 : h2;
+            const uint64_t idx = BloomSeq::positive(seq.h) % m;
+            seq.advance(j);
             if (idx > kMaxOffset) {
                 bad = true;
                 continue;
@@ -1185,11 +969,11 @@ __global__ __launch_bounds__(256) void k_wide_contains(KeysDev keys, uint64_t m,
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < keys.n; i += (uint64_t)gridDim.x * 256) {
         uint64_t h1, h2;
         hash_key<0>(keys, i, h1, h2);
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
         bool all = true, bad = false;
         for (uint32_t j = 0; j < k; ++j) {
-            const uint64_t idx = (h & 0x7fffffffffffffffULL) % m;
-            h += (j & 1) ? h1 : h2;
+            const uint64_t idx = BloomSeq::positive(seq.h) % m;
+            seq.advance(j);
             if (idx > kMaxOffset) bad = true;
             else if (!bm || !(bm[idx >> 5] & bit_in_word((uint32_t)idx))) all = false;  // no key: GETBIT reads 0
         }

@@ -1,21 +1,15 @@
 // bucket_common.h -- helpers shared by the region-partitioned Bloom pipelines
-// (contains_partitioned.hip, add_partitioned.hip): key hashing dispatch and the LDS bucket scan.
+// (contains_partitioned.hip, add_partitioned.hip), on top of bloom_common.h: the run stores, the
+// partitioned contains' geometry, the LDS bucket scan and the phase timer.
 #pragma once
 
-#include "rbx_kernels.h"
+#include "bloom_common.h"
 
 namespace rbx {
 
-// Stores of the partition passes' runs.  Experiment builds (-DRBX_RUN_STORES_PLAIN, tools/_ab/)
-// use plain stores instead, which keep the line in the XCD's L2 where partial lines written by
-// different workgroups can merge before write-back.
-template <class T> __device__ __forceinline__ void run_store(T v, T *p) {
-#ifdef RBX_RUN_STORES_PLAIN
-    *p = v;
-#else
-    __builtin_nontemporal_store(v, p);
-#endif
-}
+// Stores of the partition passes' runs: non-temporal (plain stores, which keep the line in the XCD's
+// L2, measured slower: DESIGN.md r02).
+template <class T> __device__ __forceinline__ void run_store(T v, T *p) { __builtin_nontemporal_store(v, p); }
 
 // Partitioned contains, one radix pass (contains_partitioned.hip).  Stage 1 buckets pairs by
 // 2^22-bit (512 KiB) bitmap region, at most 1024 of them; the probe holds one 2^20-bit (128 KiB)
@@ -33,100 +27,15 @@ constexpr uint32_t kBkMaxBuckets = 1u << (32 - kBkBucketBits);                  
 constexpr uint32_t kBkLine = 8;                                                 // pairs per 64-byte line
 constexpr uint32_t kBkMaxGrid1 = 512;                                           // stage-1 blocks (persistent)
 
-// HighwayHash128 of key i (Hash.hash128, M/misc/Hash.java:53-74): 16/32/64-byte fast path or
-// the generic any-length path
-template <int KLEN>
-__device__ __forceinline__ void bk_hash(const KeysDev &keys, uint64_t i, uint64_t &h1, uint64_t &h2) {
-    if constexpr (KLEN > 0) {
-        hh128_fixed<KLEN>(keys.bytes + i * (uint64_t)KLEN, h1, h2);
-    } else {
-        uint64_t a, len;
-        if (keys.offsets) {
-            a = keys.offsets[i];
-            len = keys.offsets[i + 1] - a;
-            a -= keys.off_base;
-        } else {
-            a = i * keys.stride;
-            len = keys.stride;
-        }
-        hh128_bytes(keys.bytes + a, len, h1, h2);
-    }
-}
-
-// exclusive scan of cnt[0..nb) (nb <= 128) by wave 0 into start[] and pos[]
-__device__ __forceinline__ void bk_scan128(const uint32_t *cnt, uint32_t nb, uint32_t *start, uint32_t *pos,
-                                           uint32_t lane = threadIdx.x) {
-    const uint32_t a = 2 * lane < nb ? cnt[2 * lane] : 0u;
-    const uint32_t b = 2 * lane + 1 < nb ? cnt[2 * lane + 1] : 0u;
-    uint32_t x = a + b;
+// exclusive scan of cnt[0..nb) (nb <= 64 * PER, PER consecutive buckets per lane) by wave 0 into
+// start[] and pos[]
+template <int PER>
+__device__ __forceinline__ void bk_scan(const uint32_t *cnt, uint32_t nb, uint32_t *start, uint32_t *pos,
+                                        uint32_t lane = threadIdx.x) {
+    uint32_t v[PER], s = 0;
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if ((int)lane >= off) x += y;
-    }
-    const uint32_t ex = x - a - b;
-    if (2 * lane < nb) start[2 * lane] = pos[2 * lane] = ex;
-    if (2 * lane + 1 < nb) start[2 * lane + 1] = pos[2 * lane + 1] = ex + a;
-}
-
-// exclusive scan of cnt[j] + car[j] (j < nb <= 128) by wave 0: start[j] = the bucket's image
-// offset (its carried entries first), pos[j] = start[j] + car[j] (where its new entries go)
-__device__ __forceinline__ void bk_scan128c(const uint32_t *cnt, const uint32_t *car, uint32_t nb, uint32_t *start,
-                                            uint32_t *pos) {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t ca = 2 * lane < nb ? car[2 * lane] : 0u, cb = 2 * lane + 1 < nb ? car[2 * lane + 1] : 0u;
-    const uint32_t a = (2 * lane < nb ? cnt[2 * lane] : 0u) + ca;
-    const uint32_t b = (2 * lane + 1 < nb ? cnt[2 * lane + 1] : 0u) + cb;
-    uint32_t x = a + b;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if ((int)lane >= off) x += y;
-    }
-    const uint32_t ex = x - a - b;
-    if (2 * lane < nb) {
-        start[2 * lane] = ex;
-        pos[2 * lane] = ex + ca;
-    }
-    if (2 * lane + 1 < nb) {
-        start[2 * lane + 1] = ex + a;
-        pos[2 * lane + 1] = ex + a + cb;
-    }
-}
-
-// bk_scan128c with every bucket's extent rounded up to a multiple of `al` slots (a power of two):
-// bucket starts are then aligned to whole output lines, so the 64-slot windows of a slot-linear
-// store never split a line between two store instructions
-__device__ __forceinline__ void bk_scan128c_al(const uint32_t *cnt, const uint32_t *car, uint32_t nb, uint32_t al,
-                                               uint32_t *start, uint32_t *pos) {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t ca = 2 * lane < nb ? car[2 * lane] : 0u, cb = 2 * lane + 1 < nb ? car[2 * lane + 1] : 0u;
-    const uint32_t a = ((2 * lane < nb ? cnt[2 * lane] : 0u) + ca + al - 1) & ~(al - 1);
-    const uint32_t b = ((2 * lane + 1 < nb ? cnt[2 * lane + 1] : 0u) + cb + al - 1) & ~(al - 1);
-    uint32_t x = a + b;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if ((int)lane >= off) x += y;
-    }
-    const uint32_t ex = x - a - b;
-    if (2 * lane < nb) {
-        start[2 * lane] = ex;
-        pos[2 * lane] = ex + ca;
-    }
-    if (2 * lane + 1 < nb) {
-        start[2 * lane + 1] = ex + a;
-        pos[2 * lane + 1] = ex + a + cb;
-    }
-}
-
-// the same for nb <= 256 (four buckets per lane)
-__device__ __forceinline__ void bk_scan256(const uint32_t *cnt, uint32_t nb, uint32_t *start, uint32_t *pos) {
-    const uint32_t lane = threadIdx.x;
-    uint32_t v[4], s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[j] = 4 * lane + j < nb ? cnt[4 * lane + j] : 0u;
+    for (int j = 0; j < PER; ++j) {
+        v[j] = PER * lane + j < nb ? cnt[PER * lane + j] : 0u;
         s += v[j];
     }
     uint32_t x = s;
@@ -137,8 +46,8 @@ __device__ __forceinline__ void bk_scan256(const uint32_t *cnt, uint32_t nb, uin
     }
     uint32_t ex = x - s;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (4 * lane + j < nb) start[4 * lane + j] = pos[4 * lane + j] = ex;
+    for (int j = 0; j < PER; ++j) {
+        if (PER * lane + j < nb) start[PER * lane + j] = pos[PER * lane + j] = ex;
         ex += v[j];
     }
 }

@@ -41,20 +41,6 @@ __device__ __forceinline__ void bk_direct(unsigned long long e, const uint32_t *
     if ((bm[idx >> 5] & bit_in_word(idx)) == 0u) atomicOr(&miss[key >> 6], 1ULL << (key & 63));
 }
 
-// Segment (bucket b, stage-1 block blk) of G blocks and nb buckets starts at pair
-// b * bk_seg_stride_b + blk * bk_seg_stride_blk.  Block-major: a block's nb segments are adjacent,
-// so its line stores stay inside nb * capS pairs (C2: 11 MB) and the probe reads a region's segments
-// at that stride; bucket-major (RBX_BK_BLOCK_MAJOR=0, a region's segments adjacent) measured slower.
-#ifndef RBX_BK_BLOCK_MAJOR
-#define RBX_BK_BLOCK_MAJOR 1
-#endif
-__host__ __device__ __forceinline__ uint64_t bk_seg_stride_b(uint32_t G, uint32_t nb, uint64_t capS) {
-    return RBX_BK_BLOCK_MAJOR ? capS : (uint64_t)G * capS;
-}
-__host__ __device__ __forceinline__ uint64_t bk_seg_stride_blk(uint32_t G, uint32_t nb, uint64_t capS) {
-    return RBX_BK_BLOCK_MAJOR ? (uint64_t)nb * capS : capS;
-}
-
 // K1 -----------------------------------------------------------------------------------
 // Tile = NT * PER keys; a persistent grid of G <= 512 blocks strides over the tiles.  Hash, test
 // bit 0 (one random gather per key), then each of the survivors' k-1 remaining bits takes a slot
@@ -65,7 +51,6 @@ __host__ __device__ __forceinline__ uint64_t bk_seg_stride_blk(uint32_t G, uint3
 // A partial line costs a full write request, and this way only a block's last line per bucket is
 // partial.  Block blk owns segment (b, blk) of every bucket b, so nothing is reserved globally and
 // every block writes its nb counts at its end (segcnt needs no clearing).
-template <int KMAX> constexpr int bk_per() { return KMAX <= 8 ? RBX_BK_PER8 : 1; }
 constexpr uint32_t kBkNoSlot = 0xffffffffu;
 
 template <int KLEN, int KMAX, int NT, int PER>
@@ -87,8 +72,12 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
     __shared__ uint32_t s_nlist[2];
     const uint64_t ntiles = (nchunk + TILE - 1) / TILE;
     const uint32_t lane = threadIdx.x & 63, lane8 = threadIdx.x & (kBkLine - 1);
-    const uint64_t gstride = bk_seg_stride_b(gridDim.x, nb, capS);
-    unsigned long long *seg0 = pairs + blockIdx.x * bk_seg_stride_blk(gridDim.x, nb, capS);
+    // Segment (bucket b, stage-1 block blk) of nb buckets starts at pair (blk * nb + b) * capS.
+    // Block-major: a block's nb segments are adjacent, so its line stores stay inside nb * capS pairs
+    // (C2: 11 MB) and the probe reads a region's segments at that stride (bucket-major, a region's
+    // segments adjacent, measured slower: DESIGN.md §3.6 r07).
+    const uint32_t G = gridDim.x;
+    unsigned long long *seg0 = pairs + blockIdx.x * ((uint64_t)nb * capS);
     for (uint32_t b = threadIdx.x; b < nb; b += NT) s_fill[b] = s_out[b] = 0;
     if (threadIdx.x < 2) s_nlist[threadIdx.x] = 0;
     uint32_t cur = 0;  // the list the pairs' slots are filling
@@ -102,7 +91,7 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
         for (int q = 0; q < PER; ++q) {
             const uint64_t t = tt0 + q * NT;
             h1[q] = h2[q] = 0;
-            if (t < nchunk) bk_hash<KLEN>(keys, base + t, h1[q], h2[q]);
+            if (t < nchunk) hash_key<KLEN>(keys, base + t, h1[q], h2[q]);
         }
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
             w[q] = 0;
             m[q] = 0;
             if (t < nchunk) {
-                const uint32_t idx = mod63(h1[q] & 0x7fffffffffffffffULL, mp);
+                const uint32_t idx = BloomSeq::index_of(h1[q], mp);
                 m[q] = bit_in_word(idx);
                 // diagnostics (flags 32, wrong answers): no bit-0 gather; ~54% of keys survive
                 if (flags & 32) w[q] = (uint32_t)(h2[q] >> 40) % 100u < 54u ? m[q] : 0u;
@@ -120,7 +109,7 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
     };
     if ((uint64_t)blockIdx.x < ntiles) hash_tile(blockIdx.x);
     __syncthreads();
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += G) {
         const uint64_t t0 = tile * TILE + threadIdx.x;
         uint32_t idx[NP], slot[NP];  // slot: kBkNoSlot = no pair, or the pair is in its line buffer
 #pragma unroll
@@ -129,14 +118,15 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
             const bool surv = (w[q] & m[q]) != 0u;
             const uint64_t mask = __ballot(surv);
             if (lane == 0 && t < nchunk) alive[t >> 6] = mask;  // t is 64-aligned for lane 0
-            uint64_t h = h1[q] + h2[q];
+            BloomSeq seq(h1[q], h2[q]);
+            seq.advance(0);
 #pragma unroll
             for (int j = 1; j < KMAX; ++j) {
                 const int p = q * (KMAX - 1) + j - 1;
                 slot[p] = kBkNoSlot;
                 idx[p] = 0;
                 if (surv && !(flags & 4) && (uint32_t)j < k) {
-                    idx[p] = mod63(h & 0x7fffffffffffffffULL, mp);
+                    idx[p] = seq.index(mp);
                     const uint32_t b = idx[p] >> kBkBucketBits;
                     const uint32_t s = atomicAdd(&s_fill[b], 1u);
                     if (s < kBkLine) s_buf[b * kBkLine + s] = w2((uint32_t)t, idx[p]);
@@ -144,10 +134,10 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
                     // fill was below a line at the tile's start: one pair per bucket and tile gets this slot
                     if (s == kBkLine - 1) s_list[cur][atomicAdd(&s_nlist[cur], 1u)] = (uint16_t)b;
                 }
-                h += (j & 1) ? h1[q] : h2[q];
+                seq.advance(j);
             }
         }
-        if (tile + gridDim.x < ntiles) hash_tile(tile + gridDim.x);  // the next tile (see above)
+        if (tile + G < ntiles) hash_tile(tile + G);  // the next tile (see above)
         __syncthreads();
         for (;;) {
             // store the listed buckets' full lines: eight lanes per bucket, a wave instruction stores
@@ -159,7 +149,7 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
                 const uint32_t fill = s_fill[b], out = s_out[b];  // fill >= kBkLine
                 const unsigned long long e = s_buf[b * kBkLine + lane8];
                 const bool fits = (uint64_t)out + kBkLine <= capS;
-                if (fits) run_store(e, seg0 + b * gstride + out + lane8);
+                if (fits) run_store(e, seg0 + b * capS + out + lane8);
                 else bk_direct(e, bm, miss);
                 if (lane8 == 0) {  // the eight lanes of a bucket are in one wave: their reads came first
                     s_fill[b] = fill - kBkLine;
@@ -201,10 +191,10 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
         const bool fits = (uint64_t)out + kBkLine <= capS;
         if (lane8 < fill) {
             const unsigned long long e = s_buf[b * kBkLine + lane8];
-            if (fits) run_store(e, seg0 + b * gstride + out + lane8);
+            if (fits) run_store(e, seg0 + b * capS + out + lane8);
             else bk_direct(e, bm, miss);
         }
-        if (lane8 == 0) segcnt[(uint64_t)b * gridDim.x + blockIdx.x] = out + (fits ? fill : 0u);
+        if (lane8 == 0) segcnt[(uint64_t)b * G + blockIdx.x] = out + (fits ? fill : 0u);
     }
 }
 
@@ -289,8 +279,8 @@ __global__ __launch_bounds__(1024) void k_bk_probe(const unsigned long long *__r
         uint32_t cntv = 0;
         if (lane < nsw) cntv = (uint32_t)min<uint64_t>(rcnt[wave + NW * lane], capS);
         // capS is a multiple of 8 pairs: every segment is 64-byte aligned
-        const unsigned long long *rseg = pairs + r * bk_seg_stride_b(G, nb, capS);
-        auto seg = [&](uint32_t i) { return (const u32x4 *)(rseg + (wave + NW * i) * bk_seg_stride_blk(G, nb, capS)); };
+        const unsigned long long *rseg = pairs + r * capS;
+        auto seg = [&](uint32_t i) { return (const u32x4 *)(rseg + (wave + NW * i) * ((uint64_t)nb * capS)); };
         auto load = [&](u32x4 (&v)[U], const u32x4 *src, uint32_t n, uint32_t q0) {
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) {
@@ -338,7 +328,7 @@ __global__ __launch_bounds__(1024) void k_bk_probe(const unsigned long long *__r
             __syncthreads();
             for (uint32_t i = threadIdx.x; i < nm; i += NT) atomicAdd(&s_mc[s_mrec[i] >> kBkMissRangeBits], 1u);
             __syncthreads();
-            if (threadIdx.x < 64) bk_scan256(s_mc, nmranges, s_mst, s_mpos);
+            if (threadIdx.x < 64) bk_scan<4>(s_mc, nmranges, s_mst, s_mpos);
             else if (threadIdx.x >= 256 && threadIdx.x - 256 < nmranges) {
                 const uint32_t q = threadIdx.x - 256;
                 s_mgb[q] = s_mc[q] ? atomicAdd(&mcnt[q], s_mc[q]) : 0u;
@@ -435,14 +425,21 @@ __global__ __launch_bounds__(256) void k_bk_final(const unsigned long long *__re
     }
 }
 
+// k_bk_final's blocks: each adds its count to ONE counter, and same-address atomics serialise at the
+// kernel's end, so 512 blocks (grid-stride) rather than 2048 (r05, cf. k_stream_final8)
+static unsigned grid_for_pc(uint64_t n) {
+    uint64_t g = ((n + 63) / 64 + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : (g > 512 ? 512 : g));
+}
+
 // launcher -------------------------------------------------------------------------------
-// Shapes: stage 1 at 512 threads with bk_per<KMAX>() keys per thread (512-key tiles, bk_tile_keys;
-// 1024-key tiles at k <= 8 measured slower), 78 KiB of LDS, two blocks per CU; the probe at 1024
+// Shapes: stage 1 at 512 threads with one key per thread (512-key tiles, kBkTileKeys; 1024-key
+// tiles at k <= 8 measured slower), 78 KiB of LDS, two blocks per CU; the probe at 1024
 // threads, one workgroup per CU (a 128 KiB slice + the miss buffers), in whole groups of 8 clusters.
 // The A/Bs (tile size, cluster of 8, segment layout) are in DESIGN.md §3.6 r07.
 template <int KLEN, int KMAX>
 static void bk_chunk(const PcArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL((k_bk_stage1<KLEN, KMAX, 512, bk_per<KMAX>()>), dim3(a.grid1), dim3(512), 0, st, a.keys, a.base,
+    hipLaunchKernelGGL((k_bk_stage1<KLEN, KMAX, 512, 1>), dim3(a.grid1), dim3(512), 0, st, a.keys, a.base,
                        a.nchunk, a.bm, a.mp, a.k, a.nb, a.capS, a.pairs, a.segcnt, a.alive, a.miss, a.flags);
     constexpr uint32_t kGroup = 8 * kBkCS, kMaxProbe = kBkCS == 4 ? 256 : 512;
     const uint32_t gp = std::max(kGroup, std::min(a.nb * kBkCS, kMaxProbe) / kGroup * kGroup);
@@ -457,19 +454,10 @@ static void bk_chunk(const PcArgs &a, hipStream_t st) {
                        a.out, a.count);
 }
 
-template <int KLEN>
-static void bk_chunk_len(const PcArgs &a, hipStream_t st) {
-    if (a.k <= 8) bk_chunk<KLEN, 8>(a, st);
-    else bk_chunk<KLEN, 16>(a, st);
-}
-
 void launch_contains_partitioned_chunk(const PcArgs &a, int klen_fast, hipStream_t st) {
-    switch (klen_fast) {
-    case 16: bk_chunk_len<16>(a, st); break;
-    case 32: bk_chunk_len<32>(a, st); break;
-    case 64: bk_chunk_len<64>(a, st); break;
-    default: bk_chunk_len<0>(a, st); break;
-    }
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<16, 16>(a.k, [&](auto kmax) { bk_chunk<decltype(klen)::value, decltype(kmax)::value>(a, st); });
+    });
 }
 
 }  // namespace rbx

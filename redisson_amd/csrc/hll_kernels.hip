@@ -99,13 +99,10 @@ void launch_hll_pfadd(const KeysDev &elems, int elen_fast, const HllSeg *d_tiles
                       uint32_t *d_changed, hipStream_t st) {
     if (!ntiles) return;
     const size_t lds = kHllRegs * sizeof(uint32_t);
-    switch (elen_fast) {
-    case 16: hipLaunchKernelGGL(k_hll_pfadd<16>, dim3(ntiles), dim3(kPfaddThreads), lds, st, elems, d_tiles, d_changed); break;
-    case 32: hipLaunchKernelGGL(k_hll_pfadd<32>, dim3(ntiles), dim3(kPfaddThreads), lds, st, elems, d_tiles, d_changed); break;
-    case 64: hipLaunchKernelGGL(k_hll_pfadd<64>, dim3(ntiles), dim3(kPfaddThreads), lds, st, elems, d_tiles, d_changed); break;
-    case 8: hipLaunchKernelGGL(k_hll_pfadd<8>, dim3(ntiles), dim3(kPfaddThreads), lds, st, elems, d_tiles, d_changed); break;
-    default: hipLaunchKernelGGL(k_hll_pfadd<0>, dim3(ntiles), dim3(kPfaddThreads), lds, st, elems, d_tiles, d_changed); break;
-    }
+    with_klen<true>(elen_fast, [&](auto elen) {
+        hipLaunchKernelGGL(k_hll_pfadd<decltype(elen)::value>, dim3(ntiles), dim3(kPfaddThreads), lds, st, elems, d_tiles,
+                           d_changed);
+    });
 }
 
 // ---------------------------------------------------------------------------------
@@ -660,13 +657,9 @@ void launch_hll_sparse_replay(const KeysDev &elems, int elen_fast, const HllRepl
                               uint64_t max_bytes, hipStream_t st) {
     if (!n) return;
     const dim3 grid(std::min<uint32_t>(n, 7 * 256));  // seven 21 KiB blocks per CU, all resident
-    switch (elen_fast) {
-    case 16: hipLaunchKernelGGL(k_hll_sparse_replay<16>, grid, dim3(256), 0, st, elems, items, n, max_bytes); break;
-    case 32: hipLaunchKernelGGL(k_hll_sparse_replay<32>, grid, dim3(256), 0, st, elems, items, n, max_bytes); break;
-    case 64: hipLaunchKernelGGL(k_hll_sparse_replay<64>, grid, dim3(256), 0, st, elems, items, n, max_bytes); break;
-    case 8: hipLaunchKernelGGL(k_hll_sparse_replay<8>, grid, dim3(256), 0, st, elems, items, n, max_bytes); break;
-    default: hipLaunchKernelGGL(k_hll_sparse_replay<0>, grid, dim3(256), 0, st, elems, items, n, max_bytes); break;
-    }
+    with_klen<true>(elen_fast, [&](auto elen) {
+        hipLaunchKernelGGL(k_hll_sparse_replay<decltype(elen)::value>, grid, dim3(256), 0, st, elems, items, n, max_bytes);
+    });
 }
 
 // recycled pool slots zeroed in one launch (registers + state words), one block per slot

@@ -656,6 +656,19 @@ uint64_t rbx_selftest_mod(uint64_t n, uint64_t seed) {
     return bad;
 }
 
+// The index sequence every Bloom kernel walks (BloomSeq), on both of its modulus forms.
+uint32_t rbx_selftest_bloom_indexes(uint64_t h1, uint64_t h2, uint32_t k, uint64_t size, uint32_t *out) {
+    const ModParams mp = make_mod_params(size);
+    const ModC mc = mod_compact(mp);
+    BloomSeq a(h1, h2), b(h1, h2);
+    uint32_t bad = 0;
+    for (uint32_t j = 0; j < k; ++j) {
+        out[j] = a.next(j, mp);
+        bad += b.next(j, mc) != out[j];
+    }
+    return bad;
+}
+
 // HighwayHash128 / MurmurHash64A of the host-compiled device code (CPU cross-check).
 void rbx_selftest_hash128(const uint8_t *data, uint64_t len, uint64_t out[2]) {
     HH s;

@@ -7,7 +7,7 @@
 // M/ = /root/reference/redisson/src/main/java/org/redisson/
 //
 // Everything here is __host__ __device__ where it can be, so the same code is
-// exercised on the CPU by tests/test_fastmod.py (via rbx_selftest in librbx.so).
+// exercised on the CPU by tests/test_abi.py (via the rbx_selftest_* exports of librbx.so).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,6 +86,33 @@ RBX_HD uint32_t mod63c(uint64_t h, const ModC &p) {
     r = div21_rem(r, (uint32_t)mid, p.dn, p.v);
     return r >> s;
 }
+
+// The Bloom index sequence of RedissonBloomFilter.hash() (M/RedissonBloomFilter.java:139-151), the
+// one place that must match it bit for bit:
+//   hash = h1;  for j in [0, k): index_j = (hash & Long.MAX_VALUE) % size;  hash += j odd ? h1 : h2
+// A cursor holds hash j; index() reads index_j, advance(j) steps to hash j + 1, next() does both.
+// h1 and h2 are the caller's words, by reference (a cursor lives inside the scope that hashed the key):
+// copies of them, and a step that takes them by value, reorder the kernels' code.  Kernels that keep
+// the state in registers of their own (the slot kernels) use index_of / step.
+struct BloomSeq {
+    uint64_t h;
+    const uint64_t &h1, &h2;
+    RBX_HD BloomSeq(const uint64_t &h1_, const uint64_t &h2_) : h(h1_), h1(h1_), h2(h2_) {}
+    BloomSeq(uint64_t &&, uint64_t &&) = delete;  // a temporary would dangle
+    BloomSeq(uint64_t &&, const uint64_t &) = delete;
+    BloomSeq(const uint64_t &, uint64_t &&) = delete;
+    static RBX_HD uint64_t positive(uint64_t h) { return h & 0x7fffffffffffffffULL; }
+    static RBX_HD uint32_t index_of(uint64_t h, const ModParams &mp) { return mod63(positive(h), mp); }
+    static RBX_HD uint32_t index_of(uint64_t h, const ModC &mc) { return mod63c(positive(h), mc); }
+    static RBX_HD const uint64_t &step(uint32_t j, const uint64_t &h1, const uint64_t &h2) { return (j & 1) ? h1 : h2; }
+    template <class MP> RBX_HD uint32_t index(const MP &mp) const { return index_of(h, mp); }
+    RBX_HD void advance(uint32_t j) { h += step(j, h1, h2); }
+    template <class MP> RBX_HD uint32_t next(uint32_t j, const MP &mp) {
+        const uint32_t idx = index(mp);
+        advance(j);
+        return idx;
+    }
+};
 
 // ---------------------------------------------------------------------------------
 // HighwayHash (portable form), Redisson flavour.  State lives in 32 VGPRs.

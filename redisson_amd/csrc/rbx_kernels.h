@@ -1,8 +1,11 @@
-// rbx_kernels.h -- shared device structs and kernel launchers (host <-> .hip files).
+// rbx_kernels.h -- shared device structs and kernel launchers (host <-> .hip files): the shared types
+// first, then one section per .hip file with its argument structs, its launchers and its set_* knobs.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "rbx_device.h"
 
@@ -18,7 +21,28 @@ constexpr unsigned kMaxGrid = 2048;  // grid-stride cap: 256 CUs x 8 blocks of 2
 #ifndef RBX_DIAG
 #define RBX_DIAG 0
 #endif
-constexpr bool kDiag = RBX_DIAG != 0;  // grid-stride cap: 256 CUs x 8 blocks of 256 threads
+constexpr bool kDiag = RBX_DIAG != 0;  // true only in the -DRBX_DIAG=1 profiling build
+
+// Launcher dispatch from the runtime key length to the kernels' KLEN template argument:
+// f(std::integral_constant<int, L>{}) with L = 16 / 32 / 64 for the fixed-length fast paths (and 8 with
+// WITH8: the HyperLogLog elements), 0 for the any-length path.
+template <bool WITH8 = false, class F> inline void with_klen(int klen_fast, F &&f) {
+    if constexpr (WITH8)
+        if (klen_fast == 8) return f(std::integral_constant<int, 8>{});
+    if (klen_fast == 16) return f(std::integral_constant<int, 16>{});
+    if (klen_fast == 32) return f(std::integral_constant<int, 32>{});
+    if (klen_fast == 64) return f(std::integral_constant<int, 64>{});
+    return f(std::integral_constant<int, 0>{});
+}
+// ... and from k to KMAX, the unrolled loops' bound: the smallest of 8 / 16 / 32 that holds k, up to
+// TOP (16 or 32).  A k past TOP gets REST: 0, the any-k kernels, or TOP itself where the host bounds k.
+template <int TOP, int REST = 0, class F> inline void with_kmax(uint32_t k, F &&f) {
+    static_assert((TOP == 16 || TOP == 32) && (REST == 0 || REST == TOP), "ladder 8 / 16 [/ 32] / rest");
+    if (k <= 8) return f(std::integral_constant<int, 8>{});
+    if (k <= 16) return f(std::integral_constant<int, 16>{});
+    if (TOP == 32 && k <= 32) return f(std::integral_constant<int, TOP>{});
+    return f(std::integral_constant<int, REST>{});
+}
 
 struct KeysDev {
     const uint8_t *bytes;
@@ -53,6 +77,8 @@ struct alignas(16) HTEntry {
     unsigned long long idw;  // [63:32] 254 - epoch, [31:0] min key id
 };
 
+// ---- bloom_kernels.hip
+// Contains, the table adds, the one-key kernels, the wide filters, BITCOUNT and the digest.
 struct AddChunkArgs {
     KeysDev keys;
     uint64_t base, nchunk;
@@ -71,13 +97,38 @@ struct AddChunkArgs {
     bool narrow;  // single filter, k <= 32: 8-byte entries, table cleared per chunk
 };
 
-// partitioned contains (contains_partitioned.hip): one chunk of keys against one filter
-constexpr int kBkRegionBits = 19;  // 2^19 bits = 64 KiB bitmap region = one LDS image
-#ifndef RBX_BA_SUB
-#define RBX_BA_SUB 8
-#endif
-constexpr uint32_t kBaSub = RBX_BA_SUB;  // the partitioned add's stage-1 sub-partitions per level-1 bucket
-constexpr int kBkMissRangeBits = 19;  // probe misses are bucketed by 2^19-key range (64 KiB LDS bitmap)
+void launch_bloom_contains(const KeysDev &keys, int klen_fast, const uint32_t *bm, const ModParams &mp,
+                           uint32_t k, uint8_t *out, unsigned long long *count, hipStream_t st);
+// add(T) / contains(T): one key of one filter (k <= 16), one lane; an add needs no first-setter table
+// (run_add, keys.n == 1).  done (nullable): seq is stored there last, at system scope (bloom_host_tiny)
+void launch_bloom_one(bool add, const KeysDev &keys, int klen_fast, const FilterDesc &f, uint8_t *out,
+                      unsigned long long *count, uint32_t *done, uint32_t seq, hipStream_t st);
+// one store of seq into done (coherent host memory), after the stream's earlier work
+void launch_done_word(uint32_t *done, uint32_t seq, hipStream_t st);
+// tile_seg0[t] = segment holding key 256*t (precomputed once per multi-tenant batch)
+void launch_tile_seg0(const uint64_t *seg_off, uint32_t nseg, uint64_t nkeys, uint32_t *tile_seg0, hipStream_t st);
+void launch_bloom_contains_multi(const KeysDev &keys, int klen_fast, const FilterDesc *filt,
+                                 const uint64_t *seg_off, uint32_t nseg, const uint32_t *tile_seg0, uint32_t kmax,
+                                 uint8_t *out, unsigned long long *counts, hipStream_t st, bool slots);
+void launch_bloom_add_chunk(const AddChunkArgs &a, int klen_fast, hipStream_t st);
+// |size| > 2^32 filters (k_wide_*): add = first-setter claim + resolve over a 2^tlog2-entry table
+// (all ~0 on entry); *oob = 1 when an index passes the Redis offset limit.  bm may be NULL for
+// contains (a missing key).
+void launch_bloom_wide(const KeysDev &keys, uint64_t m, uint32_t k, uint32_t *bm, unsigned long long *len,
+                       unsigned long long *table, uint32_t tlog2, bool is_add, uint8_t *out,
+                       unsigned long long *count, unsigned long long *oob, hipStream_t st);
+void launch_bitcount(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st);
+// order-independent digest of a Redis string's bytes (replica comparison); *out += digest
+void launch_digest(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st);
+void set_contains_stage1(int v);  // early-exit schedule of the staged contains; 5 = the slot kernel
+int get_contains_stage1();
+void set_contains_qgrid(int v);   // slot contains kernel grid (blocks)
+
+// ---- contains_partitioned.hip
+// One chunk of keys against one filter, one radix pass.  Stage 1 buckets pairs by 2^22-bit (512 KiB)
+// bitmap region; the probe holds one 2^20-bit (128 KiB) slice of a region in LDS (bucket_common.h).
+constexpr uint32_t kBkTileKeys = 512;  // keys per stage-1 tile: 512 threads, one key each
+constexpr int kBkMissRangeBits = 19;   // probe misses are bucketed by 2^19-key range (64 KiB LDS bitmap)
 struct PcArgs {
     KeysDev keys;
     uint64_t base, nchunk;
@@ -101,25 +152,14 @@ struct PcArgs {
     uint32_t flags;  // diagnostics only (rbx_tune "contains_partition_flags"); 0 in normal operation
     unsigned long long *stamps;  // flags & 64: probe phase times (rbx_bench_add_stamps), else null
 };
-// keys per stage-1 tile: 512 threads, one key each (RBX_BK_PER8=2, two keys each at k <= 8: an A/B build)
-#ifndef RBX_BK_PER8
-#define RBX_BK_PER8 1
-#endif
-inline uint32_t bk_tile_keys(uint32_t k) { return k <= 8 ? 512u * RBX_BK_PER8 : 512u; }
-// k_bk_final's blocks: each adds its count to ONE counter, and same-address atomics serialise at the
-// kernel's end, so 512 blocks (grid-stride) rather than 2048 (r05, cf. k_stream_final8)
-inline unsigned grid_for_pc(uint64_t n) {
-    uint64_t g = ((n + 63) / 64 + 255) / 256;
-    return (unsigned)(g < 1 ? 1 : (g > 512 ? 512 : g));
-}
 void launch_contains_partitioned_chunk(const PcArgs &a, int klen_fast, hipStream_t st);
-void set_add_region_grid(int v);  // 256..65536 (default 2048)
-void set_add_rec_lds_limit(int v);  // 0..7168 (tests)
 
-// partitioned single-filter add (add_partitioned.hip): one chunk of keys
-// Partitioned add: 2^16-bit regions (8 KiB bitmap + two bitsets + a collision table = 32 KiB
-// of LDS, two blocks per CU); at most 8 pairs per thread of the 1024-thread region block.
+// ---- add_partitioned.hip
+// The partitioned single-filter add, one chunk of keys.  2^16-bit regions (8 KiB bitmap + two bitsets
+// + a collision table = 32 KiB of LDS, two blocks per CU); at most 8 pairs per thread of the
+// 1024-thread region block.
 constexpr int kBaRegionBits = 16;
+constexpr uint32_t kBaSub = 8;               // stage-1 sub-partitions per level-1 bucket
 constexpr uint32_t kBaMaxRegionPairs = 8192;  // cap3 <= this
 constexpr int kBaKeyRangeBits = 20;           // owner records are bucketed by 2^20-key range
 struct BaArgs {
@@ -148,8 +188,12 @@ struct BaArgs {
     unsigned long long *stamps;   // diagnostics only (add_partition_diag & 64): region-pass phase times, else null
 };
 void launch_add_partitioned_chunk(const BaArgs &a, int klen_fast, hipStream_t st);
+void set_add_region_grid(int v);    // 256..65536 (default 2048)
+void set_add_rec_lds_limit(int v);  // 0..7168 (tests)
 
-// ordered mixed contains/add stream (one chunk of keys)
+// ---- stream_kernels.hip
+// The ordered mixed contains/add stream and the multi-tenant add on the 8-byte table (one chunk of keys
+// each).
 struct StreamChunkArgs {
     KeysDev keys;
     uint64_t base, nchunk;
@@ -175,12 +219,23 @@ struct StreamChunkArgs {
     uint32_t *const *fid_bm;      // bitmap words per table id (fid)
     uint32_t *fslot;              // per add-list entry: the table slot of its first zero bit's claim (r05)
 };
+// entries of the 8-byte stream table for a chunk of nadds adds (load <= 8/9 even if every bit is 0)
+__host__ __device__ inline uint32_t t8_log2(uint32_t nadds, uint32_t kmax) {
+    const uint64_t need = (uint64_t)nadds * kmax;
+    const uint64_t want = need + need / 8;
+    uint32_t lg = 12;
+    while ((1ULL << lg) < want) ++lg;
+    return lg;
+}
+
+void launch_stream_chunk(const StreamChunkArgs &a, int klen_fast, hipStream_t st);
+
 // state of the optimistic multi-tenant add's conflict table (k_maddx_*), reset per chunk
 struct MaddxState {
     uint32_t count;     // entries inserted into C
     uint32_t overflow;  // C too full (or a probe run too long): the full table T decides the chunk
 };
-// One chunk of a multi-tenant add on the 8-byte first-setter table (r05, bloom_kernels.hip k_madd_*):
+// One chunk of a multi-tenant add on the 8-byte first-setter table (r05, k_maddx_*):
 // probe (claims) -> final (replies, per-segment counts) -> walk (OR owned bits, empty the table).
 struct MaddChunkArgs {
     KeysDev keys;
@@ -207,9 +262,14 @@ struct MaddChunkArgs {
     uint64_t segmax;
 };
 void launch_madd8_chunk(const MaddChunkArgs &a, int klen_fast, hipStream_t st);
-// per-segment multi-tenant add (segment_add.hip k_madd_seg): one 256-thread workgroup per segment, every
-// filter of the batch in one segment only (disjoint bitmaps), k <= 16; segments past segmax (<= kSegMaxKeys)
-// keys set *big and are left to the k_maddx_* chunks
+void set_stream_diag(int v);        // profiling build only (kDiag): bits 1 | 8, see stream_kernels.hip
+void set_stream_final_grid(int v);  // k_stream_final8 blocks (32..2048)
+void set_stream_qgrid(int v);       // slot stream-contains kernel grid (blocks)
+
+// ---- segment_add.hip
+// The per-segment multi-tenant add (k_madd_seg): one 256-thread workgroup per segment, every filter of
+// the batch in one segment only (disjoint bitmaps), k <= 16; segments past segmax (<= kSegMaxKeys) keys
+// set *big and are left to the k_maddx_* chunks.
 constexpr uint32_t kSegMaxKeys = 16384;
 struct MaddSegArgs {
     KeysDev keys;
@@ -226,39 +286,9 @@ struct MaddSegArgs {
     FilterDesc single;
 };
 void launch_madd_seg(const MaddSegArgs &a, int klen_fast, hipStream_t st);
-// entries of the 8-byte stream table for a chunk of nadds adds (load <= 8/9 even if every bit is 0)
-__host__ __device__ inline uint32_t t8_log2(uint32_t nadds, uint32_t kmax) {
-    const uint64_t need = (uint64_t)nadds * kmax;
-    const uint64_t want = need + need / 8;
-    uint32_t lg = 12;
-    while ((1ULL << lg) < want) ++lg;
-    return lg;
-}
 
-// bloom_kernels.hip
-void launch_stream_chunk(const StreamChunkArgs &a, int klen_fast, hipStream_t st);
-void launch_bloom_contains(const KeysDev &keys, int klen_fast, const uint32_t *bm, const ModParams &mp,
-                           uint32_t k, uint8_t *out, unsigned long long *count, hipStream_t st);
-// add(T) / contains(T): one key of one filter (k <= 16), one lane; an add needs no first-setter table
-// (run_add, keys.n == 1).  done (nullable): seq is stored there last, at system scope (bloom_host_tiny)
-void launch_bloom_one(bool add, const KeysDev &keys, int klen_fast, const FilterDesc &f, uint8_t *out,
-                      unsigned long long *count, uint32_t *done, uint32_t seq, hipStream_t st);
-// one store of seq into done (coherent host memory), after the stream's earlier work
-void launch_done_word(uint32_t *done, uint32_t seq, hipStream_t st);
-// tile_seg0[t] = segment holding key 256*t (precomputed once per multi-tenant batch)
-void launch_tile_seg0(const uint64_t *seg_off, uint32_t nseg, uint64_t nkeys, uint32_t *tile_seg0, hipStream_t st);
-void launch_bloom_contains_multi(const KeysDev &keys, int klen_fast, const FilterDesc *filt,
-                                 const uint64_t *seg_off, uint32_t nseg, const uint32_t *tile_seg0, uint32_t kmax,
-                                 uint8_t *out, unsigned long long *counts, hipStream_t st, bool slots);
-void launch_bloom_add_chunk(const AddChunkArgs &a, int klen_fast, hipStream_t st);
-// |size| > 2^32 filters (k_wide_*): add = first-setter claim + resolve over a 2^tlog2-entry table
-// (all ~0 on entry); *oob = 1 when an index passes the Redis offset limit.  bm may be NULL for
-// contains (a missing key).
-void launch_bloom_wide(const KeysDev &keys, uint64_t m, uint32_t k, uint32_t *bm, unsigned long long *len,
-                       unsigned long long *table, uint32_t tlog2, bool is_add, uint8_t *out,
-                       unsigned long long *count, unsigned long long *oob, hipStream_t st);
-void launch_bitcount(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st);
-// bitset_kernels.hip -- RBitSet over bitmap strings
+// ---- bitset_kernels.hip
+// RBitSet over bitmap strings.
 struct BitopSrc {
     const uint8_t *bytes;  // a source string (null when the key is missing)
     uint64_t len;          // its Redis length: nothing at or past it is read
@@ -306,8 +336,9 @@ void launch_fields_serial(uint32_t *words, unsigned long long *len, uint64_t cap
 // one SET / INCRBY; *d_reply = its reply
 void launch_field_one(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
                       uint64_t offset, int64_t value, int64_t *d_reply, uint64_t new_len, hipStream_t st);
-// order-independent digest of a Redis string's bytes (replica comparison); *out += digest
-void launch_digest(const uint8_t *bytes, uint64_t nbytes, unsigned long long *out, hipStream_t st);
+
+// ---- bench_kernels.hip
+// Roofline probes (api_bench.cpp only).
 // region-local gathers: 6 loads per lane inside XCD-assigned regions (partitioned-probe roofline)
 void launch_gather_regions(const uint32_t *tbl, uint64_t nwords, uint64_t region_words, uint64_t total_lanes,
                            uint32_t *sink, hipStream_t st, unsigned grid);
@@ -325,14 +356,7 @@ void launch_stream_write(void *buf, uint64_t bytes, hipStream_t st);
 void launch_gather_probe(const uint32_t *tbl, uint64_t nwords, uint64_t nkeys, uint32_t k, uint32_t *sink,
                          hipStream_t st);
 
-void set_contains_stage1(int v);
-void set_contains_qgrid(int v);
-void set_stream_diag(int v);           // profiling build only (kDiag): bits 1 | 8, see stream_kernels.hip
-void set_stream_final_grid(int v);  // k_stream_final8 blocks (32..2048)
-void set_stream_qgrid(int v);  // slot stream-contains kernel grid (blocks)
-int get_contains_stage1();
-
-// hll_kernels.hip
+// ---- hll_kernels.hip
 struct HllSeg {
     uint8_t *regs;      // 16384 u8 registers
     uint64_t begin;     // element range [begin, end)

@@ -58,16 +58,16 @@ __global__ __launch_bounds__(256) void k_madd_seg(KeysDev keys, const FilterDesc
             // the gathers go out first and the tables are cleared under their latency (the barrier then
             // waits for both; r05 cleared, synchronised, then gathered)
             if (act) {
-                uint64_t h = h1;
+                BloomSeq seq(h1, h2);
 #pragma unroll
                 for (int j = 0; j < KMAX; ++j) {
                     if ((uint32_t)j < f.k) {
-                        const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                        const uint32_t idx = seq.index(f.mp);
                         idxs[j] = idx;
                         word[j] = __hip_atomic_load(&f.bm[idx >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         maxidx = idx > maxidx ? idx : maxidx;
                     }
-                    h += (j & 1) ? h1 : h2;
+                    seq.advance(j);
                 }
             }
             for (uint32_t q = tid; q < S; q += blockDim.x) {
@@ -163,19 +163,10 @@ static void launch_madd_seg_km(const MaddSegArgs &a, hipStream_t st) {
                        a.single);
 }
 
-template <int KLEN>
-static void launch_madd_seg_len(const MaddSegArgs &a, hipStream_t st) {
-    if (a.kmax <= 8) launch_madd_seg_km<KLEN, 8>(a, st);
-    else launch_madd_seg_km<KLEN, 16>(a, st);
-}
-
 void launch_madd_seg(const MaddSegArgs &a, int klen_fast, hipStream_t st) {
-    switch (klen_fast) {
-    case 16: launch_madd_seg_len<16>(a, st); break;
-    case 32: launch_madd_seg_len<32>(a, st); break;
-    case 64: launch_madd_seg_len<64>(a, st); break;
-    default: launch_madd_seg_len<0>(a, st); break;
-    }
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<16, 16>(a.kmax, [&](auto kmax) { launch_madd_seg_km<decltype(klen)::value, decltype(kmax)::value>(a, st); });
+    });
 }
 
 }  // namespace rbx

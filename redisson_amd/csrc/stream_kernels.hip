@@ -186,16 +186,16 @@ __global__ __launch_bounds__(256) void k_stream_probe(KeysDev keys, uint64_t bas
         hash_key<KLEN>(keys, i, h1, h2);
         uint32_t word[KMAX], idxs[KMAX];
         uint32_t maxidx = 0;
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if ((uint32_t)j < f.k) {
-                const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                const uint32_t idx = seq.index(f.mp);
                 idxs[j] = idx;
                 word[j] = f.bm[idx >> 5];
                 maxidx = idx > maxidx ? idx : maxidx;
             }
-            h += (j & 1) ? h1 : h2;
+            seq.advance(j);
         }
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void k_stream_contains_q(KeysDev keys, uint64_
                     hash_key<KLEN>(keys, base + t, e.h1, e.h2);
                     e.t = (uint32_t)t;
                     e.fi = kf[base + t];
-                    e.idx0 = mod63c(e.h1 & 0x7fffffffffffffffULL, pdesc[e.fi].mc);
+                    e.idx0 = BloomSeq::index_of(e.h1, pdesc[e.fi].mc);
                     qb[b * RANGE + qlen[b] + (uint32_t)__popcll(mask & lt)] = e;
                 }
                 qlen[b] += (uint32_t)__popcll(mask);
@@ -361,8 +361,8 @@ __global__ __launch_bounds__(256) void k_stream_contains_q(KeysDev keys, uint64_
                 if (!clear && ((++sjk[s]) & 0xffffu) >= (sjk[s] >> 16)) {
                     fin = fin_p = true;
                 } else if (!clear) {
-                    sidx[s] = mod63c(sh[s] & 0x7fffffffffffffffULL, smp[s]);
-                    sh[s] += (sjk[s] & 1) ? sh1[s] : sh2[s];
+                    sidx[s] = BloomSeq::index_of(sh[s], smp[s]);
+                    sh[s] += BloomSeq::step(sjk[s], sh1[s], sh2[s]);
                 }
                 if (fin) {
                     act[s] = false;
@@ -395,17 +395,17 @@ __global__ __launch_bounds__(256) void k_stream_commit(KeysDev keys, uint64_t ba
             const FilterDesc f = filt[kf[i]];
             uint64_t h1, h2;
             hash_key<KLEN>(keys, i, h1, h2);
-            uint64_t h = h1;
+            BloomSeq seq(h1, h2);
 #pragma unroll
             for (int j = 0; j < KMAX; ++j) {
                 if ((zm >> j) & 1u) {
-                    const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                    const uint32_t idx = seq.index(f.mp);
                     if (ht_owner(T, log2cap, epoch, ((uint64_t)f.fid << 32) | idx) == t) {
                         isnew = true;
                         atomicOr(&f.bm[idx >> 5], bit_in_word(idx));
                     }
                 }
-                h += (j & 1) ? h1 : h2;
+                seq.advance(j);
             }
         }
         if (out) out[i] = isnew;
@@ -442,16 +442,16 @@ __global__ __launch_bounds__(256) void k_stream_probe8(KeysDev keys, uint64_t ba
         hash_key<KLEN>(keys, i, h1, h2);
         uint32_t word[KMAX], idxs[KMAX];
         uint32_t maxidx = 0;
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if ((uint32_t)j < f.k) {
-                const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                const uint32_t idx = seq.index(f.mp);
                 idxs[j] = idx;
                 word[j] = f.bm[idx >> 5];
                 maxidx = idx > maxidx ? idx : maxidx;
             }
-            h += (j & 1) ? h1 : h2;
+            seq.advance(j);
         }
         uint32_t zm = 0;
 #pragma unroll
@@ -524,14 +524,14 @@ __global__ __launch_bounds__(256) void k_stream_final8(KeysDev keys, uint64_t ba
                 const FilterDesc f = filt[kf[i]];
                 uint64_t h1, h2;
                 hash_key<KLEN>(keys, i, h1, h2);
-                uint64_t h = h1;
+                BloomSeq seq(h1, h2);
 #pragma unroll
                 for (int j = 0; j < KMAX; ++j) {
                     if (((rest >> j) & 1u) && !isnew) {
-                        const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                        const uint32_t idx = seq.index(f.mp);
                         isnew = t8_find(T, lg, pb, ((uint64_t)f.fid << bb) | idx) == t;
                     }
-                    h += (j & 1) ? h1 : h2;
+                    seq.advance(j);
                 }
             }
         }
@@ -562,11 +562,11 @@ __global__ __launch_bounds__(256) void k_stream_final8(KeysDev keys, uint64_t ba
 template <int KMAX>
 __device__ __forceinline__ void madd_indexes(uint64_t h1, uint64_t h2, const ModParams &mp, uint32_t zm,
                                              uint32_t (&idxs)[KMAX]) {
-    uint64_t h = h1;
+    BloomSeq seq(h1, h2);
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) {
-        if ((zm >> j) & 1u) idxs[j] = mod63(h & 0x7fffffffffffffffULL, mp);
-        h += (j & 1) ? h1 : h2;
+        if ((zm >> j) & 1u) idxs[j] = seq.index(mp);
+        seq.advance(j);
     }
 }
 
@@ -612,16 +612,16 @@ __global__ __launch_bounds__(256) void k_maddx_gather(KeysDev keys, uint64_t bas
         hash_key<KLEN>(keys, i, h1, h2);
         uint32_t word[KMAX], idxs[KMAX];
         uint32_t maxidx = 0;
-        uint64_t h = h1;
+        BloomSeq seq(h1, h2);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if ((uint32_t)j < f.k) {
-                const uint32_t idx = mod63(h & 0x7fffffffffffffffULL, f.mp);
+                const uint32_t idx = seq.index(f.mp);
                 idxs[j] = idx;
                 word[j] = f.bm[idx >> 5];
                 maxidx = idx > maxidx ? idx : maxidx;
             }
-            h += (j & 1) ? h1 : h2;
+            seq.advance(j);
         }
         uint32_t zm = 0;
 #pragma unroll
@@ -827,13 +827,6 @@ static void launch_stream_chunk_k(const StreamChunkArgs &a, hipStream_t st) {
     }
 }
 
-template <int KLEN>
-static void launch_stream_chunk_len(const StreamChunkArgs &a, hipStream_t st) {
-    if (a.kmax <= 8) launch_stream_chunk_k<KLEN, 8>(a, st);
-    else if (a.kmax <= 16) launch_stream_chunk_k<KLEN, 16>(a, st);
-    else launch_stream_chunk_k<KLEN, 32>(a, st);
-}
-
 template <int KLEN, int KMAX>
 static void launch_maddx_chunk_k(const MaddChunkArgs &a, hipStream_t st) {
     const unsigned grid = grid_for(std::max<uint64_t>(a.nchunk, 1ULL << a.lgC), kMaxGrid);
@@ -850,29 +843,16 @@ static void launch_maddx_chunk_k(const MaddChunkArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(k_maddx_reset, dim3(kMaxGrid), dim3(256), 0, st, a.t8, a.lg, a.cst, a.big);
 }
 
-template <int KLEN>
-static void launch_madd8_chunk_len(const MaddChunkArgs &a, hipStream_t st) {
-    if (a.kmax <= 8) launch_maddx_chunk_k<KLEN, 8>(a, st);
-    else if (a.kmax <= 16) launch_maddx_chunk_k<KLEN, 16>(a, st);
-    else launch_maddx_chunk_k<KLEN, 32>(a, st);
-}
-
 void launch_madd8_chunk(const MaddChunkArgs &a, int klen_fast, hipStream_t st) {
-    switch (klen_fast) {
-    case 16: launch_madd8_chunk_len<16>(a, st); break;
-    case 32: launch_madd8_chunk_len<32>(a, st); break;
-    case 64: launch_madd8_chunk_len<64>(a, st); break;
-    default: launch_madd8_chunk_len<0>(a, st); break;
-    }
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<32, 32>(a.kmax, [&](auto kmax) { launch_maddx_chunk_k<decltype(klen)::value, decltype(kmax)::value>(a, st); });
+    });
 }
 
 void launch_stream_chunk(const StreamChunkArgs &a, int klen_fast, hipStream_t st) {
-    switch (klen_fast) {
-    case 16: launch_stream_chunk_len<16>(a, st); break;
-    case 32: launch_stream_chunk_len<32>(a, st); break;
-    case 64: launch_stream_chunk_len<64>(a, st); break;
-    default: launch_stream_chunk_len<0>(a, st); break;
-    }
+    with_klen(klen_fast, [&](auto klen) {
+        with_kmax<32, 32>(a.kmax, [&](auto kmax) { launch_stream_chunk_k<decltype(klen)::value, decltype(kmax)::value>(a, st); });
+    });
 }
 
 }  // namespace rbx

@@ -50,6 +50,20 @@ def test_device_hash128_host_compiled_matches_oracle():
         assert (out[0], out[1]) == O.redisson_hash128(d), ln
 
 
+def test_bloom_index_sequence_host_compiled_matches_oracle():
+    # the cursor every Bloom kernel walks (rbx_device.h BloomSeq) against RedissonBloomFilter.hash()
+    rng = np.random.default_rng(11)
+    m64 = (1 << 64) - 1
+    pairs = [(int(a), int(b)) for a, b in rng.integers(0, 1 << 64, size=(300, 2), dtype=np.uint64)]
+    pairs += [(m64, m64), (0, 0)]
+    for k in (1, 2, 7, 8, 9, 16, 17, 32, 33, 40):
+        out = (C.c_uint32 * k)()
+        for size in (1, 2, 3, 1 << 19, 95_850_584, 4_294_967_293, 1 << 32):
+            for h1, h2 in pairs:
+                assert L.lib().rbx_selftest_bloom_indexes(h1, h2, k, size, out) == 0, (h1, h2, k, size)
+                assert list(out) == O.bloom_indexes(h1, h2, k, size), (h1, h2, k, size)
+
+
 def test_crc16_and_slot_exports():
     from redisson_amd import calc_slot, crc16, slot_to_gpu
 
