@@ -17,6 +17,8 @@ void rbx_selftest_hash128(const uint8_t *data, uint64_t len, uint64_t out[2]);
 uint32_t rbx_selftest_bloom_indexes(uint64_t h1, uint64_t h2, uint32_t k, uint64_t size, uint32_t *out);
 /* BigDecimal.valueOf(d).toPlainString() (the stored falseProbability string); returns length */
 int rbx_selftest_plain_string(double d, char *out, int cap);
+/* device and pinned buffers the contexts of this process hold: rbx_shutdown returns it to its earlier value */
+int64_t rbx_selftest_live_buffers(void);
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,7 @@ SIGNATURES = {
     "rbx_selftest_hash128": (None, [u8p, C.c_uint64, u64p]),
     "rbx_selftest_bloom_indexes": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
     "rbx_selftest_plain_string": (C.c_int, [C.c_double, C.c_char_p, C.c_int]),
+    "rbx_selftest_live_buffers": (C.c_int64, []),
 }
 
 _lib = None

@@ -35,14 +35,15 @@ int rbx_bench_add_stamps(rbx_ctx *c, unsigned long long *out, uint32_t n) {
     if (!c || !out || n > 16) return fail(RBX_E_ILLEGAL_ARGUMENT, "rbx_bench_add_stamps: n <= 16");
     // the context's lock and device, and only this context's work drained
     std::lock_guard<std::recursive_mutex> g(c->ks.mu);
-    RBX_TRY(set_device(c));  // fails on a shut context (pa_stamps freed)
-    if (c->pa_stamps.cap == 0) {
+    RBX_TRY(set_device(c));  // fails on a shut context (the stamps freed)
+    DevBuf &stamps = c->dev->pa.stamps;
+    if (stamps.cap == 0) {
         memset(out, 0, n * 8);
         return RBX_OK;
     }
     RBX_TRY(quiesce(c));
-    HIP_TRY(hipMemcpyAsync(out, c->pa_stamps.p, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemsetAsync(c->pa_stamps.p, 0, 16 * 8, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, stamps.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(stamps.p, 0, 16 * 8, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RBX_OK;
 }
@@ -88,7 +89,8 @@ int rbx_bench_gather_regions(rbx_ctx *c, const void *d_table, uint64_t table_byt
 int rbx_bench_stream_geometry(rbx_ctx *c, uint64_t *out) {
     if (!c || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
     std::lock_guard<std::recursive_mutex> g(c->ks.mu);
-    for (int i = 0; i < 4; ++i) out[i] = c->st_geom[i];
+    if (c->shut) return fail(RBX_E_ILLEGAL_STATE, "the context has been shut down");
+    for (int i = 0; i < 4; ++i) out[i] = c->dev->strm.geom[i];
     return RBX_OK;
 }
 

@@ -48,10 +48,10 @@ static int bitset_lens(rbx_ctx *c, const std::vector<Bitmap *> &bms, hipStream_t
     for (size_t i0 = 0; i0 < bms.size(); i0 += 8) {
         const size_t m = std::min<size_t>(8, bms.size() - i0);
         for (size_t j = 0; j < m; ++j)
-            if (bms[i0 + j]) HIP_TRY(hipMemcpyAsync(c->pin_word + j, bms[i0 + j]->d_len, 8, hipMemcpyDeviceToHost, st));
+            if (bms[i0 + j]) HIP_TRY(hipMemcpyAsync(c->dev->stage.words() + j, bms[i0 + j]->d_len, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (size_t j = 0; j < m; ++j)
-            if (bms[i0 + j]) (*lens)[i0 + j] = c->pin_word[j];
+            if (bms[i0 + j]) (*lens)[i0 + j] = c->dev->stage.words()[j];
     }
     return RBX_OK;
 }
@@ -73,14 +73,14 @@ static uint64_t max_index(const uint64_t *idx, uint64_t n) {
 
 // the maximum of n device indexes (one wait on `st`), which must be a Redis bit offset
 static int max_index_dev(rbx_ctx *c, const uint64_t *d_idx, uint64_t n, hipStream_t st, uint64_t *out) {
-    RBX_TRY(c->counters.reserve(64));
-    auto *d = c->counters.as<unsigned long long>() + 1;
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
     HIP_TRY(hipMemsetAsync(d, 0, 8, st));
     launch_bits_max(d_idx, n, d, st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->pin_word, d, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->dev->stage.words(), d, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    *out = *c->pin_word;
+    *out = *c->dev->stage.words();
     return *out >= kMaxBitOffset ? fail(RBX_E_REDIS, kBitOffsetMsg) : RBX_OK;
 }
 
@@ -171,12 +171,12 @@ static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed
         size_t scratch = 0;
         int e = fields_grouped_scratch_bytes((uint32_t)std::min(n, kChunk), slot_bits, &scratch);
         if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
-        RBX_TRY(c->fld_sort.reserve(scratch));
+        RBX_TRY(c->dev->bits.fld_sort.reserve(scratch));
         for (uint64_t i0 = 0; i0 < n; i0 += kChunk) {
             const uint32_t m = (uint32_t)std::min(kChunk, n - i0);
             e = launch_fields_grouped(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, d_offs + i0,
                                       d_values + i0, m, d_replies ? d_replies + i0 : nullptr, need, slot_bits,
-                                      c->fld_sort.p, c->fld_sort.cap, st);
+                                      c->dev->bits.fld_sort.p, c->dev->bits.fld_sort.cap, st);
             if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
         }
     }
@@ -208,7 +208,7 @@ int rbx_bitset_get(rbx_ctx *c, rbx_name name, uint64_t index, int *bit) {
     *bit = 0;
     if (!bm || (index >> 3) >= bm->cap_bytes) return RBX_OK;
     // one byte of the string (zero past its length) into a pinned word
-    uint8_t *pin = (uint8_t *)c->pin_word;
+    uint8_t *pin = (uint8_t *)c->dev->stage.words();
     HIP_TRY(hipMemcpyAsync(pin, (const uint8_t *)bm->d_words + (index >> 3), 1, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *bit = (pin[0] >> (7 - (index & 7))) & 1;
@@ -221,8 +221,8 @@ int rbx_bitset_set(rbx_ctx *c, rbx_name name, uint64_t index, int value, int *ol
     RBX_ENTER(c, c->stream);
     std::shared_ptr<Bitmap> bm;
     RBX_TRY(bitset_for_write(c, name_of(name), (index >> 3) + 1, c->stream, &bm));
-    RBX_TRY(c->counters.reserve(64));
-    auto *d = c->counters.as<unsigned long long>() + 1;
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
     launch_bits_set_one(bm->d_words, bm->d_len, index, value != 0, d, c->stream);
     HIP_TRY(hipGetLastError());
     int rc;
@@ -237,9 +237,9 @@ int rbx_bitset_set_indexes(rbx_ctx *c, rbx_name name, const uint64_t *indexes, u
     const uint64_t mx = max_index(indexes, n);
     if (mx >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
     RBX_ENTER(c, c->stream);
-    RBX_TRY(c->bits_idx.reserve(n * 8));
-    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
-    RBX_TRY(bitset_scatter(c, name_of(name), c->bits_idx.as<uint64_t>(), n, mx, value, c->stream));
+    RBX_TRY(c->dev->bits.idx.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(c->dev->bits.idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
+    RBX_TRY(bitset_scatter(c, name_of(name), c->dev->bits.idx.as<uint64_t>(), n, mx, value, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RBX_OK;
 }
@@ -249,11 +249,11 @@ int rbx_bitset_get_indexes(rbx_ctx *c, rbx_name name, const uint64_t *indexes, u
     if (n == 0) return RBX_OK;
     if (max_index(indexes, n) >= kMaxBitOffset) return fail(RBX_E_REDIS, kBitOffsetMsg);
     RBX_ENTER(c, c->stream);
-    RBX_TRY(c->bits_idx.reserve(n * 8));
-    RBX_TRY(c->out_bytes.reserve(n));
-    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
-    RBX_TRY(bitset_gather(c, name_of(name), c->bits_idx.as<uint64_t>(), n, c->out_bytes.as<uint8_t>(), c->stream));
-    HIP_TRY(hipMemcpyAsync(out, c->out_bytes.p, n, hipMemcpyDeviceToHost, c->stream));
+    RBX_TRY(c->dev->bits.idx.reserve(n * 8));
+    RBX_TRY(c->dev->stage.out_bytes.reserve(n));
+    HIP_TRY(hipMemcpyAsync(c->dev->bits.idx.p, indexes, n * 8, hipMemcpyHostToDevice, c->stream));
+    RBX_TRY(bitset_gather(c, name_of(name), c->dev->bits.idx.as<uint64_t>(), n, c->dev->stage.out_bytes.as<uint8_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->dev->stage.out_bytes.p, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RBX_OK;
 }
@@ -328,12 +328,12 @@ int rbx_bitset_op(rbx_ctx *c, int op, rbx_name dest, const rbx_name *srcs, uint3
     // the table after dest has its final allocation: a source that is dest moved with it
     std::vector<BitopSrc> tab(nsrc);
     for (uint32_t i = 0; i < nsrc; ++i) tab[i] = BitopSrc{sb[i] ? (const uint8_t *)sb[i]->d_words : nullptr, lens[i]};
-    RBX_TRY(c->bitop_srcs.reserve(nsrc * sizeof(BitopSrc)));
+    RBX_TRY(c->dev->bits.bitop_srcs.reserve(nsrc * sizeof(BitopSrc)));
     // (a pageable source is staged by the runtime before the call returns)
-    HIP_TRY(hipMemcpyAsync(c->bitop_srcs.p, tab.data(), nsrc * sizeof(BitopSrc), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->dev->bits.bitop_srcs.p, tab.data(), nsrc * sizeof(BitopSrc), hipMemcpyHostToDevice, st));
     // the sweep also clears what a longer previous dest held past the result
     const uint64_t span = (std::max(out_len, lens[nsrc]) + 15) & ~15ULL;
-    launch_bitop(op, (uint8_t *)db->d_words, db->d_len, c->bitop_srcs.as<BitopSrc>(), nsrc, out_len, span, st);
+    launch_bitop(op, (uint8_t *)db->d_words, db->d_len, c->dev->bits.bitop_srcs.as<BitopSrc>(), nsrc, out_len, span, st);
     HIP_TRY(hipGetLastError());
     if (Entry *e = c->ks.find(dn)) e->expire_at = -1;  // setKey without KEEPTTL
     return RBX_OK;
@@ -361,7 +361,7 @@ int rbx_bitset_length(rbx_ctx *c, rbx_name name, int64_t *out) {
     std::shared_ptr<Bitmap> bm;
     uint64_t len;
     RBX_TRY(bitset_len(c, name, &bm, &len));
-    uint8_t *pin = (uint8_t *)c->pin_word;
+    uint8_t *pin = (uint8_t *)c->dev->stage.words();
     pin[0] = pin[1] = 0;
     if (len) {  // the script reads the first and the last byte only
         const uint8_t *s = (const uint8_t *)bm->d_words;
@@ -408,7 +408,7 @@ int rbx_bitset_field(rbx_ctx *c, rbx_name name, int op, int is_signed, int size,
     if (op == RBX_FIELD_GET) {
         RBX_TRY(bitset_find(c, name_of(name), &bm));
         // the field's covering bytes inside the allocation (zero past the string's length), at most 9
-        uint8_t *pin = (uint8_t *)c->pin_word;
+        uint8_t *pin = (uint8_t *)c->dev->stage.words();
         const uint64_t first = offset >> 3, last = (offset + size - 1) >> 3;
         uint64_t nb = 0;
         if (bm && first < bm->cap_bytes) {
@@ -421,8 +421,8 @@ int rbx_bitset_field(rbx_ctx *c, rbx_name name, int op, int is_signed, int size,
     }
     const uint64_t need = ((offset + size - 1) >> 3) + 1;
     RBX_TRY(bitset_for_write(c, name_of(name), need, c->stream, &bm));
-    RBX_TRY(c->counters.reserve(64));
-    auto *d = c->counters.as<unsigned long long>() + 1;
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
     launch_field_one(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, offset, value, (int64_t *)d, need,
                      c->stream);
     HIP_TRY(hipGetLastError());
@@ -444,16 +444,16 @@ int rbx_bitset_fields(rbx_ctx *c, rbx_name name, int op, int is_signed, int size
     }
     RBX_TRY(field_range_check(mx, size));
     RBX_ENTER(c, c->stream);
-    RBX_TRY(c->bits_idx.reserve(n * 8));
-    HIP_TRY(hipMemcpyAsync(c->bits_idx.p, offsets, n * 8, hipMemcpyHostToDevice, c->stream));
+    RBX_TRY(c->dev->bits.idx.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(c->dev->bits.idx.p, offsets, n * 8, hipMemcpyHostToDevice, c->stream));
     if (op != RBX_FIELD_GET) {
-        RBX_TRY(c->fld_vals.reserve(n * 8));
-        HIP_TRY(hipMemcpyAsync(c->fld_vals.p, values, n * 8, hipMemcpyHostToDevice, c->stream));
+        RBX_TRY(c->dev->bits.fld_vals.reserve(n * 8));
+        HIP_TRY(hipMemcpyAsync(c->dev->bits.fld_vals.p, values, n * 8, hipMemcpyHostToDevice, c->stream));
     }
-    if (replies) RBX_TRY(c->fld_out.reserve(n * 8));
-    RBX_TRY(fields_run(c, name_of(name), op, is_signed, size, c->bits_idx.as<uint64_t>(), c->fld_vals.as<int64_t>(), n,
-                       replies ? c->fld_out.as<int64_t>() : nullptr, mx, aligned, c->stream));
-    if (replies) HIP_TRY(hipMemcpyAsync(replies, c->fld_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (replies) RBX_TRY(c->dev->bits.fld_out.reserve(n * 8));
+    RBX_TRY(fields_run(c, name_of(name), op, is_signed, size, c->dev->bits.idx.as<uint64_t>(), c->dev->bits.fld_vals.as<int64_t>(), n,
+                       replies ? c->dev->bits.fld_out.as<int64_t>() : nullptr, mx, aligned, c->stream));
+    if (replies) HIP_TRY(hipMemcpyAsync(replies, c->dev->bits.fld_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RBX_OK;
 }
@@ -465,15 +465,15 @@ int rbx_bitset_fields_dev(rbx_ctx *c, rbx_name name, int op, int is_signed, int 
     hipStream_t st = pick_stream(c, stream);
     RBX_ENTER(c, st);
     // the batch's check result: the largest offset and whether every offset is aligned (one wait)
-    RBX_TRY(c->counters.reserve(64));
-    auto *d = c->counters.as<unsigned long long>() + 1;
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
     HIP_TRY(hipMemsetAsync(d, 0, 16, st));
     launch_fields_check(d_offsets, n, size, d, st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->pin_word, d, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->dev->stage.words(), d, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t mx = c->pin_word[0];
-    const bool aligned = c->pin_word[1] == 0;
+    const uint64_t mx = c->dev->stage.words()[0];
+    const bool aligned = c->dev->stage.words()[1] == 0;
     RBX_TRY(field_range_check(mx, size));
     return fields_run(c, name_of(name), op, is_signed, size, d_offsets, d_values, n, d_replies, mx, aligned, st);
 }

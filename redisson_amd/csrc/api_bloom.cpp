@@ -17,24 +17,6 @@ static uint64_t reply_count(bool is_add, uint64_t cnt) { return is_add ? (uint64
 // =====================================================================================
 // add(): chunked probe/commit over the first-setter table
 // =====================================================================================
-int ensure_table(rbx_ctx *c, uint64_t want_pairs, hipStream_t st) {
-    // capacity >= 2 * pairs per chunk; between 2^16 and 2^27 entries (2 GiB)
-    uint32_t lg = 16;
-    while (lg < 27 && (1ULL << lg) < 2 * want_pairs) ++lg;
-    if (lg > c->log2cap) {
-        RBX_TRY(c->table.reserve(sizeof(HTEntry) << lg));
-        c->log2cap = lg;
-        c->epoch = 255;
-    }
-    if (c->epoch >= 254) {
-        HIP_TRY(hipMemsetAsync(c->table.p, 0xff, sizeof(HTEntry) << c->log2cap, st));
-        c->epoch = 0;
-    } else {
-        c->epoch++;
-    }
-    return RBX_OK;
-}
-
 static int run_add_table(rbx_ctx *c, const KeysDev &keys, const FilterDesc *d_filt, const uint64_t *d_seg_off,
                          uint32_t nseg, const FilterDesc &single, uint32_t kmax, uint8_t *d_out_new,
                          unsigned long long *d_count, unsigned long long *d_seg_counts, hipStream_t st) {
@@ -45,7 +27,8 @@ static int run_add_table(rbx_ctx *c, const KeysDev &keys, const FilterDesc *d_fi
     uint64_t chunk = std::min<uint64_t>(keys.n, (1ULL << 26) / k);
     chunk = std::max<uint64_t>(chunk, 1);
     const size_t zbytes = kmax <= 32 ? chunk * 4 : chunk * (size_t)kmax;
-    RBX_TRY(c->zmask.reserve(zbytes));
+    FirstSetterTable &fst = c->dev->fst;
+    RBX_TRY(c->dev->shared.zmask.reserve(zbytes));
     const int fl = fast_len(keys);
     for (uint64_t base = 0; base < keys.n; base += chunk) {
         const uint64_t nch = std::min<uint64_t>(chunk, keys.n - base);
@@ -53,14 +36,12 @@ static int run_add_table(rbx_ctx *c, const KeysDev &keys, const FilterDesc *d_fi
         if (narrow) {
             uint32_t lg = 16;
             while (lg < 27 && (1ULL << lg) < 2 * nch * k) ++lg;
-            RBX_TRY(c->table.reserve(8ull << lg));
-            HIP_TRY(hipMemsetAsync(c->table.p, 0xff, 8ull << lg, st));
-            c->epoch = 255;  // the wide (16-byte) layout must be re-initialised before reuse
+            RBX_TRY(fst.use_narrow(lg, st));
             a.log2cap = lg;
         } else {
-            RBX_TRY(ensure_table(c, nch * k, st));
-            a.log2cap = c->log2cap;
-            a.epoch = c->epoch;
+            RBX_TRY(fst.ensure(nch * k, st));
+            a.log2cap = fst.log2cap;
+            a.epoch = fst.epoch;
         }
         a.keys = keys;
         a.base = base;
@@ -68,10 +49,10 @@ static int run_add_table(rbx_ctx *c, const KeysDev &keys, const FilterDesc *d_fi
         a.filt = d_filt;
         a.seg_off = d_seg_off;
         a.nseg = nseg;
-        a.tile_seg0 = c->tile_segs.as<uint32_t>();
+        a.tile_seg0 = c->dev->shared.tile_segs.as<uint32_t>();
         a.single = single;
-        a.table = c->table.as<HTEntry>();
-        a.zmask = c->zmask.as<uint32_t>();
+        a.table = fst.table.as<HTEntry>();
+        a.zmask = c->dev->shared.zmask.as<uint32_t>();
         a.kmax = kmax;
         a.out_new = d_out_new;
         a.count = d_count;
@@ -98,11 +79,8 @@ static bool use_add_partitioned(uint64_t size, uint32_t k, uint64_t n) {
 
 // the 16 phase-time words of the profiling build's stamp diagnostics (rbx_bench_add_stamps), zeroed once
 static int phase_stamps(rbx_ctx *c, hipStream_t st, unsigned long long **out) {
-    if (c->pa_stamps.cap == 0) {
-        RBX_TRY(c->pa_stamps.reserve(16 * 8));
-        HIP_TRY(hipMemsetAsync(c->pa_stamps.p, 0, 16 * 8, st));
-    }
-    *out = c->pa_stamps.as<unsigned long long>();
+    RBX_TRY(c->dev->pa.stamps.reserve_filled(16 * 8, 0, st, false));
+    *out = c->dev->pa.stamps.as<unsigned long long>();
     return RBX_OK;
 }
 
@@ -137,23 +115,21 @@ static int run_add_partitioned(rbx_ctx *c, const KeysDev &keys, const FilterDesc
         uint64_t cap = (uint64_t)(pairs * frac * slack) + add;
         return (cap + round - 1) / round * round;
     };
+    PartitionedAddScratch &pa = c->dev->pa;
     const uint64_t cap1 = cap_of(s1, 1.15 / kBaSub, 8192, 8192);
     const uint64_t cap3 = std::min<uint64_t>(kBaMaxRegionPairs, cap_of(s3, 1.3, 256, 64));
-    RBX_TRY(c->pa_p1.reserve((uint64_t)ncoarse * kBaSub * cap1 * 8));
-    RBX_TRY(c->pa_p2.reserve((uint64_t)nregions * cap3 * 8));
+    RBX_TRY(pa.p1.reserve((uint64_t)ncoarse * kBaSub * cap1 * 8));
+    RBX_TRY(pa.p2.reserve((uint64_t)nregions * cap3 * 8));
     const uint32_t nranges = (uint32_t)((chunk + (1ULL << kBaKeyRangeBits) - 1) >> kBaKeyRangeBits);
     const uint64_t cap_rec = (uint64_t)k << kBaKeyRangeBits;  // a range's owner records <= 2^20 keys x k
-    RBX_TRY(c->pa_recs.reserve((uint64_t)nranges * cap_rec * 4));
+    RBX_TRY(pa.recs.reserve((uint64_t)nranges * cap_rec * 4));
     const uint64_t ncnt = (uint64_t)ncoarse * kBaSub + nregions + nranges + 2;
-    RBX_TRY(c->pa_cnt.reserve(ncnt * 4));
+    RBX_TRY(pa.cnt.reserve(ncnt * 4));
     const uint64_t nbw = (uint64_t)nranges << (kBaKeyRangeBits - 5);  // whole ranges (the records kernel's images)
-    RBX_TRY(c->pa_bits.reserve(nbw * 4));
+    RBX_TRY(pa.bits.reserve(nbw * 4));
     // per-key non-owner counters (one byte per key; k_ba_final zeroes what it read): zeroed once
     // when (re)allocated
-    if (c->pa_ctr.cap < nbw * 32) {
-        RBX_TRY(c->pa_ctr.reserve(nbw * 32));
-        HIP_TRY(hipMemsetAsync(c->pa_ctr.p, 0, c->pa_ctr.cap, st));
-    }
+    RBX_TRY(pa.ctr.reserve_filled(nbw * 32, 0, st));
     const int fl = fast_len(keys);
     for (uint64_t base = 0; base < keys.n; base += chunk) {
         BaArgs a{};
@@ -168,19 +144,19 @@ static int run_add_partitioned(rbx_ctx *c, const KeysDev &keys, const FilterDesc
         a.nregions = nregions;
         a.cap1 = cap1;
         a.cap3 = cap3;
-        a.p1 = c->pa_p1.as<unsigned long long>();
-        a.p3 = c->pa_p2.as<unsigned long long>();
-        a.cnt1 = c->pa_cnt.as<uint32_t>();
+        a.p1 = pa.p1.as<unsigned long long>();
+        a.p3 = pa.p2.as<unsigned long long>();
+        a.cnt1 = pa.cnt.as<uint32_t>();
         a.cnt3 = a.cnt1 + (uint64_t)ncoarse * kBaSub;
         a.rec_cnt = a.cnt3 + nregions;
         a.overflow = a.rec_cnt + nranges;
         a.mode = a.overflow + 1;
-        a.recs = c->pa_recs.as<uint32_t>();
+        a.recs = pa.recs.as<uint32_t>();
         a.cap_rec = cap_rec;
         a.nranges = (uint32_t)((a.nchunk + (1ULL << kBaKeyRangeBits) - 1) >> kBaKeyRangeBits);
         a.record_policy = (uint32_t)g_tune.add_record_policy;
-        a.new_bits = c->pa_bits.as<uint32_t>();
-        a.ctr = c->pa_ctr.as<uint32_t>();
+        a.new_bits = pa.bits.as<uint32_t>();
+        a.ctr = pa.ctr.as<uint32_t>();
         a.nwords4 = (size + 127) / 128 * 4;
         a.out_new = d_out_new;
         a.count = d_count;
@@ -189,10 +165,11 @@ static int run_add_partitioned(rbx_ctx *c, const KeysDev &keys, const FilterDesc
         // the counters (but the mode word) and new_bits are zeroed by k_ba_mode, the chunk's first kernel
         launch_add_partitioned_chunk(a, fl, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->pin_word, a.overflow, 4, hipMemcpyDeviceToHost, st));  // pinned: no staging copy
+        unsigned long long *w = c->dev->stage.words();  // pinned: no staging copy
+        HIP_TRY(hipMemcpyAsync(w, a.overflow, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         uint32_t ovf;
-        memcpy(&ovf, c->pin_word, 4);
+        memcpy(&ovf, w, 4);
         if (ovf) {
             // a bucket overflowed before any bitmap word changed: this chunk on the table path
             const KeysDev sub = keys_slice(keys, base, a.nchunk);
@@ -272,14 +249,15 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
     const double lambda = (double)((ntiles0 + g0 - 1) / g0 * tile) * (k - 1) *
                           std::min(1.0, (double)(1ULL << kBkBucketBits) / (double)size);
     const uint64_t capS = ((uint64_t)(lambda + 7.0 * std::sqrt(lambda) + 24.0) + kBkLine - 1) / kBkLine * kBkLine;
-    RBX_TRY(c->pc_bits.reserve(ngroups * 16));
+    PartitionedContainsScratch &pc = c->dev->pc;
+    RBX_TRY(pc.bits.reserve(ngroups * 16));
     const uint32_t nmranges = (uint32_t)((chunk + (1ULL << kBkMissRangeBits) - 1) >> kBkMissRangeBits);
     // miss records: sized for 2 per key (C2-like batches hold ~0.2); beyond that the probe falls
     // back to a direct atomicOr per clear bit, so the answer never depends on the capacity
     const uint64_t capm = 2ULL << kBkMissRangeBits;
-    RBX_TRY(c->pc_mrec.reserve((uint64_t)nmranges * capm * 4));
-    RBX_TRY(c->pc_cnt.reserve((256 + (uint64_t)nb * g0) * 4));  // mcnt, segment counts
-    RBX_TRY(c->pc_pairs.reserve((uint64_t)nb * g0 * capS * 8));
+    RBX_TRY(pc.mrec.reserve((uint64_t)nmranges * capm * 4));
+    RBX_TRY(pc.cnt.reserve((256 + (uint64_t)nb * g0) * 4));  // mcnt, segment counts
+    RBX_TRY(pc.pairs.reserve((uint64_t)nb * g0 * capS * 8));
     const int fl = fast_len(keys);
     for (uint64_t base = 0; base < keys.n; base += chunk) {
         PcArgs a{};
@@ -293,12 +271,12 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
         a.grid1 = (uint32_t)std::min<uint64_t>((a.nchunk + tile - 1) / tile, kBkMaxGrid1);  // <= g0
         a.capS = capS;
         a.nwords4 = (size + 127) / 128 * 4;
-        a.alive = c->pc_bits.as<unsigned long long>();
+        a.alive = pc.bits.as<unsigned long long>();
         a.miss = a.alive + ngroups;
-        a.mcnt = c->pc_cnt.as<uint32_t>();
+        a.mcnt = pc.cnt.as<uint32_t>();
         a.segcnt = a.mcnt + 256;
-        a.pairs = c->pc_pairs.as<unsigned long long>();
-        a.mrec = c->pc_mrec.as<uint32_t>();
+        a.pairs = pc.pairs.as<unsigned long long>();
+        a.mrec = pc.mrec.as<uint32_t>();
         a.capm = capm;
         a.nmranges = (uint32_t)((a.nchunk + (1ULL << kBkMissRangeBits) - 1) >> kBkMissRangeBits);
         a.out = d_out;
@@ -340,8 +318,8 @@ FilterDesc desc_of(const Bitmap &b, uint64_t size, uint32_t k, uint32_t fid) {
 // replies are the in-order ones.  Chunks run in key order (each sees the previous chunks' bits).
 static int bloom_wide_op(rbx_ctx *c, const rbx_keys *keys, uint64_t m, uint32_t k, Bitmap *bm, uint8_t *out_flags,
                          uint64_t *out_count, bool is_add) {
-    RBX_TRY(c->counters.reserve(64));
-    auto *d_count = c->counters.as<unsigned long long>();
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d_count = c->dev->shared.counters.as<unsigned long long>();
     auto *d_oob = d_count + 4;
     HIP_TRY(hipMemsetAsync(d_count, 0, 8, c->stream));
     HIP_TRY(hipMemsetAsync(d_oob, 0, 8, c->stream));
@@ -365,8 +343,8 @@ static int bloom_wide_op(rbx_ctx *c, const rbx_keys *keys, uint64_t m, uint32_t 
             if (tl > 30) return fail(RBX_E_ILLEGAL_ARGUMENT, "wide-filter table past 2^30 entries");
             unsigned long long *table = nullptr;
             if (is_add) {
-                RBX_TRY(c->wide_table.reserve(8ULL << tl));
-                table = c->wide_table.as<unsigned long long>();
+                RBX_TRY(c->dev->shared.wide_table.reserve(8ULL << tl));
+                table = c->dev->shared.wide_table.as<unsigned long long>();
                 HIP_TRY(hipMemsetAsync(table, 0xff, 8ULL << tl, c->stream));
             }
             launch_bloom_wide(sk, m, k, bm ? bm->d_words : nullptr, bm ? bm->d_len : nullptr, table, tl, is_add,
@@ -396,7 +374,7 @@ static int bloom_host_small(rbx_ctx *c, const FilterDesc &f, uint32_t k, const r
     auto *d_count = (unsigned long long *)s.dp;
     const int rc = is_add ? run_add(c, s.dk, nullptr, nullptr, 0, f, k, d_out, d_count, nullptr, c->stream)
                           : run_contains(c, s.dk, f, d_out, d_count, c->stream);
-    (void)hipEventRecord(c->ev_done[0], c->stream);  // slot 0 read by what was queued, whatever rc
+    (void)hipEventRecord(c->dev->stage.ev_done[0], c->stream);  // slot 0 read by what was queued, whatever rc
     if (rc != RBX_OK) return small_fail(c, rc);
     // the readback lands in the pinned block: its upload precedes it on the stream
     HIP_TRY(hipMemcpyAsync(s.hp, s.dp, 8, hipMemcpyDeviceToHost, c->stream));
@@ -411,26 +389,26 @@ static int bloom_host_small(rbx_ctx *c, const FilterDesc &f, uint32_t k, const r
 
 static int tiny_one(rbx_ctx *c, const FilterDesc &f, const KeysDev &dk, bool is_add) {
     const uint32_t seq = tiny_next_seq(c);
-    launch_bloom_one(is_add, dk, fast_len(dk), f, c->pin_tiny_dev, nullptr, (uint32_t *)(c->pin_tiny_dev + kTinyDoneAt),
-                     seq, c->stream);
+    uint8_t *blk = c->dev->stage.pin_tiny_dev;
+    launch_bloom_one(is_add, dk, fast_len(dk), f, blk, nullptr, (uint32_t *)(blk + kTinyDoneAt), seq, c->stream);
     return tiny_wait(c, RBX_OK, seq, true);
 }
 
 static int bloom_host_tiny(rbx_ctx *c, const FilterDesc &f, uint32_t k, const rbx_keys *keys, uint8_t *out_flags,
                            uint64_t *out_count, bool is_add) {
     const KeysDev dk = tiny_stage(c, keys);
-    uint8_t *d_flags = c->pin_tiny_dev;
+    uint8_t *d_flags = c->dev->stage.pin_tiny_dev;
     const bool spin = g_tune.tiny_spin;  // once per call
     if (keys->n == 1 && f.k <= 16 && spin && (!is_add || g_tune.add_one)) {
         RBX_TRY(tiny_one(c, f, dk, is_add));
-        const uint8_t v = c->pin_tiny[0];
+        const uint8_t v = c->dev->stage.tiny()[0];
         if (out_flags) out_flags[0] = v;
         if (out_count) *out_count = v;
         return RBX_OK;
     }
     RBX_TRY(tiny_done(c, is_add ? run_add(c, dk, nullptr, nullptr, 0, f, k, d_flags, nullptr, nullptr, c->stream)
                                   : run_contains(c, dk, f, d_flags, nullptr, c->stream), spin));
-    const uint8_t *fl = c->pin_tiny;
+    const uint8_t *fl = c->dev->stage.tiny();
     uint64_t cnt = 0;
     for (uint64_t i = 0; i < keys->n; ++i) cnt += fl[i];
     if (out_flags) memcpy(out_flags, fl, keys->n);
@@ -472,8 +450,8 @@ static int bloom_host_op(rbx_ctx *c, const std::string &name, int64_t size, uint
     FilterDesc f = desc_of(*bm, size_bits(size), k, 0);
     if (bloom_tiny_fits(c, keys)) return bloom_host_tiny(c, f, k, keys, out_flags, out_count, is_add);
     if (bloom_small_fits(c, keys)) return bloom_host_small(c, f, k, keys, out_flags, out_count, is_add);
-    RBX_TRY(c->counters.reserve(64));
-    auto *d_count = c->counters.as<unsigned long long>();
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d_count = c->dev->shared.counters.as<unsigned long long>();
     HIP_TRY(hipMemsetAsync(d_count, 0, 8, c->stream));
     uint8_t *d_out;
     RBX_TRY(out_flags_dev(c, out_flags, keys->n, &d_out));
@@ -501,8 +479,8 @@ int bitcount_locked(rbx_ctx *c, const std::string &name, uint64_t *out) {
     int rc;
     uint64_t len = read_dev_u64(c, e->bm->d_len, &rc);
     RBX_TRY(rc);
-    RBX_TRY(c->counters.reserve(64));
-    auto *d = c->counters.as<unsigned long long>() + 1;
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
     HIP_TRY(hipMemsetAsync(d, 0, 8, c->stream));
     if (len) launch_bitcount((const uint8_t *)e->bm->d_words, len, d, c->stream);
     HIP_TRY(hipGetLastError());

@@ -13,7 +13,7 @@ rbx::HllState::~HllState() {
     if (d_regs && owner) {
         {
             std::lock_guard<std::recursive_mutex> g(owner->ks.mu);
-            if (!owner->shut) owner->hll_dirty.push_back({d_regs, d_promoted, d_slot_ops});
+            if (!owner->shut) owner->dev->hll.dirty.push_back({d_regs, d_promoted, d_slot_ops});
         }
         if (d_big_ops) (void)hipFree(d_big_ops);  // its own allocation: released also after a shutdown
         ctx_release(owner);
@@ -35,29 +35,30 @@ static int hll_ops_reserve(HllState *h, uint64_t nops) {
 
 // A fresh zeroed HLL register block; the fill runs on `st` (see SlabPool).
 static int hll_alloc(rbx_ctx *c, hipStream_t st, std::shared_ptr<HllState> *out) {
-    if (c->hll_free.empty() && !c->hll_dirty.empty()) {
+    HllPool &hp = c->dev->hll;
+    if (hp.avail.empty() && !hp.dirty.empty()) {
         // the deleted HLLs' slots, zeroed in one launch on the caller's stream (creating 10k HLLs
         // cost 20k small fills, ~10 ms of enqueueing, when each slot was zeroed on its own)
-        const size_t n = c->hll_dirty.size();
+        const size_t n = hp.dirty.size();
         std::vector<void *> ptrs(2 * n);
         for (size_t i = 0; i < n; ++i) {
-            ptrs[i] = c->hll_dirty[i].regs;
-            ptrs[n + i] = c->hll_dirty[i].state;
+            ptrs[i] = hp.dirty[i].regs;
+            ptrs[n + i] = hp.dirty[i].state;
         }
-        RBX_TRY(c->hll_zero_ptrs.reserve(ptrs.size() * sizeof(void *)));
-        HIP_TRY(hipMemcpyAsync(c->hll_zero_ptrs.p, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, st));
-        uint8_t *const *d_regs = c->hll_zero_ptrs.as<uint8_t *>();
+        RBX_TRY(hp.zero_ptrs.reserve(ptrs.size() * sizeof(void *)));
+        HIP_TRY(hipMemcpyAsync(hp.zero_ptrs.p, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, st));
+        uint8_t *const *d_regs = hp.zero_ptrs.as<uint8_t *>();
         launch_hll_zero(d_regs, (uint32_t *const *)(d_regs + n), (uint32_t)n, st);
         HIP_TRY(hipGetLastError());
         // handed out last-deleted first, as before
-        c->hll_free.insert(c->hll_free.end(), c->hll_dirty.begin(), c->hll_dirty.end());
-        c->hll_dirty.clear();
+        hp.avail.insert(hp.avail.end(), hp.dirty.begin(), hp.dirty.end());
+        hp.dirty.clear();
     }
-    if (c->hll_free.empty()) {
+    if (hp.avail.empty()) {
         // registers of kHllPerChunk HLLs, then their state words, then their sparse opcode lists
         uint8_t *chunk = nullptr;
         HIP_TRY(hipMalloc(&chunk, (kHllBytes + kHllStateWords * 4 + kHllOpsBytes) * kHllPerChunk));
-        c->hll_chunks.push_back(chunk);
+        hp.chunks.push_back(chunk);
         uint32_t *words = (uint32_t *)(chunk + kHllBytes * kHllPerChunk);
         uint16_t *ops = (uint16_t *)(words + kHllStateWords * kHllPerChunk);
         // registers and state words of the whole chunk zeroed at once: creating 10k HLLs cost
@@ -65,14 +66,14 @@ static int hll_alloc(rbx_ctx *c, hipStream_t st, std::shared_ptr<HllState> *out)
         HIP_TRY(hipMemsetAsync(chunk, 0, (kHllBytes + kHllStateWords * 4) * kHllPerChunk, st));
         // hand out in reverse so that successive allocations are ascending
         for (size_t i = kHllPerChunk; i-- > 0;)
-            c->hll_free.push_back({chunk + i * kHllBytes, words + i * kHllStateWords, ops + i * (kHllOpsBytes / 2)});
+            hp.avail.push_back({chunk + i * kHllBytes, words + i * kHllStateWords, ops + i * (kHllOpsBytes / 2)});
     }
     auto h = std::make_shared<HllState>();
-    const auto slot = c->hll_free.back();
+    const auto slot = hp.avail.back();
     h->d_regs = slot.regs;
     h->d_promoted = slot.state;
     h->d_sp_ops = h->d_slot_ops = slot.ops;
-    c->hll_free.pop_back();
+    hp.avail.pop_back();
     h->owner = c;
     c->refs.fetch_add(1);
     // every slot in hll_free is zero: registers 0, state 0 (not promoted, the createHLLObject
@@ -138,14 +139,10 @@ static int replay_sparse(rbx_ctx *c, std::vector<HllReplay> &items, const KeysDe
         HIP_TRY(hipGetLastError());
         return RBX_OK;
     }
-    const bool same = c->check_cache.size() == items.size() &&
-                      memcmp(c->check_cache.data(), items.data(), items.size() * sizeof(HllReplay)) == 0;
-    if (!same) {
-        RBX_TRY(c->hll_checks.reserve(items.size() * sizeof(HllReplay)));
-        HIP_TRY(hipMemcpyAsync(c->hll_checks.p, items.data(), items.size() * sizeof(HllReplay), hipMemcpyHostToDevice, st));
-        c->check_cache = items;
-    }
-    launch_hll_sparse_replay(dk, fl, c->hll_checks.as<HllReplay>(), (uint32_t)items.size(), kHllSparseMaxBytes, st);
+    CachedTable<HllReplay> &tab = c->dev->hll.replay;  // cached by content
+    const HllReplay *d_items = tab.sync(items, st);
+    if (!d_items) return tab.err;
+    launch_hll_sparse_replay(dk, fl, d_items, (uint32_t)items.size(), kHllSparseMaxBytes, st);
     HIP_TRY(hipGetLastError());
     return RBX_OK;
 }
@@ -195,19 +192,11 @@ static int pfadd_run(rbx_ctx *c, const std::vector<HllState *> &hl, const uint64
             // a tiny call's tile list is read from the coherent block (each round its own copy)
             const HllSeg *d_tiles = ta ? (const HllSeg *)ta->put(tiles.data(), tiles.size() * sizeof(HllSeg)) : nullptr;
             if (!d_tiles) {
-                // the tile table is cached by content (a steady PFADD pipeline re-sends the same one)
-                const bool single_round = s0 == 0 && s1 == nseg;
-                const bool same = single_round && c->tiles_valid && c->tile_cache.size() == tiles.size() &&
-                                  memcmp(c->tile_cache.data(), tiles.data(), tiles.size() * sizeof(HllSeg)) == 0;
-                if (!same) {
-                    RBX_TRY(c->hll_tiles.reserve(tiles.size() * sizeof(HllSeg)));
-                    // pageable source: staged by the runtime before the call returns; stream order
-                    // keeps the previous round's kernel ahead of this overwrite
-                    HIP_TRY(hipMemcpyAsync(c->hll_tiles.p, tiles.data(), tiles.size() * sizeof(HllSeg), hipMemcpyHostToDevice, st));
-                    c->tiles_valid = single_round;
-                    if (single_round) c->tile_cache = tiles;
-                }
-                d_tiles = c->hll_tiles.as<HllSeg>();
+                // the tile table is cached by content (a steady PFADD pipeline re-sends the same one), for
+                // single-round calls; stream order keeps the previous round's kernel ahead of an overwrite
+                CachedTable<HllSeg> &tab = c->dev->hll.tiles;
+                d_tiles = tab.sync(tiles, st, s0 == 0 && s1 == nseg);
+                if (!d_tiles) return tab.err;
             }
             launch_hll_pfadd(dk, fl, d_tiles, (uint32_t)tiles.size(), d_changed, st);
             HIP_TRY(hipGetLastError());
@@ -233,6 +222,7 @@ int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint6
     for (uint32_t s = 0; s < nseg; ++s)
         if (seg_offsets[s + 1] < seg_offsets[s]) return fail(RBX_E_ILLEGAL_ARGUMENT, "segment offsets must be ascending");
     RBX_ENTER(c, c->stream);
+    Staging &sg = c->dev->stage;
     std::vector<HllState *> hl(nseg);
     std::vector<std::shared_ptr<HllState>> keep(nseg);
     std::vector<uint8_t> created(nseg, 0);
@@ -252,11 +242,11 @@ int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint6
     };
     if (nseg <= kSegMaxKeys && bloom_tiny_fits(c, elements)) {
         // elements, changed words, tile list and replay items in coherent pinned memory (bloom_host_tiny)
-        auto *ch_h = (uint32_t *)(c->pin_tiny + kTinySegAt);
+        auto *ch_h = (uint32_t *)(sg.tiny() + kTinySegAt);
         memset(ch_h, 0, (size_t)nseg * 4);
         const KeysDev dk = tiny_stage(c, elements);
-        TinyArena ta{c->pin_tiny + kTinyArenaAt, c->pin_tiny_dev + kTinyArenaAt, kTinyArenaBytes, 0};
-        RBX_TRY(tiny_done(c, pfadd_run(c, hl, seg_offsets, dk, (uint32_t *)(c->pin_tiny_dev + kTinySegAt), c->stream,
+        TinyArena ta{sg.tiny() + kTinyArenaAt, sg.pin_tiny_dev + kTinyArenaAt, kTinyArenaBytes, 0};
+        RBX_TRY(tiny_done(c, pfadd_run(c, hl, seg_offsets, dk, (uint32_t *)(sg.pin_tiny_dev + kTinySegAt), c->stream,
                                        &ta),
                           g_tune.tiny_spin));
         memcpy(ch.data(), ch_h, (size_t)nseg * 4);
@@ -267,15 +257,15 @@ int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint6
         SmallStage sm;
         RBX_TRY(small_stage(c, elements, nseg * 4, &sm));
         const int rc = pfadd_run(c, hl, seg_offsets, sm.dk, (uint32_t *)sm.dp, c->stream);
-        (void)hipEventRecord(c->ev_done[0], c->stream);
+        (void)hipEventRecord(sg.ev_done[0], c->stream);
         if (rc != RBX_OK) return small_fail(c, rc);
         HIP_TRY(hipMemcpyAsync(sm.hp, sm.dp, nseg * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         memcpy(ch.data(), sm.hp, nseg * 4);
         return reply();
     }
-    RBX_TRY(c->misc.reserve(nseg * 4));
-    auto *d_changed = c->misc.as<uint32_t>();
+    RBX_TRY(c->dev->shared.misc.reserve(nseg * 4));
+    auto *d_changed = c->dev->shared.misc.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(d_changed, 0, nseg * 4, c->stream));
     auto span_bytes = [&](uint64_t e0, uint64_t e1) {
         return elements->offsets ? elements->offsets[e1] - elements->offsets[e0] : (e1 - e0) * elements->stride;
@@ -344,21 +334,22 @@ static uint64_t hll_count_from_histo(const int *reghisto) {
 static int count_regs(rbx_ctx *c, const std::vector<uint8_t *> &regs, uint64_t *out) {
     uint32_t n = (uint32_t)regs.size();
     if (!n) return RBX_OK;
-    RBX_TRY(c->ptrs.reserve(n * sizeof(uint8_t *)));
-    RBX_TRY(c->histo.reserve((size_t)n * 64 * sizeof(int)));
-    RBX_TRY(c->misc.reserve(n * 8));
-    HIP_TRY(hipMemcpyAsync(c->ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-    launch_hll_count(c->ptrs.as<uint8_t *>(), n, c->histo.as<int>(), c->misc.as<unsigned long long>(), c->stream);
+    SharedScratch &sh = c->dev->shared;
+    RBX_TRY(sh.ptrs.reserve(n * sizeof(uint8_t *)));
+    RBX_TRY(sh.histo.reserve((size_t)n * 64 * sizeof(int)));
+    RBX_TRY(sh.misc.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(sh.ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    launch_hll_count(sh.ptrs.as<uint8_t *>(), n, sh.histo.as<int>(), sh.misc.as<unsigned long long>(), c->stream);
     HIP_TRY(hipGetLastError());
     std::vector<unsigned long long> res(n);
-    HIP_TRY(hipMemcpyAsync(res.data(), c->misc.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(res.data(), sh.misc.p, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<int> h;
     for (uint32_t i = 0; i < n; ++i) {
         if (res[i] == ~0ULL) {  // tau branch: histogram to host, glibc pow
             if (h.empty()) {
                 h.resize((size_t)n * 64);
-                HIP_TRY(hipMemcpy(h.data(), c->histo.p, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(h.data(), sh.histo.p, h.size() * sizeof(int), hipMemcpyDeviceToHost));
             }
             res[i] = hll_count_from_histo(&h[(size_t)i * 64]);
         }
@@ -422,13 +413,14 @@ int hll_count(rbx_ctx *c, const std::vector<std::string> &names, uint64_t *out) 
         *out = 0;
         return RBX_OK;
     }
-    RBX_TRY(c->ptrs.reserve(srcs.size() * sizeof(uint8_t *)));
-    RBX_TRY(c->out_bytes.reserve(kHllBytes));
-    HIP_TRY(hipMemcpyAsync(c->ptrs.p, srcs.data(), srcs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-    launch_hll_union(c->ptrs.as<uint8_t *>(), (uint32_t)srcs.size(), c->out_bytes.as<uint8_t>(), c->stream);
+    DevBuf &ptrs = c->dev->shared.ptrs, &merged = c->dev->stage.out_bytes;
+    RBX_TRY(ptrs.reserve(srcs.size() * sizeof(uint8_t *)));
+    RBX_TRY(merged.reserve(kHllBytes));
+    HIP_TRY(hipMemcpyAsync(ptrs.p, srcs.data(), srcs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    launch_hll_union(ptrs.as<uint8_t *>(), (uint32_t)srcs.size(), merged.as<uint8_t>(), c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    std::vector<uint8_t *> u{c->out_bytes.as<uint8_t>()};
+    std::vector<uint8_t *> u{merged.as<uint8_t>()};
     return count_regs(c, u, out);
 }
 
@@ -453,9 +445,10 @@ int hll_merge(rbx_ctx *c, const std::string &dest, const std::vector<std::string
         d->dense = d->dense || h->dense;  // pfmergeCommand: use_dense if any input is
     }
     if (!sp.empty()) {
-        RBX_TRY(c->ptrs.reserve(sp.size() * sizeof(uint8_t *)));
-        HIP_TRY(hipMemcpyAsync(c->ptrs.p, sp.data(), sp.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-        launch_hll_merge(d->d_regs, c->ptrs.as<uint8_t *>(), (uint32_t)sp.size(), c->stream);
+        DevBuf &ptrs = c->dev->shared.ptrs;
+        RBX_TRY(ptrs.reserve(sp.size() * sizeof(uint8_t *)));
+        HIP_TRY(hipMemcpyAsync(ptrs.p, sp.data(), sp.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+        launch_hll_merge(d->d_regs, ptrs.as<uint8_t *>(), (uint32_t)sp.size(), c->stream);
         HIP_TRY(hipGetLastError());
         RBX_TRY(replay_merge(c, {d.get()}, c->stream));
     }
@@ -671,9 +664,10 @@ static int hll_pack_locked(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, uint8_t
     std::vector<uint8_t *> regs;
     RBX_TRY(hll_handles_regs(c, hlls, n, st, &regs));
     if (!n) return RBX_OK;
-    RBX_TRY(c->ptrs.reserve(n * sizeof(uint8_t *)));
-    HIP_TRY(hipMemcpyAsync(c->ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, st));
-    launch_hll_pack(c->ptrs.as<uint8_t *>(), n, d_buf, unpack_max, st);
+    DevBuf &ptrs = c->dev->shared.ptrs;
+    RBX_TRY(ptrs.reserve(n * sizeof(uint8_t *)));
+    HIP_TRY(hipMemcpyAsync(ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, st));
+    launch_hll_pack(ptrs.as<uint8_t *>(), n, d_buf, unpack_max, st);
     HIP_TRY(hipGetLastError());
     if (unpack_max) {
         // the exchange merges the other ranks' registers in: a sparse HLL's string takes them
@@ -913,8 +907,8 @@ int rbx_hll_allreduce_max(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n) {
     RBX_ENTER(c, c->stream);
     if (!c->comm) return fail(RBX_E_ILLEGAL_STATE, "rbx_rccl_init has not been called");
     const size_t bytes = (size_t)n * kHllBytes;
-    RBX_TRY(c->hll_pack.reserve(std::max<size_t>(bytes, 16)));
-    uint8_t *buf = c->hll_pack.as<uint8_t>();
+    RBX_TRY(c->dev->hll.pack.reserve(std::max<size_t>(bytes, 16)));
+    uint8_t *buf = c->dev->hll.pack.as<uint8_t>();
     RBX_TRY(hll_pack_locked(c, hlls, n, buf, false, c->stream));
     ncclResult_t r = ncclAllReduce(buf, buf, bytes, ncclUint8, ncclMax, c->comm, c->stream);
     if (r != ncclSuccess) return fail(RBX_E_DEVICE, ncclGetErrorString(r));

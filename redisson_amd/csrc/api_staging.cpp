@@ -32,29 +32,30 @@ int validate_keys(const rbx_keys *k) {
 // Copies keys [i0, i1) of a host arena to device buffers; returns a device view with keys renumbered
 // from 0 (the offsets as the caller's: KeysDev.off_base = offsets[i0]).
 int upload_keys(rbx_ctx *c, const rbx_keys *k, uint64_t i0, uint64_t i1, KeysDev *out) {
+    Staging &sg = c->dev->stage;
     uint64_t n = i1 - i0;
     if (k->offsets) {
         uint64_t b0 = k->offsets[i0], b1 = k->offsets[i1];
-        RBX_TRY(c->keys_bytes.reserve(b1 - b0 + 16));
-        RBX_TRY(c->keys_offs.reserve((n + 1) * 8));
-        if (b1 > b0) HIP_TRY(hipMemcpyAsync(c->keys_bytes.p, k->bytes + b0, b1 - b0, hipMemcpyHostToDevice, c->stream));
+        RBX_TRY(sg.keys_bytes.reserve(b1 - b0 + 16));
+        RBX_TRY(sg.keys_offs.reserve((n + 1) * 8));
+        if (b1 > b0) HIP_TRY(hipMemcpyAsync(sg.keys_bytes.p, k->bytes + b0, b1 - b0, hipMemcpyHostToDevice, c->stream));
         // the caller's offsets as they are (the kernels subtract off_base): no rebased copy on the stack,
         // so no sync before returning (a pageable source is staged by the runtime before the call returns)
-        HIP_TRY(hipMemcpyAsync(c->keys_offs.p, k->offsets + i0, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        *out = KeysDev{c->keys_bytes.as<uint8_t>(), c->keys_offs.as<uint64_t>(), 0, n, b0};
+        HIP_TRY(hipMemcpyAsync(sg.keys_offs.p, k->offsets + i0, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        *out = KeysDev{sg.keys_bytes.as<uint8_t>(), sg.keys_offs.as<uint64_t>(), 0, n, b0};
     } else {
         uint64_t bytes = n * k->stride;
-        RBX_TRY(c->keys_bytes.reserve(bytes + 16));
-        if (bytes) HIP_TRY(hipMemcpyAsync(c->keys_bytes.p, k->bytes + i0 * k->stride, bytes, hipMemcpyHostToDevice, c->stream));
-        *out = KeysDev{c->keys_bytes.as<uint8_t>(), nullptr, k->stride, n};
+        RBX_TRY(sg.keys_bytes.reserve(bytes + 16));
+        if (bytes) HIP_TRY(hipMemcpyAsync(sg.keys_bytes.p, k->bytes + i0 * k->stride, bytes, hipMemcpyHostToDevice, c->stream));
+        *out = KeysDev{sg.keys_bytes.as<uint8_t>(), nullptr, k->stride, n};
     }
     return RBX_OK;
 }
 
 int out_flags_dev(rbx_ctx *c, const void *want, uint64_t n, uint8_t **d_out) {
     *d_out = nullptr;
-    if (want) RBX_TRY(c->out_bytes.reserve(n));
-    if (want) *d_out = c->out_bytes.as<uint8_t>();
+    if (want) RBX_TRY(c->dev->stage.out_bytes.reserve(n));
+    if (want) *d_out = c->dev->stage.out_bytes.as<uint8_t>();
     return RBX_OK;
 }
 
@@ -70,24 +71,19 @@ static size_t small_pin_bytes(uint64_t limit) { return kSmallHead + limit + limi
 // the pinned block of the one-transfer path, laid out for host_small_bytes = limit (or a larger limit it
 // already had); false (the caller takes the pipelined path) when pinned memory cannot be had
 static bool small_pinned(rbx_ctx *c, uint64_t limit) {
-    if (c->pin_small && c->pin_small_limit >= limit) return true;
-    if (c->pin_small) (void)hipHostFree(c->pin_small);
-    c->pin_small = nullptr;
-    c->pin_small_cap = 0;
-    c->pin_small_limit = 0;
-    const size_t pin = small_pin_bytes(limit);
-    if (hipHostMalloc(&c->pin_small, pin, hipHostMallocDefault) != hipSuccess) {
+    Staging &sg = c->dev->stage;
+    if (sg.pin_small.p && sg.pin_small_limit >= limit) return true;
+    sg.pin_small_limit = 0;
+    if (sg.pin_small.alloc(small_pin_bytes(limit), hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
-        c->pin_small = nullptr;
         return false;
     }
-    c->pin_small_cap = pin;
-    c->pin_small_limit = limit;
+    sg.pin_small_limit = limit;
     return true;
 }
 
 // the process-wide limit is read ONCE here (rbx_tune may change it on another thread);
-// the staging below uses the block's own layout (c->pin_small_limit >= the limit checked here)
+// the staging below uses the block's own layout (pin_small_limit >= the limit checked here)
 bool bloom_small_fits(rbx_ctx *c, const rbx_keys *k) {
     const uint64_t limit = g_tune.small_bytes;
     if (!g_tune.small_host || k->n == 0 || k->n > limit / 4) return false;
@@ -104,13 +100,14 @@ int small_fail(rbx_ctx *c, int rc) {
 
 // One-transfer staging of a small host arena (bloom_small_fits): pinned [0, head) zeroed, the key bytes
 // from `head`, then the offsets (absolute: KeysDev.off_base), uploaded with one copy into staging slot 0
-// on the context stream after slot 0's last reader (its event).  The caller records c->ev_done[0] after
+// on the context stream after slot 0's last reader (its event).  The caller records ev_done[0] after
 // its launches, reads results back into hp / tail_h and syncs; the pinned block stays untouched until then.
 int small_stage(rbx_ctx *c, const rbx_keys *keys, uint64_t head, SmallStage *s, const void *head_src,
                 uint64_t head_src_at, uint64_t head_src_len) {
-    const size_t pin = c->pin_small_cap;  // allocated by bloom_small_fits (small_pinned)
+    Staging &sg = c->dev->stage;
+    const size_t pin = sg.pin_small.cap;  // allocated by bloom_small_fits (small_pinned)
     head = (std::max<uint64_t>(head, 8) + 63) / 64 * 64;  // <= kSmallHead (callers bound it)
-    uint8_t *hp = (uint8_t *)c->pin_small;
+    uint8_t *hp = sg.pin_small.as<uint8_t>();
     const uint64_t n = keys->n, b0 = keys->offsets ? keys->offsets[0] : 0;
     const uint64_t nb = arena_bytes(keys);
     const uint64_t off_at = keys->offsets ? (head + nb + 7) / 8 * 8 : 0, end = off_at ? off_at + (n + 1) * 8 : head + nb;
@@ -118,13 +115,13 @@ int small_stage(rbx_ctx *c, const rbx_keys *keys, uint64_t head, SmallStage *s, 
     if (head_src_len) memcpy(hp + head_src_at, head_src, head_src_len);  // e.g. segment offsets behind the counts
     if (nb) memcpy(hp + head, keys->bytes + b0, nb);
     if (off_at) memcpy(hp + off_at, keys->offsets, (n + 1) * 8);
-    RBX_TRY(c->slot_bytes[0].reserve(pin));
-    uint8_t *dp = c->slot_bytes[0].as<uint8_t>();
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_done[0], 0));  // slot 0's last reader (any stream)
+    RBX_TRY(sg.slot_bytes[0].reserve(pin));
+    uint8_t *dp = sg.slot_bytes[0].as<uint8_t>();
+    HIP_TRY(hipStreamWaitEvent(c->stream, sg.ev_done[0], 0));  // slot 0's last reader (any stream)
     HIP_TRY(hipMemcpyAsync(dp, hp, end, hipMemcpyHostToDevice, c->stream));
     s->hp = hp;
     s->dp = dp;
-    s->tail_h = hp + kSmallHead + c->pin_small_limit;
+    s->tail_h = hp + kSmallHead + sg.pin_small_limit;
     s->dk = KeysDev{dp + head, off_at ? (const uint64_t *)(dp + off_at) : nullptr, keys->stride, n, off_at ? b0 : 0};
     return RBX_OK;
 }
@@ -140,27 +137,24 @@ bool bloom_tiny_fits(rbx_ctx *c, const rbx_keys *keys) {
     if (!g_tune.small_host || keys->n == 0 || keys->n > lim || keys->n > kSegMaxKeys) return false;
     const uint64_t nb = arena_bytes(keys);
     if (nb > kTinyBytes) return false;
-    if (c->pin_tiny) return true;
-    void *h = nullptr, *d = nullptr;
-    if (hipHostMalloc(&h, kTinyBlock, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+    Staging &sg = c->dev->stage;
+    if (sg.pin_tiny.p) return true;
+    void *d = nullptr;
+    if (sg.pin_tiny.alloc(kTinyBlock, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer(&d, sg.pin_tiny.p, 0) != hipSuccess) {
         (void)hipGetLastError();
+        sg.pin_tiny.release();
         return false;
     }
-    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipHostFree(h);
-        return false;
-    }
-    memset(h, 0, kTinyBlock);  // the completion word starts below every sequence number
-    c->pin_tiny = (uint8_t *)h;
-    c->pin_tiny_dev = (uint8_t *)d;
-    c->tiny_seq = 0;
+    memset(sg.pin_tiny.p, 0, kTinyBlock);  // the completion word starts below every sequence number
+    sg.pin_tiny_dev = (uint8_t *)d;
+    sg.tiny_seq = 0;
     return true;
 }
 
 // the keys into the block (the previous call's kernels were done when it returned: tiny_wait); their device view
 KeysDev tiny_stage(rbx_ctx *c, const rbx_keys *keys) {
-    uint8_t *hp = c->pin_tiny, *dp = c->pin_tiny_dev;
+    uint8_t *hp = c->dev->stage.tiny(), *dp = c->dev->stage.pin_tiny_dev;
     const uint64_t n = keys->n, b0 = keys->offsets ? keys->offsets[0] : 0;
     const uint64_t nb = arena_bytes(keys);
     if (nb) memcpy(hp + kTinyKeysAt, keys->bytes + b0, nb);
@@ -176,8 +170,9 @@ KeysDev tiny_stage(rbx_ctx *c, const rbx_keys *keys) {
 // without it (a queue still busy with earlier work, or a fault) the host waits for the stream, which also
 // reports any error.
 uint32_t tiny_next_seq(rbx_ctx *c) {
-    uint32_t seq = ++c->tiny_seq;
-    if (seq == 0) seq = c->tiny_seq = 1;
+    uint32_t &last = c->dev->stage.tiny_seq;
+    uint32_t seq = ++last;
+    if (seq == 0) seq = last = 1;
     return seq;
 }
 
@@ -191,7 +186,7 @@ int tiny_wait(rbx_ctx *c, int rc, uint32_t seq, bool word_launched) {
         HIP_TRY(es);
         return RBX_OK;
     }
-    const auto *h_done = (const uint32_t *)(c->pin_tiny + kTinyDoneAt);
+    const auto *h_done = (const uint32_t *)(c->dev->stage.tiny() + kTinyDoneAt);
     const auto t0 = std::chrono::steady_clock::now();
     while (__atomic_load_n(h_done, __ATOMIC_ACQUIRE) != seq) {
         if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
@@ -209,7 +204,7 @@ int tiny_wait(rbx_ctx *c, int rc, uint32_t seq, bool word_launched) {
 int tiny_done(rbx_ctx *c, int rc, bool spin) {
     spin = spin && rc == RBX_OK;
     const uint32_t seq = spin ? tiny_next_seq(c) : 0;
-    if (spin) launch_done_word((uint32_t *)(c->pin_tiny_dev + kTinyDoneAt), seq, c->stream);
+    if (spin) launch_done_word((uint32_t *)(c->dev->stage.pin_tiny_dev + kTinyDoneAt), seq, c->stream);
     return tiny_wait(c, rc, seq, spin);
 }
 

@@ -21,6 +21,7 @@ inline uint64_t arena_bytes(const rbx_keys *k) { return k->offsets ? k->offsets[
 // chunk j is uploaded on copy_stream into slot j%2 while chunk j-1 computes on `st`.
 template <class Fn>
 int pipelined_host_batches(rbx_ctx *c, const rbx_keys *k, hipStream_t st, Fn &&fn) {
+    Staging &sg = c->dev->stage;
     uint64_t j = 0;
     for (uint64_t i0 = 0; i0 < k->n; ++j) {
         // chunk [i0, i1) of <= staging_bytes key bytes (at least one key)
@@ -28,36 +29,36 @@ int pipelined_host_batches(rbx_ctx *c, const rbx_keys *k, hipStream_t st, Fn &&f
         if (k->offsets) {
             uint64_t lo = i0 + 1, hi = k->n;
             const uint64_t b0 = k->offsets[i0];
-            if (k->offsets[hi] - b0 <= c->staging_bytes) {
+            if (k->offsets[hi] - b0 <= sg.staging_bytes) {
                 lo = hi;
             } else {
                 while (hi - lo > 0) {  // largest i1 >= i0+1 with bytes <= staging
                     const uint64_t mid = (lo + hi + 1) / 2;
-                    if (k->offsets[mid] - b0 <= c->staging_bytes) lo = mid;
+                    if (k->offsets[mid] - b0 <= sg.staging_bytes) lo = mid;
                     else hi = mid - 1;
                 }
             }
             i1 = lo;
         } else {
-            const uint64_t per = k->stride ? std::max<uint64_t>(1, c->staging_bytes / k->stride) : k->n;
+            const uint64_t per = k->stride ? std::max<uint64_t>(1, sg.staging_bytes / k->stride) : k->n;
             i1 = std::min<uint64_t>(k->n, i0 + per);
         }
         const int s = (int)(j & 1);
         const uint64_t n = i1 - i0;
         const uint64_t b0 = k->offsets ? k->offsets[i0] : i0 * k->stride;
         const uint64_t nb = k->offsets ? k->offsets[i1] - b0 : n * k->stride;
-        RBX_TRY(c->slot_bytes[s].reserve(nb + 16));
-        if (k->offsets) RBX_TRY(c->slot_offs[s].reserve((n + 1) * 8));
-        HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->ev_done[s], 0));
-        if (nb) HIP_TRY(hipMemcpyAsync(c->slot_bytes[s].p, k->bytes + b0, nb, hipMemcpyHostToDevice, c->copy_stream));
+        RBX_TRY(sg.slot_bytes[s].reserve(nb + 16));
+        if (k->offsets) RBX_TRY(sg.slot_offs[s].reserve((n + 1) * 8));
+        HIP_TRY(hipStreamWaitEvent(sg.copy_stream, sg.ev_done[s], 0));
+        if (nb) HIP_TRY(hipMemcpyAsync(sg.slot_bytes[s].p, k->bytes + b0, nb, hipMemcpyHostToDevice, sg.copy_stream));
         if (k->offsets)
-            HIP_TRY(hipMemcpyAsync(c->slot_offs[s].p, k->offsets + i0, (n + 1) * 8, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(hipEventRecord(c->ev_copied[s], c->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_copied[s], 0));
-        KeysDev dk{c->slot_bytes[s].as<uint8_t>(), k->offsets ? c->slot_offs[s].as<uint64_t>() : nullptr, k->stride, n,
+            HIP_TRY(hipMemcpyAsync(sg.slot_offs[s].p, k->offsets + i0, (n + 1) * 8, hipMemcpyHostToDevice, sg.copy_stream));
+        HIP_TRY(hipEventRecord(sg.ev_copied[s], sg.copy_stream));
+        HIP_TRY(hipStreamWaitEvent(st, sg.ev_copied[s], 0));
+        KeysDev dk{sg.slot_bytes[s].as<uint8_t>(), k->offsets ? sg.slot_offs[s].as<uint64_t>() : nullptr, k->stride, n,
                    k->offsets ? b0 : 0};
         RBX_TRY(fn(dk, i0));
-        HIP_TRY(hipEventRecord(c->ev_done[s], st));
+        HIP_TRY(hipEventRecord(sg.ev_done[s], st));
         i0 = i1;
     }
     return RBX_OK;

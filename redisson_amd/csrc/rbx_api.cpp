@@ -74,9 +74,10 @@ int grow_bitmap(rbx_ctx *c, Bitmap &b, uint64_t size_bits, hipStream_t st) {
 uint64_t read_dev_u64(rbx_ctx *c, const unsigned long long *p, int *rc) {
     unsigned long long v = 0;
     // into a pinned word: a pageable destination costs the runtime a staging copy
-    hipError_t e = hipMemcpyAsync(c->pin_word, p, 8, hipMemcpyDeviceToHost, c->stream);
+    unsigned long long *w = c->dev->stage.words();
+    hipError_t e = hipMemcpyAsync(w, p, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) v = *c->pin_word;
+    if (e == hipSuccess) v = *w;
     *rc = e == hipSuccess ? RBX_OK : fail(RBX_E_DEVICE, hipGetErrorString(e));
     return v;
 }
@@ -342,13 +343,14 @@ int rbx_init(int device, rbx_ctx **out) {
     c->device = device;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
+    Staging &sg = c->dev->stage;
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&sg.copy_stream, hipStreamNonBlocking);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipEventCreateWithFlags(&c->ev_copied[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming);
+        e = hipEventCreateWithFlags(&sg.ev_copied[i], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sg.ev_done[i], hipEventDisableTiming);
         if (e == hipSuccess && i == 0) e = hipEventCreateWithFlags(&c->ev_scratch, hipEventDisableTiming);
     }
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->pin_word, 64, hipHostMallocDefault);
+    if (e == hipSuccess) e = sg.pin_word.alloc(64, hipHostMallocDefault);
     if (e != hipSuccess) {
         delete c;
         return fail(RBX_E_DEVICE, hipGetErrorString(e));
@@ -384,42 +386,13 @@ int rbx_shutdown(rbx_ctx *c) {
         c->comm = nullptr;
         c->shut = true;  // from here on released HLL blocks are not recycled
         c->ks.clear();
-        for (auto *p : c->hll_chunks) (void)hipFree(p);
-        c->hll_chunks.clear();
-        c->hll_free.clear();
-        c->hll_dirty.clear();
-        c->st_t8_entries = 0;
+        c->dev->hll.free_chunks();
         c->slab.reset();  // bitmaps still held by open handles keep their slab alive
-        for (DevBuf *b : {&c->table, &c->zmask, &c->keys_bytes, &c->keys_offs, &c->out_bytes, &c->seg_offs,
-                          &c->counters, &c->filt_table, &c->probe_table, &c->ptrs, &c->histo, &c->misc, &c->tile_segs,
-                          &c->hll_tiles, &c->pc_bits, &c->pc_cnt, &c->pc_pairs, &c->pc_mrec,
-                          &c->pa_p1, &c->pa_p2, &c->pa_cnt, &c->pa_bits, &c->pa_ctr, &c->pa_recs, &c->st_adds,
-                          &c->st_nadds, &c->zero_bm, &c->hll_pack, &c->slot_bytes[0], &c->slot_bytes[1],
-                          &c->slot_offs[0], &c->slot_offs[1], &c->st_t8, &c->fid_table,
-                          &c->hll_zero_ptrs, &c->wide_table, &c->st_fslot, &c->madd_c, &c->bits_idx,
-                          &c->bitop_srcs, &c->fld_vals, &c->fld_out, &c->fld_sort, &c->pa_stamps, &c->hll_checks}) {
-            if (b->p) (void)hipFree(b->p);
-            b->p = nullptr;
-            b->cap = 0;
-        }
-        for (int i = 0; i < 2; ++i) {
-            if (c->ev_copied[i]) (void)hipEventDestroy(c->ev_copied[i]);
-            if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
-            c->ev_copied[i] = c->ev_done[i] = nullptr;
-        }
+        c->dev.reset();   // every buffer, the staging events, the pinned blocks, the copy stream
         if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
         c->ev_scratch = nullptr;
-        if (c->pin_small) (void)hipHostFree(c->pin_small);
-        c->pin_small = nullptr;
-        c->pin_small_cap = 0;
-        c->pin_small_limit = 0;
-        if (c->pin_word) (void)hipHostFree(c->pin_word);
-        c->pin_word = nullptr;
-        if (c->pin_tiny) (void)hipHostFree(c->pin_tiny);
-        c->pin_tiny = c->pin_tiny_dev = nullptr;
-        if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
         if (c->stream) (void)hipStreamDestroy(c->stream);
-        c->copy_stream = c->stream = nullptr;
+        c->stream = nullptr;
     }
     ctx_release(c);
     return RBX_OK;
@@ -691,6 +664,9 @@ void rbx_selftest_hash128(const uint8_t *data, uint64_t len, uint64_t out[2]) {
     hh_finalize128(s, out[0], out[1]);
 }
 
+// allocations the contexts' DevBuf / PinBuf objects hold in this process (0 once every context is shut down)
+int64_t rbx_selftest_live_buffers(void) { return g_live_buffers.load(); }
+
 int rbx_host_alloc(uint64_t bytes, void **out) {
     if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL out");
     HIP_TRY(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));
@@ -705,7 +681,8 @@ int rbx_host_free(void *p) {
 int rbx_set_staging(rbx_ctx *c, uint64_t bytes) {
     if (!c || bytes < 4096) return fail(RBX_E_ILLEGAL_ARGUMENT, "staging must be >= 4 KiB");
     std::lock_guard<std::recursive_mutex> g(c->ks.mu);
-    c->staging_bytes = bytes;
+    if (c->shut) return fail(RBX_E_ILLEGAL_STATE, "the context has been shut down");
+    c->dev->stage.staging_bytes = bytes;
     return RBX_OK;
 }
 
@@ -767,8 +744,8 @@ int rbx_bloom_digest_n(rbx_ctx *c, rbx_name name, uint64_t *out) {
     int rc;
     const uint64_t len = read_dev_u64(c, e->bm->d_len, &rc);
     RBX_TRY(rc);
-    RBX_TRY(c->counters.reserve(64));
-    auto *d = c->counters.as<unsigned long long>() + 4;
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 4;
     HIP_TRY(hipMemsetAsync(d, 0, 8, c->stream));
     if (len) launch_digest((const uint8_t *)e->bm->d_words, len, d, c->stream);
     HIP_TRY(hipGetLastError());

@@ -1,15 +1,19 @@
-// rbx_ctx.h -- private to csrc/ (never included from include/): the context, its device objects and the
-// call scope, shared by the host translation units of librbx.so (rbx_api.cpp and the api_*.cpp files).
+// rbx_ctx.h -- private to csrc/ (never included from include/), shared by the host translation units of
+// librbx.so (rbx_api.cpp and the api_*.cpp files): the owning buffer types (DevBuf, PinBuf, CachedTable), the
+// objects the keyspace holds, the context with its device state grouped by subsystem, and the call scope.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rbx.h"
@@ -31,26 +35,98 @@
         if (r_ != RBX_OK) return r_; \
     } while (0)
 
-// ---- device buffers ---------------------------------------------------------------------------------
+// ---- buffers that own their allocation ----------------------------------------------------------------
+// Neither copies nor moves: a buffer is freed once, by the destructor of the group it is a member of.
+inline std::atomic<int64_t> g_live_buffers{0};  // allocations DevBuf / PinBuf hold now (rbx_selftest_live_buffers)
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
+    size_t filled = 0;  // bytes from p that hold reserve_filled's byte: 0 until the fill has been queued
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p && hipFree(p) == hipSuccess) --g_live_buffers;
+        p = nullptr;
+        cap = filled = 0;
     }
     int reserve(size_t n) {
         if (n <= cap) return RBX_OK;
-        if (p) {
-            (void)hipFree(p);
-            p = nullptr;
-            cap = 0;
-        }
+        release();
         size_t want = std::max<size_t>(n, 4096);
         HIP_TRY(hipMalloc(&p, want));
+        ++g_live_buffers;
         cap = want;
         return RBX_OK;
     }
+    // reserve(n) for a buffer whose users rely on a fill they restore themselves (an EMPTY table, zeroed
+    // counters): `byte` is queued on `st` only when the buffer grows or an earlier fill did not get queued,
+    // over the whole capacity or (whole = false) over the n bytes asked for
+    int reserve_filled(size_t n, int byte, hipStream_t st, bool whole = true) {
+        if (n <= filled) return RBX_OK;
+        filled = 0;
+        RBX_TRY(reserve(n));
+        const size_t m = whole ? cap : n;
+        HIP_TRY(hipMemsetAsync(p, byte, m, st));
+        filled = m;
+        return RBX_OK;
+    }
+    void invalidate() { filled = 0; }  // a user left the content in an unknown state: the next call fills again
     template <class T> T *as() const { return (T *)p; }
+};
+static_assert(!std::is_copy_constructible_v<DevBuf> && !std::is_move_constructible_v<DevBuf>, "DevBuf owns");
+
+struct PinBuf {  // pinned host memory (hipHostMalloc with the caller's flags)
+    void *p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { release(); }
+    void release() {
+        if (p && hipHostFree(p) == hipSuccess) --g_live_buffers;
+        p = nullptr;
+        cap = 0;
+    }
+    hipError_t alloc(size_t n, unsigned flags) {  // replaces the block
+        release();
+        const hipError_t e = hipHostMalloc(&p, n, flags);
+        if (e != hipSuccess) p = nullptr;
+        else ++g_live_buffers, cap = n;
+        return e;
+    }
+    template <class T> T *as() const { return (T *)p; }
+};
+static_assert(!std::is_copy_constructible_v<PinBuf>, "PinBuf owns");
+
+// A device table uploaded only when its content changes: the buffer and the host copy of what it holds.
+template <class T> struct CachedTable {
+    DevBuf buf;
+    std::vector<T> host;    // content of buf while `valid`
+    bool valid = false;
+    bool uploaded = false;  // the last sync copied (its caller refreshes what it derives from the table)
+    int err = RBX_OK;       // why the last sync returned null
+    void invalidate() { valid = false; }
+    // the device table holding `items`; not cacheable: uploaded now and not compared against next time
+    const T *sync(const std::vector<T> &items, hipStream_t st, bool cacheable = true) {
+        const size_t bytes = items.size() * sizeof(T);
+        uploaded = !(cacheable && valid && host.size() == items.size() && memcmp(host.data(), items.data(), bytes) == 0);
+        if (!uploaded) return buf.as<T>();
+        valid = false;
+        // pageable source: the runtime has staged it when the copy call returns; stream order keeps the
+        // table's previous reader ahead of this overwrite
+        if ((err = upload(items.data(), bytes, st)) != RBX_OK) return nullptr;
+        if (cacheable) host = items;
+        valid = cacheable;
+        return buf.as<T>();
+    }
+    int upload(const T *src, size_t bytes, hipStream_t st) {
+        RBX_TRY(buf.reserve(bytes));
+        HIP_TRY(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
+        return RBX_OK;
+    }
 };
 
 // ---- device objects held by the keyspace (keyspace.h declares them opaque) -------------------------
@@ -149,6 +225,169 @@ struct rbx_hll {
     uint64_t gen = 0;
 };
 
+// ---- the context's device state, grouped by the subsystem that owns it ----------------------------------
+// Each group holds its buffers and the host fields that say what they contain.  rbx_ctx keeps them in one
+// DeviceState, which rbx_shutdown destroys as a whole: a buffer added to a group needs no other mention.
+
+// First-setter table of add() (16-byte HTEntry, cleared once per 254 epochs) and of its narrow 8-byte layout.
+struct FirstSetterTable {
+    DevBuf table;
+    uint32_t log2cap = 0;
+    uint32_t epoch = 255;  // 255 = table needs (re)initialisation
+    // capacity >= 2 * pairs per chunk, between 2^16 and 2^27 entries (2 GiB), and the chunk's epoch
+    int ensure(uint64_t want_pairs, hipStream_t st) {
+        uint32_t lg = 16;
+        while (lg < 27 && (1ULL << lg) < 2 * want_pairs) ++lg;
+        if (lg > log2cap) {
+            RBX_TRY(table.reserve(sizeof(rbx::HTEntry) << lg));
+            log2cap = lg;
+            epoch = 255;
+        }
+        if (epoch >= 254) {
+            HIP_TRY(hipMemsetAsync(table.p, 0xff, sizeof(rbx::HTEntry) << log2cap, st));
+            epoch = 0;
+        } else {
+            epoch++;
+        }
+        return RBX_OK;
+    }
+    // 2^lg EMPTY 8-byte entries for one chunk; the wide layout must be re-initialised before reuse
+    int use_narrow(uint32_t lg, hipStream_t st) {
+        RBX_TRY(table.reserve(8ull << lg));
+        HIP_TRY(hipMemsetAsync(table.p, 0xff, 8ull << lg, st));
+        epoch = 255;
+        return RBX_OK;
+    }
+};
+
+// 8-byte first-setter table shared by the ordered stream and the multi-tenant add: every chunk's walk
+// restores EMPTY, so it is filled only when it grows (or after a user failed midway: buf.invalidate()).
+struct T8Table {
+    DevBuf buf;
+    int ensure(uint64_t entries, hipStream_t st) { return buf.reserve_filled(entries * 8, 0xff, st, false); }
+};
+
+// what upload_filters hands its callers: the device tables of a multi-tenant call and their extent
+struct FilterView {
+    const rbx::FilterDesc *filt = nullptr;  // per segment
+    const rbx::ProbeDesc *probes = nullptr;  // per segment
+    uint32_t *const *fid_bm = nullptr;      // bitmap words per table id (fid)
+    uint32_t kmax = 1;
+    uint64_t bytes = 0;    // of the distinct bitmaps
+    uint32_t nfids = 0;    // distinct table ids
+    uint64_t maxbits = 0;  // the largest of their bitmaps, in bits
+};
+
+// Per-segment descriptor tables of the multi-tenant calls (upload_filters), cached by content and by handle list.
+struct FilterTable {
+    CachedTable<rbx::FilterDesc> table;
+    uint64_t generation = 0;  // ks.generation `table` was built under (a bitmap may have moved since)
+    DevBuf probes, fids;      // ProbeDesc per entry of table; bitmap words per fid
+    // all-zero words standing in for a missing bitmap in multi-tenant contains (GETBIT on a
+    // missing key reads 0; the key is not created), grown on demand, never written by a kernel
+    DevBuf zero_bm;
+    // the handle list the tables were built from (fast path for repeated multi-tenant calls)
+    std::vector<std::pair<const rbx_bloom *, uint64_t>> keys;
+    uint64_t key_generation = ~0ULL;
+    bool create = false;
+    FilterView view;  // of the tables as they are
+};
+
+struct StreamScratch {  // ordered stream and chunked multi-tenant add
+    DevBuf adds, nadds;  // add list, one add counter per chunk
+    DevBuf fslot;        // per add, the slot of its first zero bit's claim
+    DevBuf madd_c;       // multi-tenant add: conflict table C + its MaddxState (+ the `big` flag)
+    uint64_t geom[4] = {0, 0, 0, 0};  // last stream call: bb, fbits, pb, chunk
+};
+
+struct PartitionedContainsScratch {
+    DevBuf bits, cnt, pairs, mrec;
+};
+
+struct PartitionedAddScratch {
+    DevBuf p1, p2, cnt, bits, recs;
+    DevBuf ctr;     // per-key non-owner counters: k_ba_final zeroes what it read
+    DevBuf stamps;  // diagnostics: region-pass phase times (rbx_bench_add_stamps), also the partitioned contains'
+};
+
+// Host-buffer calls: plain uploads, the copy-stream double buffer, the small and tiny tiers' pinned blocks.
+struct Staging {
+    DevBuf keys_bytes, keys_offs, out_bytes, seg_offs;
+    // pipeline: uploads on copy_stream into two device slots while the previous slot's kernels run
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+    DevBuf slot_bytes[2], slot_offs[2];
+    uint64_t staging_bytes = 64ull << 20;
+    // small host batches (bloom_host_small): a pinned copy of the keys, uploaded on the context stream with
+    // the zeroed count word in one transfer; the count and flags come back into it
+    PinBuf pin_small;
+    uint64_t pin_small_limit = 0;  // the host_small_bytes the block was laid out for (its tail offset)
+    PinBuf pin_word;  // pinned readback words (counts, the partitioned add's overflow flag)
+    // tiny host batches (bloom_host_tiny): coherent pinned memory the kernel reads the keys from and
+    // writes the flags into, no transfer on either side
+    PinBuf pin_tiny;
+    uint8_t *pin_tiny_dev = nullptr;  // its device address
+    uint32_t tiny_seq = 0;            // the last completion word a one-key kernel stored into the block
+    unsigned long long *words() const { return pin_word.as<unsigned long long>(); }
+    uint8_t *tiny() const { return pin_tiny.as<uint8_t>(); }
+    ~Staging() {
+        for (hipEvent_t e : {ev_copied[0], ev_copied[1], ev_done[0], ev_done[1]})
+            if (e) (void)hipEventDestroy(e);
+        if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    }
+};
+
+// HLL register pool (chunks of kHllPerChunk x 16 KiB) and PFADD's uploaded tables.
+struct HllPool {
+    struct Slot {
+        uint8_t *regs;
+        uint32_t *state;
+        uint16_t *ops;
+    };
+    std::vector<uint8_t *> chunks;
+    std::vector<Slot> avail;  // zeroed slots (registers, state words, sparse opcodes)
+    std::vector<Slot> dirty;  // slots of deleted HLLs, zeroed together when `avail` runs out
+    DevBuf zero_ptrs;         // their pointers for k_hll_zero
+    CachedTable<rbx::HllSeg> tiles;      // k_hll_pfadd tile list (cached for single-round calls)
+    CachedTable<rbx::HllReplay> replay;  // k_hll_sparse_replay items
+    DevBuf pack;                         // contiguous registers for the RCCL merge
+    void free_chunks() {
+        for (auto *p : chunks) (void)hipFree(p);
+        chunks.clear();
+        avail.clear();
+        dirty.clear();
+    }
+    ~HllPool() { free_chunks(); }
+};
+
+struct BitsetScratch {
+    DevBuf idx, bitop_srcs;             // uploaded indexes, the BITOP source table
+    DevBuf fld_vals, fld_out, fld_sort;  // BITFIELD: uploaded values, replies, the grouped path's sort scratch
+};
+
+// Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).
+struct SharedScratch {
+    DevBuf zmask;       // add(): table path, chunked multi-tenant add, stream -- per key zero-bit masks
+    DevBuf misc;        // per-segment counts (multi_host), PFADD changed words, PFCOUNT results
+    DevBuf counters;    // 64 bytes of count words: Bloom host calls, BITCOUNT, digest, stream, RBitSet
+    DevBuf ptrs, histo;  // register pointers and histograms: PFCOUNT, PFMERGE, register packing
+    DevBuf tile_segs;   // each 256-key tile's first segment: multi-tenant contains and add, the table path
+    DevBuf wide_table;  // first-setter table of |size| > 2^32 adds (bloom_wide_op)
+};
+
+struct DeviceState {
+    FirstSetterTable fst;
+    T8Table t8;
+    FilterTable filt;
+    StreamScratch strm;
+    PartitionedContainsScratch pc;
+    PartitionedAddScratch pa;
+    Staging stage;
+    HllPool hll;
+    BitsetScratch bits;
+    SharedScratch shared;
+};
+
 struct rbx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -158,80 +397,14 @@ struct rbx_ctx {
     std::atomic<int> refs{1};
     bool shut = false;  // rbx_shutdown ran: device resources are gone, calls fail
 
-    // Every DevBuf below is freed by rbx_shutdown from a list of its own: add a new one there too.
-    // first-setter table for add()
-    DevBuf table;
-    uint32_t log2cap = 0;
-    uint32_t epoch = 255;  // 255 = table needs (re)initialisation
-    DevBuf zmask;
-
-    // staging for host-buffer calls
-    DevBuf keys_bytes, keys_offs, out_bytes, seg_offs, counters, filt_table, ptrs, histo, misc, tile_segs, hll_tiles;
-    DevBuf probe_table;  // ProbeDesc per entry of filt_table
-    DevBuf pc_bits, pc_cnt, pc_pairs, pc_mrec;  // partitioned contains
-    DevBuf pa_p1, pa_p2, pa_cnt, pa_bits, pa_ctr, pa_recs;  // partitioned add
-    DevBuf pa_stamps;  // add_partition_diag & 64: region-pass phase times (rbx_bench_add_stamps)
-    DevBuf st_adds, st_nadds;    // ordered stream: add list, one add counter per chunk
-    DevBuf st_t8;                // ordered stream (r04): 8-byte first-setter table (EMPTY between chunks)
-    DevBuf st_fslot;             // ordered stream (r05): per add, the slot of its first zero bit's claim
-    DevBuf madd_c;               // multi-tenant add (r05): conflict table C + its MaddxState (+ the `big` flag)
-    uint64_t madd_maxseg_hint = ~0ULL;  // set by the host-arena add_multi: its largest segment (keys)
-    uint64_t st_t8_entries = 0;  // initialized size of st_t8
-    uint64_t st_geom[4] = {0, 0, 0, 0};             // last stream call: bb, fbits, pb, chunk
-    DevBuf fid_table;            // bitmap words per table id (fid) of the filters of filt_table
-    uint32_t filt_nfids = 0;     // distinct table ids of filt_table
-    uint64_t filt_maxbits = 0;   // the largest of their bitmaps, in bits
-    // all-zero words standing in for a missing bitmap in multi-tenant contains (GETBIT on a
-    // missing key reads 0; the key is not created), grown on demand, never written by a kernel
-    DevBuf zero_bm;
-    DevBuf hll_pack;                                // contiguous registers for the RCCL merge
-    DevBuf wide_table;  // first-setter table of |size| > 2^32 adds (bloom_wide_op)
-    DevBuf bits_idx, bitop_srcs;  // RBitSet: uploaded indexes, the BITOP source table
-    DevBuf fld_vals, fld_out, fld_sort;  // BITFIELD: uploaded values, replies, the grouped path's sort scratch
-    std::vector<rbx::HllSeg> tile_cache;  // content of hll_tiles (valid when tiles_valid)
-    bool tiles_valid = false;
-    std::vector<rbx::FilterDesc> filt_cache;  // content of filt_table
-    uint64_t filt_generation = 0;
-    // the handle list filt_table was built from (fast path for repeated multi-tenant calls)
-    std::vector<std::pair<const rbx_bloom *, uint64_t>> filt_keys;
-    uint64_t filt_key_generation = ~0ULL, filt_bytes = 0;
-    bool filt_create = false;
-    uint32_t filt_kmax = 1;
+    // every device and pinned allocation of the context; gone after rbx_shutdown, so reached only behind
+    // RBX_ENTER / set_device (which fail on `shut`) or an explicit check of `shut` under the lock
+    std::optional<DeviceState> dev{std::in_place};
 
     std::shared_ptr<SlabPool> slab = std::make_shared<SlabPool>();
 
-    // HLL register pool: chunks of kHllPerChunk x 16 KiB
-    std::vector<uint8_t *> hll_chunks;
-    struct HllSlot {
-        uint8_t *regs;
-        uint32_t *state;
-        uint16_t *ops;
-    };
-    std::vector<HllSlot> hll_free;   // zeroed slots (registers, state words, sparse opcodes)
-    std::vector<HllSlot> hll_dirty;  // slots of deleted HLLs, zeroed together when hll_free runs out
-    DevBuf hll_zero_ptrs;            // their pointers for k_hll_zero
-    DevBuf hll_checks;                     // k_hll_sparse_replay items (cached by content)
-    std::vector<rbx::HllReplay> check_cache;
-
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
-
-    // host-buffer pipeline: uploads on copy_stream into two device slots while the
-    // previous slot's kernels run on the compute stream
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-    DevBuf slot_bytes[2], slot_offs[2];
-    uint64_t staging_bytes = 64ull << 20;
-    // small host batches (bloom_host_small): a pinned copy of the keys, uploaded on `stream` with the
-    // zeroed count word in one transfer; the count and flags come back into it
-    void *pin_small = nullptr;
-    size_t pin_small_cap = 0;
-    uint64_t pin_small_limit = 0;  // the host_small_bytes the block was laid out for (its tail offset)
-    unsigned long long *pin_word = nullptr;  // pinned readback words (counts, the partitioned add's overflow flag)
-    // tiny host batches (bloom_host_tiny): coherent pinned memory the kernel reads the keys from and
-    // writes the flags into, no transfer on either side
-    uint8_t *pin_tiny = nullptr, *pin_tiny_dev = nullptr;
-    uint32_t tiny_seq = 0;  // the last completion word a one-key kernel stored into the block
 
     // stream order of the scratch above across calls issued on different streams (CallScope)
     hipEvent_t ev_scratch = nullptr;
@@ -271,8 +444,9 @@ inline hipStream_t pick_stream(rbx_ctx *c, void *s) { return s ? (hipStream_t)s 
 // CallScope opens such a call in the one safe order: the context lock, then the shutdown check and
 // hipSetDevice (nothing touches ev_scratch on a shut context), then that wait.  Its destructor records
 // the event -- only if the constructor got that far -- and then drops the lock.  The caller picks the
-// stream (pick_stream) first.  Scopes nest on one thread (the mutex is recursive: multi_host calls the
-// public *_multi_dev entry points under its own).  RBX_ENTER is an entry point's whole preamble.
+// stream (pick_stream) first.  Scopes nest on one thread (the mutex is recursive: rbx_bloom_stream calls
+// rbx_bloom_stream_dev, and the copies between contexts enter the destination, under their own).
+// RBX_ENTER is an entry point's whole preamble.
 struct CallScope {
     std::lock_guard<std::recursive_mutex> lock;
     rbx_ctx *const c;
@@ -334,7 +508,6 @@ int bitmap_export(rbx_ctx *c, const std::string &name, uint8_t *out, uint64_t ca
 int bitmap_import(rbx_ctx *c, const std::string &name, const uint8_t *bytes, uint64_t len);
 int quiesce(rbx_ctx *c);
 // api_bloom.cpp
-int ensure_table(rbx_ctx *c, uint64_t want_pairs, hipStream_t st);
 int run_add(rbx_ctx *c, const KeysDev &keys, const FilterDesc *d_filt, const uint64_t *d_seg_off, uint32_t nseg,
             const FilterDesc &single, uint32_t kmax, uint8_t *d_out_new, unsigned long long *d_count,
             unsigned long long *d_seg_counts, hipStream_t st);

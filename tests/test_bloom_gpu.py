@@ -873,6 +873,66 @@ def _stream_case(client, fresh, seed):
         client.getBloomFilter(n).delete()
 
 
+def test_t8_table_shared_by_stream_and_multi_add(client, fresh):
+    """The ordered stream and the chunked multi-tenant add share one 8-byte first-setter table, filled with
+    EMPTY only when it grows: each user must leave it EMPTY for the next.  In one context, a 600-command
+    stream, a 5,000-key multi-tenant add whose chunks overflow a 64-entry conflict table into that table, and
+    a second stream, all in 128-command chunks; replies, counts and bitmaps vs the in-order oracle after
+    each step."""
+    from redisson_amd import bloom_stream
+
+    rng = np.random.default_rng(41)
+    names = [f"{fresh}-{i}" for i in range(3)]
+    refs = []
+    for nm in names:
+        f = client.getBloomFilter(nm)
+        f.tryInit(1000, 0.01)
+        refs.append(O.OracleBloom(f.getSize(), f.getHashIterations()))
+    handles = [BloomHandle(client, nm) for nm in names]
+    pool = [rng.bytes(int(n)) for n in rng.integers(0, 40, size=1500)]
+
+    def stream_step():
+        n = 600
+        kf = rng.integers(0, 3, size=n).astype(np.uint32)
+        op = (rng.random(n) < 0.4).astype(np.uint8)
+        keys = [pool[int(j)] for j in rng.integers(0, len(pool), size=n)]
+        out, counts = bloom_stream(client, handles, kf, op, Arena(keys))
+        want = np.zeros(n, np.uint8)
+        for i in range(n):
+            b, o = O.arena([keys[i]])
+            want[i] = refs[kf[i]].add(b, o) if op[i] else refs[kf[i]].contains(b, o)
+        assert np.array_equal(out, want)
+        assert counts[0] == int(want[op == 0].sum()) and counts[1] == int(want[op == 1].sum())
+
+    def multi_add_step():
+        order = [0, 1, 2, 1, 0]  # a filter in two segments: the chunked path, not the per-segment kernel
+        segs = np.array([0, 1000, 2000, 3000, 4000, 5000], np.uint64)
+        keys = [pool[int(j)] for j in rng.integers(0, len(pool), size=5000)]
+        counts, flags = bloom_add_multi(client, [handles[t] for t in order], segs, Arena(keys), per_key=True)
+        for s, t in enumerate(order):
+            a, b = int(segs[s]), int(segs[s + 1])
+            c, fl = refs[t].add(*O.arena(keys[a:b]), per_key=True)
+            assert counts[s] == c and np.array_equal(flags[a:b], fl), s
+
+    def bitmaps():
+        for nm, r in zip(names, refs):
+            assert client.getBloomFilter(nm).exportBitmap() == r.redis_string(), nm
+
+    assert L.lib().rbx_tune(b"stream_chunk", 128) == 0
+    assert L.lib().rbx_tune(b"add_multi_conflict_log2", 6) == 0
+    try:
+        for step in (stream_step, multi_add_step, stream_step):
+            step()
+            bitmaps()
+    finally:
+        L.lib().rbx_tune(b"stream_chunk", 0)
+        L.lib().rbx_tune(b"add_multi_conflict_log2", 17)
+    for h in handles:
+        h.close()
+    for nm in names:
+        client.getBloomFilter(nm).delete()
+
+
 def test_mixed_stream_multi_chunk(client, fresh):
     """A 5M-command stream with k = 32 (chunks of 2^26 / 32 = 2M commands, so three chunks and a
     multi-block add compaction in each): runs of adds and contains on two filters, replayed on

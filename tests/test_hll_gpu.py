@@ -120,6 +120,43 @@ def test_pfadd_pipeline_sequential_replies(client, fresh):
         assert np.array_equal(regs_of(client.getHyperLogLog(nm)), r)
 
 
+def test_pfadd_tile_table_cache(client, fresh):
+    """The uploaded PFADD tile table is cached by content for single-round calls: the same names and segment
+    offsets with other elements (the cached table), another segmentation, and the first one again after one
+    HLL was deleted and re-created (same offsets, another register block) -- registers and counts after
+    each call vs the oracle."""
+    from redisson_amd import _lib as L
+
+    rng = np.random.default_rng(9)
+    names = [f"{fresh}-{i}" for i in range(3)]
+    refs = [O.hll_new() for _ in names]
+    missing = [True] * 3  # PFADD creates the key: reply 1
+    seg_a, seg_b = [0, 300, 700, 1200], [0, 500, 600, 1200]
+
+    def call(segs):
+        mat = rng.integers(0, 256, size=(segs[-1], 16), dtype=np.uint8)
+        replies = hll_add_multi(client, names, np.array(segs, np.uint64), Arena.fixed(mat))
+        for i, nm in enumerate(names):
+            ch = O.hll_pfadd(refs[i], *O.fixed_arena(mat[segs[i]:segs[i + 1]]))
+            assert replies[i] == int(bool(ch) or missing[i]), nm
+            missing[i] = False
+            h = client.getHyperLogLog(nm)
+            assert np.array_equal(regs_of(h), refs[i]), nm
+            assert h.count() == O.hll_count(refs[i])
+
+    assert L.lib().rbx_tune(b"host_small_batches", 0) == 0
+    try:
+        call(seg_a)
+        call(seg_a)
+        call(seg_b)
+        call(seg_a)
+        assert client.getHyperLogLog(names[1]).delete()
+        refs[1], missing[1] = O.hll_new(), True
+        call(seg_a)
+    finally:
+        L.lib().rbx_tune(b"host_small_batches", 1)
+
+
 def test_count_each_and_union(client, fresh):
     rng = np.random.default_rng(8)
     names, refs = [], []

@@ -126,6 +126,93 @@ def test_handles_outlive_shutdown():
     assert L.lib().rbx_hll_close(hp) == 0
 
 
+def test_shutdown_releases_every_buffer():
+    """rbx_shutdown frees every device and pinned buffer of the context (rbx_selftest_live_buffers, relative
+    to what other contexts of the process, such as the session's, hold): each scratch group is reached at
+    the smallest shape that allocates it -- the tiny, small and pipelined host tiers, the table and the
+    partitioned add / contains, the multi-tenant calls on both first-setter tables with a bitmap-less filter
+    (zero_bm), the ordered stream on both tables, HLL PFADD / PFCOUNT / PFMERGE / export, RBitSet index
+    batches, BITOP and BITFIELD.  What the calls return is the parity tests' business; here they only have
+    to succeed."""
+    from redisson_amd import bloom_add_multi, bloom_contains_multi, bloom_stream, hll_add_multi
+
+    lib = L.lib()
+    live = lib.rbx_selftest_live_buffers
+    b0 = live()
+    c = RedissonClient(0)
+    rng = np.random.default_rng(27)
+    mat = rng.integers(0, 256, size=(2000, 16), dtype=np.uint8)
+    defaults = dict(host_tiny_keys=16384, host_small_batches=1, add_partition=2, add_single_seg_keys=256,
+                    contains_partition=2, add_multi_table8=2, stream_table8=1)
+
+    def tune(**kw):
+        for key, v in kw.items():
+            assert lib.rbx_tune(key.encode(), v) == 0
+
+    handles = []
+    try:
+        f = c.getBloomFilter("rel")
+        f.tryInit(100_000, 0.01)
+        f.add(Arena([b"one"]))  # tiny tier
+        f.contains(Arena([b"one"]))
+        tune(host_tiny_keys=0)  # small tier
+        f.addEach(Arena.fixed(mat))
+        f.containsEach(Arena.fixed(mat))
+        tune(host_small_batches=0)  # pipelined tier, in 4 KiB chunks
+        assert lib.rbx_set_staging(c.ctx, 4096) == 0
+        f.addEach(Arena.fixed(mat))
+        f.containsEach(Arena.fixed(mat))
+        tune(add_partition=0, add_single_seg_keys=0)  # table add
+        f.addEach(Arena.fixed(mat[:300]))
+        assert lib.rbx_set_staging(c.ctx, 64 << 20) == 0
+        tune(contains_partition=1, add_partition=1)  # partitioned contains and add
+        big = c.getBloomFilter("rel-big")
+        big.tryInitRaw(1 << 22, 7)
+        m5 = rng.integers(0, 256, size=(5000, 16), dtype=np.uint8)
+        big.addEach(Arena.fixed(m5))
+        big.containsEach(Arena.fixed(m5))
+        tune(contains_partition=2, add_partition=2, add_single_seg_keys=256)
+        # multi-tenant: the third filter has a config and no bitmap
+        names = ["rel-m0", "rel-m1", "rel-m2"]
+        for nm in names:
+            c.getBloomFilter(nm).tryInit(1000, 0.01)
+        for nm in names[:2]:
+            c.getBloomFilter(nm).add(Arena([b"x"]))
+        handles = [BloomHandle(c, nm) for nm in names]
+        segs = np.array([0, 100, 200, 300], np.uint64)
+        bloom_contains_multi(c, handles, segs, Arena.fixed(mat[:300]), per_key=True)
+        for t8 in (2, 0):
+            tune(add_multi_table8=t8)
+            bloom_add_multi(c, handles, segs, Arena.fixed(mat[:300]), per_key=True)
+        kf = rng.integers(0, 3, size=500).astype(np.uint32)
+        op = (rng.random(500) < 0.5).astype(np.uint8)
+        for t8 in (1, 0):
+            tune(stream_table8=t8)
+            bloom_stream(c, handles, kf, op, Arena.fixed(mat[:500]))
+        # HLL (host_small_batches is still 0: the uploaded tile and replay tables)
+        hn = ["rel-h0", "rel-h1", "rel-h2"]
+        hll_add_multi(c, hn, np.array([0, 200, 400, 600], np.uint64), Arena.fixed(mat[:600]))
+        h0 = c.getHyperLogLog(hn[0])
+        h0.count()
+        h0.mergeWith(hn[1], hn[2])
+        h0.exportString()
+        # RBitSet
+        bs = c.getBitSet("rel-b0")
+        idx = rng.integers(0, 100_000, size=100).astype(np.uint64)
+        bs.setIndexes(idx)
+        bs.getIndexes(idx)
+        c.getBitSet("rel-b1").setIndexes(idx[:50])
+        c.getBitSet("rel-b2").or_("rel-b0", "rel-b1")
+        bs.incrementFields(8, np.arange(100, dtype=np.uint64) * 8, np.ones(100, np.int64), replies=True)
+        assert live() > b0
+    finally:
+        tune(**defaults)
+        for h in handles:
+            h.close()
+        c.shutdown()
+    assert live() == b0
+
+
 def test_negative_expected_insertions_filter(client, fresh):
     f = client.getBloomFilter(fresh)
     assert f.tryInit(-20_000, 0.01)
