@@ -51,8 +51,8 @@ int rbx_bench_stream_geometry(rbx_ctx *ctx, uint64_t *out);
  *   "contains_multi_slots"  multi-tenant contains with key slots: 0 never, 1 always,
  *                           2 auto (default: the call's bitmaps exceed 64 MiB)
  *   "contains_qgrid"        slot contains kernel grid, 256..8192 (default 2048)
- *   "contains_partition"    region-bucketed contains for one large filter (one radix pass by 512 KiB
- *                           region, each region probed from LDS in four 128 KiB slices): 0 never,
+ *   "contains_partition"    region-bucketed contains for one large filter (one radix pass by 256 KiB
+ *                           region, each region probed from LDS in two 128 KiB slices): 0 never,
  *                           1 always (k in [2,16]), 2 auto (default: bitmap >= 256 MiB, >= 4M keys)
  *   "add_partition"         region-partitioned add: 0 never, 1 always, 2 auto (default:
  *                           bitmap >= 8 MiB and >= max(2^17, bits / 2^12) keys)

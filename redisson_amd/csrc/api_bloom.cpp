@@ -239,7 +239,7 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
     const uint64_t ngroups = (chunk + 63) / 64;
     // Segment capacity.  Stage-1 block blk owns one segment per region.  With every key surviving
     // stage 1 and the pairs spread uniformly over [0, size), a segment's fill is Poisson with mean
-    //   lambda = (keys per block) * (k - 1) * min(1, 2^22 / size).
+    //   lambda = (keys per block) * (k - 1) * min(1, 2^21 / size).
     // Chernoff: P(X >= lambda + x) <= exp(-x^2 / (2 (lambda + x/3))); x = 7 sqrt(lambda) + 24 keeps
     // that below 1e-9 per segment for every lambda, i.e. below 1e-3 over the <= 2^19 segments of a
     // chunk.  A pair past the capacity is probed directly (bk_direct): capacity never changes answers.

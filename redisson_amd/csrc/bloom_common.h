@@ -9,8 +9,10 @@ namespace rbx {
 // ---------------------------------------------------------------------------------
 // key hashing dispatch
 // ---------------------------------------------------------------------------------
+// (zero: see hh128_bytes; the fixed-length hashes have no use for it)
 template <int KLEN>
-__device__ __forceinline__ void hash_key(const KeysDev &keys, uint64_t i, uint64_t &h1, uint64_t &h2) {
+__device__ __forceinline__ void hash_key(const KeysDev &keys, uint64_t i, uint64_t &h1, uint64_t &h2,
+                                         uint64_t zero = 0) {
     if constexpr (KLEN > 0) {
         hh128_fixed<KLEN>(keys.bytes + i * (uint64_t)KLEN, h1, h2);
     } else {
@@ -23,7 +25,7 @@ __device__ __forceinline__ void hash_key(const KeysDev &keys, uint64_t i, uint64
             a = i * keys.stride;
             len = keys.stride;
         }
-        hh128_bytes(keys.bytes + a, len, h1, h2);
+        hh128_bytes(keys.bytes + a, len, h1, h2, zero);
     }
 }
 

@@ -12,20 +12,15 @@ namespace rbx {
 template <class T> __device__ __forceinline__ void run_store(T v, T *p) { __builtin_nontemporal_store(v, p); }
 
 // Partitioned contains, one radix pass (contains_partitioned.hip).  Stage 1 buckets pairs by
-// 2^22-bit (512 KiB) bitmap region, at most 1024 of them; the probe holds one 2^20-bit (128 KiB)
-// slice of a region in LDS, and the kBkCS workgroups of a cluster hold the kBkCS slices of one
-// region.  RBX_BK_CS=8 (64 KiB slices, two probe workgroups per CU) is an A/B build only.
-#ifndef RBX_BK_CS
-#define RBX_BK_CS 4
-#endif
-static_assert(RBX_BK_CS == 4 || RBX_BK_CS == 8, "cluster of 4 (shipped) or 8 (A/B) workgroups");
-constexpr uint32_t kBkCS = RBX_BK_CS;
-constexpr uint32_t kBkBucketBits = 22;                                          // bits per region
-constexpr uint32_t kBkSliceBits = kBkBucketBits - (kBkCS == 4 ? 2 : 3);         // bits per slice
+// 2^21-bit (256 KiB) bitmap region, at most 2048 of them; the probe holds one 2^20-bit (128 KiB)
+// slice of a region in LDS, and the two workgroups of a cluster hold the two slices of one region.
+constexpr uint32_t kBkCS = 2;                                                   // workgroups per cluster
+constexpr uint32_t kBkBucketBits = 21;                                          // bits per region
+constexpr uint32_t kBkSliceBits = kBkBucketBits - 1;                            // bits per slice
 constexpr uint32_t kBkSliceWords = 1u << (kBkSliceBits - 5);
 constexpr uint32_t kBkMaxBuckets = 1u << (32 - kBkBucketBits);                  // filters hold <= 2^32 bits
 constexpr uint32_t kBkLine = 8;                                                 // pairs per 64-byte line
-constexpr uint32_t kBkMaxGrid1 = 512;                                           // stage-1 blocks (persistent)
+constexpr uint32_t kBkMaxGrid1 = 256;                                           // stage-1 blocks (persistent), one per CU
 
 // exclusive scan of cnt[0..nb) (nb <= 64 * PER, PER consecutive buckets per lane) by wave 0 into
 // start[] and pos[]

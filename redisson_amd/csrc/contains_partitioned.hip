@@ -11,15 +11,15 @@
 //   K1 stage1 : hash every key, test bit 0 with one random gather (a key is absent at its first
 //               0 bit, and on a lightly filled filter most absent keys fail here); `alive` bit per
 //               key; the survivors' k-1 remaining bits become (bit index, key id) pairs, bucketed
-//               by 512 KiB bitmap region (<= 1024 buckets) through one 64-byte line buffer per
+//               by 256 KiB bitmap region (<= 2048 buckets) through one 64-byte line buffer per
 //               bucket in LDS; a full buffer is stored as one whole line into the segment that
 //               this block owns for the bucket (no global reservations).
-//   K4 probe  : a cluster of kBkCS workgroups per region, each holding one 128 KiB slice of it in
-//               LDS.  Every workgroup streams all of the region's segments and tests the pairs
-//               that fall into its slice; a clear bit (only keys that survived stage 1 by chance)
+//   K4 probe  : a cluster of two workgroups per region, each holding one 128 KiB slice (half) of it
+//               in LDS.  Both workgroups stream all of the region's segments and test the pairs
+//               that fall into their slice; a clear bit (only keys that survived stage 1 by chance)
 //               records the key id, bucketed by 2^19-key range.  The workgroups of a cluster share
 //               blockIdx % 8 and are adjacent in dispatch order, so they tend to share an XCD and
-//               three of the four reads of a segment are served by its L2.  They never communicate:
+//               one of the two reads of a segment is served by its L2.  They never communicate:
 //               placement changes only the speed.
 //   K5 misses : records -> LDS image of the range's miss words -> OR-ed into `miss`.
 //   K6 final  : present = alive AND NOT miss; count (+ per-key bytes).
@@ -42,7 +42,7 @@ __device__ __forceinline__ void bk_direct(unsigned long long e, const uint32_t *
 }
 
 // K1 -----------------------------------------------------------------------------------
-// Tile = NT * PER keys; a persistent grid of G <= 512 blocks strides over the tiles.  Hash, test
+// Tile = NT * PER keys; a persistent grid of G <= 256 blocks strides over the tiles.  Hash, test
 // bit 0 (one random gather per key), then each of the survivors' k-1 remaining bits takes a slot
 // of its bucket's line buffer (one LDS atomic).  A pair whose slot is past the line stays in its
 // registers until a flush round has stored the line: a round stores every full line (eight lanes
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
                                                    unsigned long long *__restrict__ miss, uint32_t flags) {
     if (!kDiag) flags = 0;  // wrong-answer diagnostics exist in the profiling build only (rbx_kernels.h)
     constexpr int TILE = NT * PER, NP = PER * (KMAX - 1);
-    // 78 KiB with the lists: two blocks per CU
+    // 2048 line buffers are 128 KiB, 152 KiB with the counters and lists: one block per CU
     __shared__ __attribute__((aligned(16))) unsigned long long s_buf[kBkMaxBuckets * kBkLine];
     __shared__ uint32_t s_fill[kBkMaxBuckets];  // pairs in the bucket's line buffer (and pending past it)
     __shared__ uint32_t s_out[kBkMaxBuckets];   // pairs of the bucket this block has stored
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
     const uint32_t lane = threadIdx.x & 63, lane8 = threadIdx.x & (kBkLine - 1);
     // Segment (bucket b, stage-1 block blk) of nb buckets starts at pair (blk * nb + b) * capS.
     // Block-major: a block's nb segments are adjacent, so its line stores stay inside nb * capS pairs
-    // (C2: 11 MB) and the probe reads a region's segments at that stride (bucket-major, a region's
+    // (C2: 23 MB) and the probe reads a region's segments at that stride (bucket-major, a region's
     // segments adjacent, measured slower: DESIGN.md §3.6 r07).
     const uint32_t G = gridDim.x;
     unsigned long long *seg0 = pairs + blockIdx.x * ((uint64_t)nb * capS);
@@ -91,7 +91,16 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
         for (int q = 0; q < PER; ++q) {
             const uint64_t t = tt0 + q * NT;
             h1[q] = h2[q] = 0;
-            if (t < nchunk) hash_key<KLEN>(keys, base + t, h1[q], h2[q]);
+            // Generic key length: the hash's reset words, hoisted out of the tile loop, took 32 of a
+            // 1024-thread block's 128 VGPRs per thread and made k > 8 spill; a zero the compiler
+            // cannot see through keeps them literals (hh128_bytes).
+            uint64_t zero = 0;
+            if constexpr (KLEN == 0) {
+                uint32_t z = 0;
+                asm volatile("" : "+v"(z));
+                zero = ((uint64_t)z << 32) | z;
+            }
+            if (t < nchunk) hash_key<KLEN>(keys, base + t, h1[q], h2[q], zero);
         }
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
@@ -205,13 +214,13 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
 // atomicOr per clear bit (~21M per 1e8 C2 keys: keys that passed bit 0 by chance, ~5.5 clear
 // bits each) cost one memory request each; the runs cost ~1 per 27 records.
 // records per slice held in LDS (C2: ~5.1k per 128 KiB slice); beyond: direct atomicOr
-constexpr uint32_t kBkMissBuf = kBkCS == 4 ? 6400 : 2800;
+constexpr uint32_t kBkMissBuf = 6400;
 
 __device__ __forceinline__ void bk_miss_direct(uint32_t key, unsigned long long *miss) {
     atomicOr(&miss[key >> 6], 1ULL << (key & 63));
 }
 
-// one pair against the slice in LDS; pairs of the region's other slices are skipped
+// one pair against the slice in LDS; pairs of the region's other slice are skipped
 __device__ __forceinline__ void bk_test(const uint32_t *s_bm, uint32_t slice, uint32_t key, uint32_t idx,
                                         unsigned long long *miss, uint32_t *s_mrec, uint32_t *s_mn, uint32_t flags) {
     if (((idx >> kBkSliceBits) & (kBkCS - 1)) != slice) return;
@@ -229,11 +238,12 @@ __device__ __forceinline__ void bk_test(const uint32_t *s_bm, uint32_t slice, ui
     }
 }
 
-// Block bid: x = bid % 8, j = bid / 8; slice = j % kBkCS, cluster = (j / kBkCS) * 8 + x.  A cluster
-// walks regions cluster, cluster + nclusters, ...  Wave v of a workgroup reads segments v, v + 16,
-// ... of the region: a lane loads two pairs (16 B) at a time, kBkProbeU loads per segment in flight,
-// and the next segment's loads are issued before the current one's pairs are tested.  Plain loads,
-// not nontemporal ones: the sibling workgroups need the lines to stay in L2.
+// Block bid: x = bid % 8, j = bid / 8; slice = j % 2, cluster = (j / 2) * 8 + x: 128 clusters in a
+// grid of 256.  A cluster walks regions cluster, cluster + nclusters, ...  Wave v of a workgroup reads
+// segments v, v + 16, ... of the region's <= 256 (16 per wave): a lane loads two pairs (16 B) at a
+// time, kBkProbeU loads per segment in flight, and the next segment's loads are issued before the
+// current one's pairs are tested.  Plain loads, not nontemporal ones: the sibling workgroup needs
+// the lines to stay in L2.
 constexpr uint32_t kBkProbeU = 6;  // 768 pairs per segment in one round (C2: ~620)
 
 template <bool STAMP>
@@ -433,15 +443,16 @@ static unsigned grid_for_pc(uint64_t n) {
 }
 
 // launcher -------------------------------------------------------------------------------
-// Shapes: stage 1 at 512 threads with one key per thread (512-key tiles, kBkTileKeys; 1024-key
-// tiles at k <= 8 measured slower), 78 KiB of LDS, two blocks per CU; the probe at 1024
-// threads, one workgroup per CU (a 128 KiB slice + the miss buffers), in whole groups of 8 clusters.
-// The A/Bs (tile size, cluster of 8, segment layout) are in DESIGN.md §3.6 r07.
+// Shapes: stage 1 at 1024 threads with one key per thread (1024-key tiles, kBkTileKeys), 152 KiB
+// of LDS, one block per CU; the probe at 1024 threads, one workgroup per CU (a 128 KiB slice + the
+// miss buffers), in whole groups of 8 clusters.  The A/Bs (region size, tile size, segment layout)
+// are in DESIGN.md §3.6 r07 and r08.
 template <int KLEN, int KMAX>
 static void bk_chunk(const PcArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL((k_bk_stage1<KLEN, KMAX, 512, 1>), dim3(a.grid1), dim3(512), 0, st, a.keys, a.base,
+    static_assert(kBkTileKeys == 1024, "the stage-1 tile is the block: one key per thread");
+    hipLaunchKernelGGL((k_bk_stage1<KLEN, KMAX, 1024, 1>), dim3(a.grid1), dim3(1024), 0, st, a.keys, a.base,
                        a.nchunk, a.bm, a.mp, a.k, a.nb, a.capS, a.pairs, a.segcnt, a.alive, a.miss, a.flags);
-    constexpr uint32_t kGroup = 8 * kBkCS, kMaxProbe = kBkCS == 4 ? 256 : 512;
+    constexpr uint32_t kGroup = 8 * kBkCS, kMaxProbe = 256;
     const uint32_t gp = std::max(kGroup, std::min(a.nb * kBkCS, kMaxProbe) / kGroup * kGroup);
     if (kDiag && a.stamps)
         hipLaunchKernelGGL((k_bk_probe<true>), dim3(gp), dim3(1024), 0, st, a.pairs, a.segcnt, a.grid1, a.capS, a.nb,

@@ -324,10 +324,16 @@ __device__ __forceinline__ void load_words_unaligned(const uint8_t *p, uint32_t 
     for (int i = 0; i < 8; ++i) out[i] = __builtin_amdgcn_alignbyte(r[i + 1], r[i], sh);
 }
 
-// HighwayHash128 of an arbitrary-length key (generic path).
-__device__ __forceinline__ void hh128_bytes(const uint8_t *p, uint64_t len, uint64_t &h1, uint64_t &h2) {
+// HighwayHash128 of an arbitrary-length key (generic path).  `zero` is 0, XOR-ed into the reset
+// state: a caller inside a long loop passes a zero the compiler cannot see through, so that the 32
+// reset words are literals of those XORs and not 32 VGPRs hoisted out of the caller's loop
+// (k_bk_stage1).  The default folds away.
+__device__ __forceinline__ void hh128_bytes(const uint8_t *p, uint64_t len, uint64_t &h1, uint64_t &h2,
+                                            uint64_t zero = 0) {
     HH s;
     hh_reset(s);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s.v0[j] ^= zero, s.v1[j] ^= zero, s.mul0[j] ^= zero, s.mul1[j] ^= zero;
     uint64_t i = 0;
     uint32_t w[8];
     for (; i + 32 <= len; i += 32) {

@@ -125,9 +125,9 @@ int get_contains_stage1();
 void set_contains_qgrid(int v);   // slot contains kernel grid (blocks)
 
 // ---- contains_partitioned.hip
-// One chunk of keys against one filter, one radix pass.  Stage 1 buckets pairs by 2^22-bit (512 KiB)
+// One chunk of keys against one filter, one radix pass.  Stage 1 buckets pairs by 2^21-bit (256 KiB)
 // bitmap region; the probe holds one 2^20-bit (128 KiB) slice of a region in LDS (bucket_common.h).
-constexpr uint32_t kBkTileKeys = 512;  // keys per stage-1 tile: 512 threads, one key each
+constexpr uint32_t kBkTileKeys = 1024;  // keys per stage-1 tile: 1024 threads, one key each
 constexpr int kBkMissRangeBits = 19;   // probe misses are bucketed by 2^19-key range (64 KiB LDS bitmap)
 struct PcArgs {
     KeysDev keys;
@@ -135,8 +135,8 @@ struct PcArgs {
     const uint32_t *bm;
     ModParams mp;
     uint32_t k;
-    uint32_t nb;            // regions (stage-1 buckets) = ceil(size / 2^22) <= 1024
-    uint32_t grid1;         // stage-1 blocks G = min(tiles of the chunk, 512); every block owns a segment per bucket
+    uint32_t nb;            // regions (stage-1 buckets) = ceil(size / 2^21) <= 2048
+    uint32_t grid1;         // stage-1 blocks G = min(tiles of the chunk, 256); every block owns a segment per bucket
     uint64_t capS;          // pair capacity of one segment, a multiple of 8
     uint64_t nwords4;       // bitmap words rounded up to a multiple of 4
     unsigned long long *pairs;  // nb * G segments of capS pairs (bit index << 32 | key id): segment (b, blk) at (blk*nb + b) * capS
