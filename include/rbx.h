@@ -299,6 +299,54 @@ int rbx_bitset_fields_dev(rbx_ctx *ctx, rbx_name name, int op, int is_signed, in
                           const int64_t *d_values, uint64_t n, int64_t *d_replies, void *stream);
 /* GET over a host string, no context (as rbx_bitset_length_of) */
 int rbx_bitset_field_of(const uint8_t *bytes, uint64_t len, int is_signed, int size, uint64_t offset, int64_t *out);
+/* BITCOUNT key start end [BYTE|BIT] and BITPOS key bit [start [end [BYTE|BIT]]] -- the two bit commands that
+ * Spring Data's RedissonConnection (S/ = redisson-spring-data/redisson-spring-data-31/src/main/java/org/
+ * redisson/spring/data/connection/RedissonConnection.java) sends beside the ones above: bitCount(key, begin,
+ * end) S:638-646 and bitPos(key, bit, range) S:2337-2359 (getBit / setBit S:628-636, bitOp S:650-661 and
+ * strLen S:663-666 are rbx_bitset_get / _set / _op / _size).  RBitSet itself has neither.  Restated from
+ * [redis-7.2] bitops.c bitcountCommand / bitposCommand; parity is unpinned, as for the HLL strings.
+ *   Range   start and end are signed; the unit is RBX_RANGE_BYTE or RBX_RANGE_BIT and T = the string's
+ *           length in that unit.  A negative start or end counts from the end (+= T); then start is clamped to
+ *           >= 0 and end to [0, T - 1]; start > end is the empty range.  Both ends are inclusive.
+ *   COUNT   the ones of the range; 0 for an empty range and a missing key.  start < 0 && end < 0 && start >
+ *           end is 0 before anything is normalised (-10 -20 on 3 bytes would otherwise count byte 0).
+ *   POS     the first position of the range whose bit equals `bit`, as an absolute bit offset.  nargs says
+ *           how much was given: 0 = BITPOS key bit, 1 = + start, 2 = + start end [unit]; the default start
+ *           is 0, the default end the last byte.  An empty range is -1 (every query on an existing empty
+ *           string); there is no pre-check (1 -10 -20 on 3 bytes searches byte 0).  Nothing found: -1 for
+ *           bit 1 and for bit 0 with an end given, else 8 * length (the string counts as zero-padded on the
+ *           right).  A missing key is -1 for bit 1 and 0 for bit 0.  A bit other than 0 / 1 is RBX_E_REDIS
+ *           "ERR The bit argument must be 1 or 0."; RBX_RANGE_BIT with nargs < 2 is RBX_E_REDIS "ERR
+ *           syntax error" (a unit needs an end).
+ *   Errors  an unknown unit or nargs is RBX_E_ILLEGAL_ARGUMENT.  A key of another type is RBX_E_WRONGTYPE, an
+ *           HLL key included (the divergence noted at rbx_bitset_op).  Neither command creates, grows or
+ *           touches a key or its timeout.
+ *   Batch   rbx_bitset_count_ranges / _pos_ranges are n commands on one key in one call (engine extension,
+ *           like rbx_bitset_get_indexes): out[i] is what single call i returns.  pos takes one `bit` per batch;
+ *           ends == NULL makes every query "bit start" (RBX_RANGE_BYTE only).  n = 0 sends nothing.
+ *   Paths   one command: a grid-wide masked count, or a search over ascending chunks that stops at the first
+ *           hit.  A batch: one wave per query, which walks its range or -- when the ranges together hold more
+ *           bytes than the string plus 8 KiB per query, or one exceeds rbx_tune "bitrange_chain_max" -- reads
+ *           whole 4 KiB blocks from a prefix-sum directory built for the call.  Every path answers the same.
+ * The _dev forms take device arrays and enqueue on `stream`; like rbx_bitset_get_indexes_dev they wait once on
+ * the stream, for the length word and the batch's work summary (the bytes its ranges cover, and the longest). */
+enum { RBX_RANGE_BYTE = 0, RBX_RANGE_BIT = 1 };
+int rbx_bitset_count_range(rbx_ctx *ctx, rbx_name name, int64_t start, int64_t end, int unit, uint64_t *out);
+int rbx_bitset_pos(rbx_ctx *ctx, rbx_name name, int bit, int nargs, int64_t start, int64_t end, int unit, int64_t *out);
+int rbx_bitset_count_ranges(rbx_ctx *ctx, rbx_name name, const int64_t *starts, const int64_t *ends, uint64_t n,
+                            int unit, uint64_t *out);
+int rbx_bitset_pos_ranges(rbx_ctx *ctx, rbx_name name, int bit, const int64_t *starts, const int64_t *ends, uint64_t n,
+                          int unit, int64_t *out);
+int rbx_bitset_count_ranges_dev(rbx_ctx *ctx, rbx_name name, const int64_t *d_starts, const int64_t *d_ends, uint64_t n,
+                                int unit, uint64_t *d_out, void *stream);
+int rbx_bitset_pos_ranges_dev(rbx_ctx *ctx, rbx_name name, int bit, const int64_t *d_starts, const int64_t *d_ends,
+                              uint64_t n, int unit, int64_t *d_out, void *stream);
+/* the same rules over a host string, no context (as rbx_bitset_field_of); missing != 0 (with len == 0) = a
+ * missing key */
+int rbx_bitset_count_of(const uint8_t *bytes, uint64_t len, int missing, int64_t start, int64_t end, int unit,
+                        uint64_t *out);
+int rbx_bitset_pos_of(const uint8_t *bytes, uint64_t len, int missing, int bit, int nargs, int64_t start, int64_t end,
+                      int unit, int64_t *out);
 
 /* ---- replicas ("replicate the bitmap, split contains keys across GPUs") ---------
  * Redisson serves contains' GETBITs as reads that may go to a replica

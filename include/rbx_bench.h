@@ -42,6 +42,11 @@ int rbx_bench_gather_segments(rbx_ctx *ctx, const void *d_table, uint64_t table_
  * bits), out[2] = pb = 64 - bb - fbits (chunk-position bits; 0 when the 16-byte table ran),
  * out[3] = commands per chunk.  Tests pin the production packing with it. */
 int rbx_bench_stream_geometry(rbx_ctx *ctx, uint64_t *out);
+/* The path a batch of n >= 2 ranged BITCOUNT / BITPOS queries takes on a string of `len` bytes when its clamped
+ * ranges cover `total` bytes together and `longest` at most, under rbx_tune "bitrange_dir" and
+ * "bitrange_chain_max" as they stand: 0 = each wave walks its range, 1 = the block directory.  The rule
+ * the batch calls themselves apply; no context, no device. */
+int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t longest);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -102,6 +107,14 @@ int rbx_bench_stream_geometry(rbx_ctx *ctx, uint64_t *out);
  *   "host_tiny_spin"        1 (default): a one-key host add/contains (k <= 16) spins on its kernel's
  *                           completion word in the pinned block (2 ms, then a stream sync);
  *                           0: a stream sync
+ *   "bitrange_dir"          batches of ranged BITCOUNT / BITPOS (n >= 2) through a per-call directory of 4 KiB
+ *                           block counts: 0 never (each wave walks its range), 1 always, 2 auto (default:
+ *                           the ranges cover more bytes than the string + 8 KiB per query, or the
+ *                           longest exceeds bitrange_chain_max)
+ *   "bitrange_chain_max"    bytes one wave may walk alone before the batch takes the directory
+ *                           (default 128 KiB)
+ *   "bitrange_pos_chunk"    bytes per chunk of the single BITPOS search, a power of two in
+ *                           4 KiB .. 1 MiB (default 256 KiB)
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

@@ -7,7 +7,7 @@ from .client import (BloomHandle, RBitSet, RBloomFilter, RedissonClient, RHyperL
                      bloom_contains_multi, calc_slot, crc16, hll_add_multi, hll_count_each, slot_to_gpu)
 from .codec import ByteArrayCodec, StringCodec
 from .exceptions import (ArithmeticException, DeviceError, IllegalArgumentException, IllegalStateException,
-                         RedisException)
+                         RedisException, UnsupportedOperationException)
 from .keys import Arena, device_keys
 
 Redisson = RedissonClient
@@ -15,6 +15,6 @@ Redisson = RedissonClient
 __all__ = [
     "Arena", "ArithmeticException", "BloomHandle", "bloom_stream", "ByteArrayCodec", "DeviceError", "IllegalArgumentException",
     "IllegalStateException", "RBitSet", "RBloomFilter", "RHyperLogLog", "RedisException", "Redisson", "RedissonClient",
-    "StringCodec", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
+    "StringCodec", "UnsupportedOperationException", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
     "hll_add_multi", "hll_count_each", "slot_to_gpu",
 ]

@@ -73,6 +73,7 @@ RBX_E_TIMEOUT = -10
 
 RBX_BITOP_AND, RBX_BITOP_OR, RBX_BITOP_XOR, RBX_BITOP_NOT = 0, 1, 2, 3
 RBX_FIELD_GET, RBX_FIELD_SET, RBX_FIELD_INCRBY = 0, 1, 2
+RBX_RANGE_BYTE, RBX_RANGE_BIT = 0, 1
 
 # name -> (restype, argtypes); every function declared in include/rbx.h
 SIGNATURES = {
@@ -223,9 +224,18 @@ SIGNATURES = {
     "rbx_bitset_fields": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, u64p, i64p, C.c_uint64, i64p]),
     "rbx_bitset_fields_dev": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp, vp]),
     "rbx_bitset_field_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, i64p]),
+    "rbx_bitset_count_range": (C.c_int, [vp, RbxName, C.c_int64, C.c_int64, C.c_int, u64p]),
+    "rbx_bitset_pos": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, i64p]),
+    "rbx_bitset_count_ranges": (C.c_int, [vp, RbxName, i64p, i64p, C.c_uint64, C.c_int, u64p]),
+    "rbx_bitset_pos_ranges": (C.c_int, [vp, RbxName, C.c_int, i64p, i64p, C.c_uint64, C.c_int, i64p]),
+    "rbx_bitset_count_ranges_dev": (C.c_int, [vp, RbxName, vp, vp, C.c_uint64, C.c_int, vp, vp]),
+    "rbx_bitset_pos_ranges_dev": (C.c_int, [vp, RbxName, C.c_int, vp, vp, C.c_uint64, C.c_int, vp, vp]),
+    "rbx_bitset_count_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.c_int64, C.c_int64, C.c_int, u64p]),
+    "rbx_bitset_pos_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, i64p]),
     "rbx_bench_gather": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     "rbx_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "rbx_bench_stream_geometry": (C.c_int, [vp, u64p]),
+    "rbx_bench_bitrange_path": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

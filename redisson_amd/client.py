@@ -547,6 +547,88 @@ class RBitSet(_Expirable):
         _check(L.lib().rbx_bitset_length(self._client.ctx, nm, C.byref(out)))
         return int(out.value)
 
+    # ---- ranged BITCOUNT / BITPOS: engine extensions, the reference's RBitSet has none of them ----
+    @staticmethod
+    def _unit(unit) -> int:
+        u = unit.upper() if isinstance(unit, str) else unit
+        if u not in ("BYTE", "BIT", L.RBX_RANGE_BYTE, L.RBX_RANGE_BIT):
+            raise IllegalArgumentException("the unit is 'BYTE' or 'BIT'")
+        return L.RBX_RANGE_BIT if u in ("BIT", L.RBX_RANGE_BIT) else L.RBX_RANGE_BYTE
+
+    @staticmethod
+    def _bounds(values, what: str) -> np.ndarray:
+        a = np.asarray(values)
+        if a.size and (a.dtype.kind not in "iu" or (a.dtype == np.uint64 and int(a.max()) >= 1 << 63)):
+            raise IllegalArgumentException(f"range {what} are signed 64-bit integers")
+        return np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+
+    def bitCount(self, start: int | None = None, end: int | None = None, unit="BYTE") -> int:
+        """Engine extension (rbx_bitset_count_range): BITCOUNT name start end [BYTE|BIT], both ends inclusive,
+        negative values counting from the end.  Without arguments it is cardinality()."""
+        if start is None and end is None:
+            return self.cardinality()
+        if start is None or end is None:
+            raise IllegalArgumentException("BITCOUNT takes both start and end, or neither")
+        nm, _keep = self._n()
+        out = C.c_uint64()
+        _check(L.lib().rbx_bitset_count_range(self._client.ctx, nm, self._java(start, 64, "start"),
+                                              self._java(end, 64, "end"), self._unit(unit), C.byref(out)))
+        return int(out.value)
+
+    def bitPos(self, bit, start: int | None = None, end: int | None = None, unit="BYTE") -> int:
+        """Engine extension (rbx_bitset_pos): BITPOS name bit [start [end [BYTE|BIT]]] -> the first position
+        holding `bit` as an absolute bit offset, or -1 (see rbx.h for the string's zero-padded right side)."""
+        if start is None and end is not None:
+            raise IllegalArgumentException("BITPOS takes an end only after a start")
+        nargs = 0 if start is None else (1 if end is None else 2)
+        nm, _keep = self._n()
+        out = C.c_int64()
+        _check(L.lib().rbx_bitset_pos(self._client.ctx, nm, self._java(int(bit), 32, "bit"), nargs,
+                                      self._java(start or 0, 64, "start"), self._java(end or 0, 64, "end"),
+                                      self._unit(unit), C.byref(out)))
+        return int(out.value)
+
+    def countRanges(self, starts, ends, unit="BYTE") -> np.ndarray:
+        """Engine extension (rbx_bitset_count_ranges): one bitCount(starts[i], ends[i], unit) per element, in one
+        call -> uint64 counts."""
+        s, e = self._bounds(starts, "starts"), self._bounds(ends, "ends")
+        if s.size != e.size:
+            raise IllegalArgumentException("one end per start")
+        out = np.zeros(max(s.size, 1), np.uint64)
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_count_ranges(self._client.ctx, nm, s.ctypes.data_as(L.i64p), e.ctypes.data_as(L.i64p),
+                                               s.size, self._unit(unit), out.ctypes.data_as(L.u64p)))
+        return out[: s.size]
+
+    def posRanges(self, bit, starts, ends=None, unit="BYTE") -> np.ndarray:
+        """Engine extension (rbx_bitset_pos_ranges): one bitPos(bit, starts[i], ends[i], unit) per element, in one
+        call -> int64 positions; ends=None makes every query bitPos(bit, starts[i])."""
+        s = self._bounds(starts, "starts")
+        e = None if ends is None else self._bounds(ends, "ends")
+        if e is not None and s.size != e.size:
+            raise IllegalArgumentException("one end per start")
+        out = np.zeros(max(s.size, 1), np.int64)
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_pos_ranges(self._client.ctx, nm, self._java(int(bit), 32, "bit"),
+                                             s.ctypes.data_as(L.i64p), None if e is None else e.ctypes.data_as(L.i64p),
+                                             s.size, self._unit(unit), out.ctypes.data_as(L.i64p)))
+        return out[: s.size]
+
+    def countRangesDev(self, d_starts: int, d_ends: int, n: int, d_out: int, unit="BYTE",
+                       stream: int | None = None) -> None:
+        """Engine extension: countRanges over device arrays, n i64 starts and ends, n u64 counts
+        (rbx_bitset_count_ranges_dev; waits once on the stream)."""
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_count_ranges_dev(self._client.ctx, nm, d_starts, d_ends, int(n), self._unit(unit),
+                                                   d_out, stream))
+
+    def posRangesDev(self, bit, d_starts: int, d_ends: int | None, n: int, d_out: int, unit="BYTE",
+                     stream: int | None = None) -> None:
+        """Engine extension: posRanges over device arrays; d_ends may be None (rbx_bitset_pos_ranges_dev)."""
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_pos_ranges_dev(self._client.ctx, nm, self._java(int(bit), 32, "bit"), d_starts, d_ends,
+                                                 int(n), self._unit(unit), d_out, stream))
+
     def toByteArray(self) -> bytes:
         """:327-334 GET (empty for a missing key)"""
         nm, _keep = self._n()

@@ -1,6 +1,11 @@
 // api_bitset.cpp -- RBitSet over the bitmap keys (M/RedissonBitSet.java): single and batched SETBIT /
-// GETBIT, range fill, BITOP, cardinality / size / length, and the typed fields of BITFIELD.
+// GETBIT, range fill, BITOP, cardinality / size / length, the typed fields of BITFIELD, and the ranged
+// BITCOUNT / BITPOS that Spring Data reaches the same strings with.
+// S/ = redisson-spring-data/redisson-spring-data-31/src/main/java/org/redisson/spring/data/connection/
+#include <cstring>
+
 #include "rbx_ctx.h"
+#include "tunables.h"
 
 namespace rbx {
 
@@ -193,9 +198,185 @@ static int fields_args_check(rbx_ctx *c, rbx_name name, int op, int is_signed, i
     return RBX_OK;
 }
 
+// ---- ranged BITCOUNT / BITPOS (S/RedissonConnection.java:638-646, :2337-2359; rules: rbx_kernels.h) ----
+static int range_unit_check(int unit) {
+    if (unit != RBX_RANGE_BYTE && unit != RBX_RANGE_BIT) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown range unit");
+    return RBX_OK;
+}
+
+// BITPOS's own checks; nargs < 0 = a batch without ends ("bit start")
+static int pos_args_check(int bit, int nargs, int unit) {
+    if (nargs > 2) return fail(RBX_E_ILLEGAL_ARGUMENT, "nargs is 0, 1 or 2");
+    RBX_TRY(range_unit_check(unit));
+    if (bit != 0 && bit != 1) return fail(RBX_E_REDIS, "ERR The bit argument must be 1 or 0.");
+    if (nargs < 2 && unit == RBX_RANGE_BIT) return fail(RBX_E_REDIS, "ERR syntax error");  // a unit needs an end
+    return RBX_OK;
+}
+
+// A query over a string of len bytes: its interval, or false with the reply no kernel is needed for.
+static bool range_interval(bool pos, int64_t start, int64_t end, bool end_given, int unit, uint64_t len, uint64_t *lo,
+                           uint64_t *hi, int64_t *fixed) {
+    *fixed = pos ? -1 : 0;  // the empty range
+    if (!pos) return bits_count_interval(start, end, unit, len, lo, hi);
+    return bits_normalise(start, end_given ? end : (int64_t)len - 1, unit, len, lo, hi);
+}
+
+// n replies that are all 0 or all -1: a missing key, an existing empty string
+static int range_fill(void *out, uint64_t n, int64_t value, bool dev, hipStream_t st) {
+    if (dev) HIP_TRY(hipMemsetAsync(out, value ? 0xFF : 0, n * 8, st));
+    else memset(out, value ? 0xFF : 0, n * 8);
+    return RBX_OK;
+}
+static int64_t missing_reply(bool pos, int bit) { return pos && bit ? -1 : 0; }
+
+// one query over the normalised [lo, hi], its reply to the device word d_out: the grid-wide count, or the
+// chunked search
+static int range_one(rbx_ctx *c, const Bitmap &bm, bool pos, int bit, bool end_given, uint64_t lo, uint64_t hi,
+                     void *d_out, hipStream_t st) {
+    if (!pos) {
+        HIP_TRY(hipMemsetAsync(d_out, 0, 8, st));
+        launch_bits_count_range(bm.d_words, lo, hi, (unsigned long long *)d_out, st);
+    } else {
+        RBX_TRY(c->dev->bits.rng_pos.reserve(kBitsPosStateBytes));
+        HIP_TRY(hipMemsetAsync(c->dev->bits.rng_pos.p, 0xFF, kBitsPosStateBytes, st));
+        launch_bits_pos(bm.d_words, lo, hi, bit, g_tune.bitrange_pos_chunk, c->dev->bits.rng_pos.as<unsigned long long>(),
+                        bits_pos_reply(kBitsNone, bit, end_given, hi), (int64_t *)d_out, st);
+    }
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+// The batch path under the knobs as they stand: true = the block directory.  rbx_bench_bitrange_path shows it.
+static bool ranges_take_directory(uint64_t len, uint64_t n, uint64_t total, uint64_t longest) {
+    const int mode = g_tune.bitrange_dir;
+    return mode == 1 || (mode == 2 && (total > len + n * 8192 || longest > g_tune.bitrange_chain_max));
+}
+
+// n >= 2 queries over a string of len > 0 bytes.  total / longest: the bytes the clamped intervals cover
+// together, and the longest of them.  The walk reads `total` bytes, the directory path len to build the
+// directory and then at most 8 KiB per query: it is taken when that is less, and when one wave would walk more
+// than bitrange_chain_max bytes alone.  The directory lives for this call only: any write would invalidate it.
+static int ranges_run(rbx_ctx *c, const Bitmap &bm, uint64_t len, bool pos, int bit, const int64_t *d_starts,
+                      const int64_t *d_ends, uint64_t n, int unit, void *d_out, uint64_t total, uint64_t longest,
+                      hipStream_t st) {
+    const bool dir = ranges_take_directory(len, n, total, longest);
+    unsigned long long *d_dir = nullptr;
+    if (dir) {
+        RBX_TRY(c->dev->bits.rng_dir.reserve((bits_dir_blocks(len) + 1) * 8));
+        d_dir = c->dev->bits.rng_dir.as<unsigned long long>();
+        launch_bits_directory(bm.d_words, len, d_dir, st);
+    }
+    if (pos) launch_bits_pos_ranges(bm.d_words, len, bit, d_starts, d_ends, n, unit, d_dir, (int64_t *)d_out, st);
+    else launch_bits_count_ranges(bm.d_words, len, d_starts, d_ends, n, unit, d_dir, (uint64_t *)d_out, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+static int ranges_args_check(rbx_ctx *c, rbx_name name, bool pos, int bit, const void *starts, const void *ends,
+                             uint64_t n, int unit, const void *out) {
+    if (!c || bad_name(name) || (n && (!starts || !out || (!pos && !ends)))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return pos ? pos_args_check(bit, ends ? 2 : -1, unit) : range_unit_check(unit);
+}
+
+// a batch over host arrays, n >= 2 (one query goes through the single entry points)
+static int ranges_host(rbx_ctx *c, rbx_name name, bool pos, int bit, const int64_t *starts, const int64_t *ends,
+                       uint64_t n, int unit, void *out) {
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t len;
+    RBX_TRY(bitset_len(c, name, &bm, &len));
+    if (!bm) return range_fill(out, n, missing_reply(pos, bit), false, st);
+    if (len == 0) return range_fill(out, n, pos ? -1 : 0, false, st);
+    uint64_t total = 0, longest = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t b = bits_interval_bytes(starts[i], ends ? ends[i] : (int64_t)len - 1, unit, len, pos);
+        total += b;
+        longest = std::max(longest, b);
+    }
+    BitsetScratch &bs = c->dev->bits;
+    RBX_TRY(bs.rng_args.reserve(n * 16));
+    RBX_TRY(bs.rng_out.reserve(n * 8));
+    int64_t *d_starts = bs.rng_args.as<int64_t>(), *d_ends = ends ? d_starts + n : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_starts, starts, n * 8, hipMemcpyHostToDevice, st));
+    if (ends) HIP_TRY(hipMemcpyAsync(d_ends, ends, n * 8, hipMemcpyHostToDevice, st));
+    RBX_TRY(ranges_run(c, *bm, len, pos, bit, d_starts, d_ends, n, unit, bs.rng_out.p, total, longest, st));
+    HIP_TRY(hipMemcpyAsync(out, bs.rng_out.p, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RBX_OK;
+}
+
+// a batch over device arrays: one wait, for the length word, the work summary and -- n = 1 -- the query itself
+static int ranges_dev(rbx_ctx *c, rbx_name name, bool pos, int bit, const int64_t *d_starts, const int64_t *d_ends,
+                      uint64_t n, int unit, void *d_out, hipStream_t st) {
+    RBX_ENTER(c, st);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name_of(name), &bm));
+    if (!bm) return range_fill(d_out, n, missing_reply(pos, bit), true, st);
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 4;  // count words 4 .. 6
+    unsigned long long *w = c->dev->stage.words();
+    HIP_TRY(hipMemsetAsync(d, 0, 24, st));
+    launch_bits_ranges_summary(d_starts, d_ends, n, unit, pos, bm->d_len, d, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(w, d, 24, hipMemcpyDeviceToHost, st));
+    if (n == 1) {
+        HIP_TRY(hipMemcpyAsync(w + 3, d_starts, 8, hipMemcpyDeviceToHost, st));
+        if (d_ends) HIP_TRY(hipMemcpyAsync(w + 4, d_ends, 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t len = w[0], total = w[1], longest = w[2];
+    if (len == 0) return range_fill(d_out, n, pos ? -1 : 0, true, st);
+    if (n > 1) return ranges_run(c, *bm, len, pos, bit, d_starts, d_ends, n, unit, d_out, total, longest, st);
+    uint64_t lo, hi;
+    int64_t fixed;
+    if (!range_interval(pos, (int64_t)w[3], (int64_t)w[4], d_ends != nullptr, unit, len, &lo, &hi, &fixed))
+        return range_fill(d_out, 1, fixed, true, st);
+    return range_one(c, *bm, pos, bit, d_ends != nullptr, lo, hi, d_out, st);
+}
+
+// one command on the context's stream: its reply in *out
+static int range_single(rbx_ctx *c, rbx_name name, bool pos, int bit, int64_t start, int64_t end, bool end_given,
+                        int unit, int64_t *out) {
+    RBX_ENTER(c, c->stream);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t len, lo, hi;
+    RBX_TRY(bitset_len(c, name, &bm, &len));
+    *out = missing_reply(pos, bit);
+    if (!bm) return RBX_OK;
+    if (!range_interval(pos, start, end, end_given, unit, len, &lo, &hi, out)) return RBX_OK;
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
+    RBX_TRY(range_one(c, *bm, pos, bit, end_given, lo, hi, d, c->stream));
+    int rc;
+    *out = (int64_t)read_dev_u64(c, d, &rc);
+    return rc;
+}
+
+// the two commands over a host string
+static int range_of(const uint8_t *bytes, uint64_t len, int missing, bool pos, int bit, int64_t start, int64_t end,
+                    bool end_given, int unit, int64_t *out) {
+    if (missing) len = 0;
+    uint64_t lo, hi;
+    *out = missing_reply(pos, bit);
+    if (missing || !range_interval(pos, start, end, end_given, unit, len, &lo, &hi, out)) return RBX_OK;
+    uint64_t ones = 0, found = kBitsNone;
+    for (uint64_t p = lo; p <= hi && found == kBitsNone; ++p) {
+        const int b = (bytes[p >> 3] >> (7 - (p & 7))) & 1;
+        ones += b;
+        if (pos && b == bit) found = p;
+    }
+    *out = pos ? bits_pos_reply(found, bit, end_given, hi) : (int64_t)ones;
+    return RBX_OK;
+}
+
 }  // namespace rbx
 
 using namespace rbx;
+
+extern "C" int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t longest) {
+    return ranges_take_directory(len, n, total, longest) ? 1 : 0;
+}
 
 extern "C" {
 
@@ -396,6 +577,64 @@ int rbx_bitset_field_of(const uint8_t *bytes, uint64_t len, int is_signed, int s
     RBX_TRY(field_range_check(offset, size));
     *out = field_of_bytes(bytes, len, is_signed, size, offset);
     return RBX_OK;
+}
+
+int rbx_bitset_count_range(rbx_ctx *c, rbx_name name, int64_t start, int64_t end, int unit, uint64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(range_unit_check(unit));
+    return range_single(c, name, false, 0, start, end, true, unit, (int64_t *)out);
+}
+
+int rbx_bitset_pos(rbx_ctx *c, rbx_name name, int bit, int nargs, int64_t start, int64_t end, int unit, int64_t *out) {
+    if (!c || bad_name(name) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (nargs < 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "nargs is 0, 1 or 2");
+    RBX_TRY(pos_args_check(bit, nargs, unit));
+    return range_single(c, name, true, bit, nargs >= 1 ? start : 0, end, nargs == 2, unit, out);
+}
+
+int rbx_bitset_count_ranges(rbx_ctx *c, rbx_name name, const int64_t *starts, const int64_t *ends, uint64_t n, int unit,
+                            uint64_t *out) {
+    RBX_TRY(ranges_args_check(c, name, false, 0, starts, ends, n, unit, out));
+    if (n == 0) return RBX_OK;  // no command is sent
+    if (n == 1) return rbx_bitset_count_range(c, name, starts[0], ends[0], unit, out);
+    return ranges_host(c, name, false, 0, starts, ends, n, unit, out);
+}
+
+int rbx_bitset_pos_ranges(rbx_ctx *c, rbx_name name, int bit, const int64_t *starts, const int64_t *ends, uint64_t n,
+                          int unit, int64_t *out) {
+    RBX_TRY(ranges_args_check(c, name, true, bit, starts, ends, n, unit, out));
+    if (n == 0) return RBX_OK;
+    if (n == 1) return rbx_bitset_pos(c, name, bit, ends ? 2 : 1, starts[0], ends ? ends[0] : 0, unit, out);
+    return ranges_host(c, name, true, bit, starts, ends, n, unit, out);
+}
+
+int rbx_bitset_count_ranges_dev(rbx_ctx *c, rbx_name name, const int64_t *d_starts, const int64_t *d_ends, uint64_t n,
+                                int unit, uint64_t *d_out, void *stream) {
+    RBX_TRY(ranges_args_check(c, name, false, 0, d_starts, d_ends, n, unit, d_out));
+    if (n == 0) return RBX_OK;
+    return ranges_dev(c, name, false, 0, d_starts, d_ends, n, unit, d_out, pick_stream(c, stream));
+}
+
+int rbx_bitset_pos_ranges_dev(rbx_ctx *c, rbx_name name, int bit, const int64_t *d_starts, const int64_t *d_ends,
+                              uint64_t n, int unit, int64_t *d_out, void *stream) {
+    RBX_TRY(ranges_args_check(c, name, true, bit, d_starts, d_ends, n, unit, d_out));
+    if (n == 0) return RBX_OK;
+    return ranges_dev(c, name, true, bit, d_starts, d_ends, n, unit, d_out, pick_stream(c, stream));
+}
+
+int rbx_bitset_count_of(const uint8_t *bytes, uint64_t len, int missing, int64_t start, int64_t end, int unit,
+                        uint64_t *out) {
+    if ((len && !bytes) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(range_unit_check(unit));
+    return range_of(bytes, len, missing, false, 0, start, end, true, unit, (int64_t *)out);
+}
+
+int rbx_bitset_pos_of(const uint8_t *bytes, uint64_t len, int missing, int bit, int nargs, int64_t start, int64_t end,
+                      int unit, int64_t *out) {
+    if ((len && !bytes) || !out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (nargs < 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "nargs is 0, 1 or 2");
+    RBX_TRY(pos_args_check(bit, nargs, unit));
+    return range_of(bytes, len, missing, true, bit, nargs >= 1 ? start : 0, end, nargs == 2, unit, out);
 }
 
 int rbx_bitset_field(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, uint64_t offset, int64_t value,

@@ -256,17 +256,20 @@ static uint64_t mix64_host(uint64_t x) {
 // ---- rbx_tune: one row per key (include/rbx_bench.h documents them) --------------------------------
 struct TuneRow {
     const char *key;
-    enum Kind { kRange, kOneOf, kBits } kind;  // v = {lo, hi} | the n values | {mask of the bits}
+    enum Kind { kRange, kOneOf, kBits, kPow2 } kind;  // v = {lo, hi} | the n values | {mask of the bits} | {lo, hi}
     int v[7], n;
     bool diag;            // exists only in the profiling build (kDiag, librbx_diag.so)
     void (*store)(int);   // a field of g_tune, or a set_* function of rbx_kernels.h
     bool accepts(int x) const {
         if (kind == kRange) return x >= v[0] && x <= v[1];
+        if (kind == kPow2) return x >= v[0] && x <= v[1] && (x & (x - 1)) == 0;
         if (kind == kBits) return (x & ~v[0]) == 0;
         return std::find(v, v + n, x) != v + n;
     }
     std::string wants() const {  // the tail of the rejection message
-        if (kind == kRange) return " in [" + std::to_string(v[0]) + ", " + std::to_string(v[1]) + "]";
+        if (kind == kRange || kind == kPow2)
+            return std::string(kind == kPow2 ? ": a power of two" : "") + " in [" + std::to_string(v[0]) + ", " +
+                   std::to_string(v[1]) + "]";
         std::string s;
         if (kind == kOneOf)
             for (int i = 0; i < n; ++i) s += (i ? ", " : "") + std::to_string(v[i]);
@@ -279,6 +282,7 @@ struct TuneRow {
 #define RANGE(lo, hi) TuneRow::kRange, {lo, hi}, 2
 #define ONE_OF(...) TuneRow::kOneOf, {__VA_ARGS__}, (int)std::initializer_list<int>{__VA_ARGS__}.size()
 #define BITS(mask) TuneRow::kBits, {mask}, 1
+#define POW2(lo, hi) TuneRow::kPow2, {lo, hi}, 2
 #define FIELD(f) [](int x) { g_tune.f = (decltype(g_tune.f.load()))x; }
 static constexpr int kSegMax = (int)kSegMaxKeys, kIntMax = 0x7fffffff;
 static const TuneRow kTuneRows[] = {
@@ -310,10 +314,14 @@ static const TuneRow kTuneRows[] = {
     {"host_small_batches", RANGE(0, 1), false, FIELD(small_host)},
     {"add_rec_lds_limit", RANGE(0, 7168), false, set_add_rec_lds_limit},
     {"contains_stage1", RANGE(0, 5), false, set_contains_stage1},  // early-exit width of contains (0 = off)
+    {"bitrange_pos_chunk", POW2(4096, 1 << 20), false, FIELD(bitrange_pos_chunk)},
+    {"bitrange_chain_max", RANGE(0, kIntMax), false, FIELD(bitrange_chain_max)},
+    {"bitrange_dir", RANGE(0, 2), false, FIELD(bitrange_dir)},
 };
 #undef RANGE
 #undef ONE_OF
 #undef BITS
+#undef POW2
 #undef FIELD
 
 }  // namespace rbx

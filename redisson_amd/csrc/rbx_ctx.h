@@ -363,6 +363,8 @@ struct HllPool {
 struct BitsetScratch {
     DevBuf idx, bitop_srcs;             // uploaded indexes, the BITOP source table
     DevBuf fld_vals, fld_out, fld_sort;  // BITFIELD: uploaded values, replies, the grouped path's sort scratch
+    DevBuf rng_args, rng_out, rng_dir;   // ranged BITCOUNT / BITPOS batches: starts | ends, replies, the block directory
+    DevBuf rng_pos;                      // the single search's running minimum and chunk ticket
 };
 
 // Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).

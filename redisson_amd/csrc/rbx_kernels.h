@@ -337,6 +337,64 @@ void launch_fields_serial(uint32_t *words, unsigned long long *len, uint64_t cap
 void launch_field_one(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
                       uint64_t offset, int64_t value, int64_t *d_reply, uint64_t new_len, hipStream_t st);
 
+// ---- bitrange_kernels.hip
+// Ranged BITCOUNT / BITPOS ([redis-7.2] bitops.c bitcountCommand / bitposCommand as DESIGN §11.2 restates
+// them).  The reply rules are host and device code: single calls and the host-string forms apply them on the
+// host, the batch kernels in their query prologue.  unit: RBX_RANGE_BYTE (0) or RBX_RANGE_BIT of rbx.h.
+constexpr unsigned long long kBitsNone = 1ULL << 40;  // "no such bit": above every bit position
+// Normalise(start, end) over a string of len bytes: the bit interval [*lo, *hi], or false = empty
+RBX_HD bool bits_normalise(int64_t start, int64_t end, int unit, uint64_t len, uint64_t *lo, uint64_t *hi) {
+    const int64_t t = (int64_t)(unit ? len * 8 : len);
+    if (start < 0) start += t;
+    if (end < 0) end += t;
+    if (start < 0) start = 0;
+    if (end < 0) end = 0;
+    if (end > t - 1) end = t - 1;
+    if (start > end) return false;
+    *lo = unit ? (uint64_t)start : (uint64_t)start * 8;
+    *hi = unit ? (uint64_t)end : (uint64_t)end * 8 + 7;
+    return true;
+}
+// BITCOUNT's interval: "start < 0 && end < 0 && start > end" answers 0 before anything is normalised
+RBX_HD bool bits_count_interval(int64_t start, int64_t end, int unit, uint64_t len, uint64_t *lo, uint64_t *hi) {
+    if (start < 0 && end < 0 && start > end) return false;
+    return bits_normalise(start, end, unit, len, lo, hi);
+}
+// BITPOS's reply over a non-empty interval ending at hi; found >= kBitsNone = no position holds the bit: -1,
+// but hi + 1 for a clear bit when no end was given (the string counts as zero-padded on the right)
+RBX_HD int64_t bits_pos_reply(uint64_t found, int bit, bool end_given, uint64_t hi) {
+    if (found < kBitsNone) return (int64_t)found;
+    return (bit || end_given) ? -1 : (int64_t)hi + 1;
+}
+// the bytes a query's clamped interval covers (0 = empty): the batch's work summary adds them up
+RBX_HD uint64_t bits_interval_bytes(int64_t start, int64_t end, int unit, uint64_t len, bool pos) {
+    uint64_t lo, hi;
+    const bool any = pos ? bits_normalise(start, end, unit, len, &lo, &hi) : bits_count_interval(start, end, unit, len, &lo, &hi);
+    return any ? (hi >> 3) - (lo >> 3) + 1 : 0;
+}
+// the directory's 4 KiB blocks over a string of len bytes; the directory holds one more word than that
+RBX_HD uint64_t bits_dir_blocks(uint64_t len) { return (len + 4095) >> 12; }
+// Every interval below is normalised: lo <= hi < 8 * length.
+// *d_out += the ones of [lo, hi] (the caller zeroes it)
+void launch_bits_count_range(const uint32_t *words, uint64_t lo, uint64_t hi, unsigned long long *d_out, hipStream_t st);
+// *d_out = the first position of [lo, hi] holding `bit`, or none_reply.  d_state: kBitsPosStateBytes of scratch
+// that the caller has set to all ones (the running minimum, the chunk ticket, the count of finished
+// workgroups); chunk_bytes: a power of two >= 4096
+constexpr size_t kBitsPosTicketAt = 16, kBitsPosDoneAt = 32, kBitsPosStateBytes = 384;  // u64 indexes: 128 bytes apart
+void launch_bits_pos(const uint32_t *words, uint64_t lo, uint64_t hi, int bit, uint32_t chunk_bytes,
+                     unsigned long long *d_state, int64_t none_reply, int64_t *d_out, hipStream_t st);
+// d_dir[b] = the ones below 4 KiB block b, b = 0 .. bits_dir_blocks(len) (len > 0)
+void launch_bits_directory(const uint32_t *words, uint64_t len, unsigned long long *d_dir, hipStream_t st);
+// d_out3 (zeroed by the caller) = {*d_len, sum of bits_interval_bytes, their maximum}; d_ends nullable (pos)
+void launch_bits_ranges_summary(const int64_t *d_starts, const int64_t *d_ends, uint64_t n, int unit, bool pos,
+                                const unsigned long long *d_len, unsigned long long *d_out3, hipStream_t st);
+// d_out[i] = BITCOUNT / BITPOS reply of query i over a string of len > 0 bytes, one wave per query; d_dir
+// null = walk the interval, else the directory of launch_bits_directory.  pos: d_ends null = "bit start"
+void launch_bits_count_ranges(const uint32_t *words, uint64_t len, const int64_t *d_starts, const int64_t *d_ends,
+                              uint64_t n, int unit, const unsigned long long *d_dir, uint64_t *d_out, hipStream_t st);
+void launch_bits_pos_ranges(const uint32_t *words, uint64_t len, int bit, const int64_t *d_starts, const int64_t *d_ends,
+                            uint64_t n, int unit, const unsigned long long *d_dir, int64_t *d_out, hipStream_t st);
+
 // ---- bench_kernels.hip
 // Roofline probes (api_bench.cpp only).
 // region-local gathers: 6 loads per lane inside XCD-assigned regions (partitioned-probe roofline)

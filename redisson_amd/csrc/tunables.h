@@ -69,6 +69,16 @@ struct Tunables {
     // "stream_table8": 1 (default) the 8-byte first-setter table + walk commit (r04) when (fid, bit) fits
     // 41 bits, 0 the r03 16-byte epoch-tagged table (the fallback past 41 bits; tests)
     std::atomic<int> stream_table8{1};
+
+    // ---- ranged BITCOUNT / BITPOS (api_bitset.cpp) ----
+    // "bitrange_pos_chunk": bytes of a chunk of the single search (k_bits_pos), a power of two in 4 KiB..1 MiB
+    std::atomic<uint32_t> bitrange_pos_chunk{256 << 10};
+    // "bitrange_chain_max": a batch whose longest interval exceeds this many bytes takes the block directory
+    // (the longest walk one wave makes alone on the direct path)
+    std::atomic<uint64_t> bitrange_chain_max{128 << 10};
+    // "bitrange_dir": batches of >= 2 queries through the block directory 0 never, 1 always, 2 (default) by
+    // the read-bytes and chain-length rules (ranges_run)
+    std::atomic<int> bitrange_dir{2};
 };
 
 extern Tunables g_tune;

@@ -21,6 +21,10 @@ class ArithmeticException(RedissonAmdError, ZeroDivisionError):
     """java.lang.ArithmeticException "/ by zero": add/contains of an empty collection (:121, :170)."""
 
 
+class UnsupportedOperationException(RedissonAmdError):
+    """java.lang.UnsupportedOperationException (RedissonConnection.bitOp NOT with several sources)."""
+
+
 class DeviceError(RedissonAmdError):
     """HIP / RCCL failure inside librbx.so."""
 

@@ -1,9 +1,14 @@
-"""Spring Data Redis connection surface for HyperLogLog (second caller of the HLL path).
+"""Spring Data Redis connection surface: HyperLogLog (second caller of the HLL path) and the bit commands
+on strings (second caller of the RBitSet path).
 
 Mirrors redisson-spring-data's RedissonConnection.pfAdd / pfCount / pfMerge
 (redisson-spring-data/redisson-spring-data-32/src/main/java/org/redisson/spring/data/connection/
 RedissonConnection.java:2200-2226): raw byte[] keys and members, no codec (ByteArrayCodec /
 StringCodec pass the bytes through), PFADD's integer reply as a Long.
+
+The bit commands mirror redisson-spring-data-31's RedissonConnection (S/ = redisson-spring-data/
+redisson-spring-data-31/src/main/java/org/redisson/spring/data/connection/RedissonConnection.java): getBit /
+setBit S:628-636, bitCount S:638-646, bitOp S:650-661, strLen S:663-666, bitPos S:2337-2359.
 
 Keys are binary-safe: they travel as (bytes, length) pairs through the *_n entry points
 (rbx_hll_add_multi_n / rbx_hll_count_n / rbx_hll_merge_n), so a key may hold any byte, zero
@@ -17,7 +22,7 @@ import numpy as np
 
 from . import _lib as L
 from .client import RedissonClient, _check
-from .exceptions import IllegalArgumentException
+from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
 
 
@@ -57,3 +62,67 @@ class RedissonConnection:
         srcs, keep = L.names_array([_key(k) for k in sourceKeys])
         dest, keep_d = L.name_struct(_key(destinationKey))
         _check(L.lib().rbx_hll_merge_n(self._client.ctx, dest, srcs, len(sourceKeys)))
+
+    # ---- bit commands on strings (rbx_bitset_*, binary names) ---------------------------------
+    def getBit(self, key: bytes, offset: int) -> bool:
+        """GETBIT key offset  S:628-631"""
+        nm, _keep = L.name_struct(_key(key))
+        bit = C.c_int()
+        _check(L.lib().rbx_bitset_get(self._client.ctx, nm, int(offset), C.byref(bit)))
+        return bool(bit.value)
+
+    def setBit(self, key: bytes, offset: int, value: bool) -> bool:
+        """SETBIT key offset value -> the bit before  S:633-636"""
+        nm, _keep = L.name_struct(_key(key))
+        old = C.c_int()
+        _check(L.lib().rbx_bitset_set(self._client.ctx, nm, int(offset), int(bool(value)), C.byref(old)))
+        return bool(old.value)
+
+    def bitCount(self, key: bytes, begin: int | None = None, end: int | None = None) -> int:
+        """BITCOUNT key  S:638-641, BITCOUNT key begin end  S:643-646 (bytes, both inclusive)"""
+        nm, _keep = L.name_struct(_key(key))
+        out = C.c_uint64()
+        if begin is None and end is None:
+            _check(L.lib().rbx_bitset_cardinality(self._client.ctx, nm, C.byref(out)))
+        elif begin is None or end is None:
+            raise IllegalArgumentException("bitCount takes both begin and end, or neither")
+        else:
+            _check(L.lib().rbx_bitset_count_range(self._client.ctx, nm, int(begin), int(end), L.RBX_RANGE_BYTE,
+                                                  C.byref(out)))
+        return int(out.value)
+
+    def bitOp(self, op, destination: bytes, *keys: bytes) -> int:
+        """BITOP op destination k1..kn -> the result's length  S:650-661.  op: AND / OR / XOR / NOT (a name or
+        an RBX_BITOP_* value).  NOT with more than one source fails before any command is sent (S:652-654)."""
+        ops = {"AND": L.RBX_BITOP_AND, "OR": L.RBX_BITOP_OR, "XOR": L.RBX_BITOP_XOR, "NOT": L.RBX_BITOP_NOT}
+        code = ops.get(op.upper()) if isinstance(op, str) else (op if op in ops.values() else None)
+        if code is None:
+            raise IllegalArgumentException(f"unknown BITOP operation {op!r}")
+        if code == L.RBX_BITOP_NOT and len(keys) > 1:
+            raise UnsupportedOperationException("NOT operation doesn't support more than single source key")
+        dest, _keep_d = L.name_struct(_key(destination))
+        srcs, _keep = L.names_array([_key(k) for k in keys])
+        out = C.c_uint64()
+        _check(L.lib().rbx_bitset_op(self._client.ctx, code, dest, srcs, len(keys), C.byref(out)))
+        return int(out.value)
+
+    def strLen(self, key: bytes) -> int:
+        """STRLEN key  S:663-666"""
+        nm, _keep = L.name_struct(_key(key))
+        out = C.c_uint64()
+        _check(L.lib().rbx_bitset_size(self._client.ctx, nm, C.byref(out)))
+        return int(out.value) // 8
+
+    def bitPos(self, key: bytes, bit: bool, range=(None, None)) -> int:
+        """BITPOS key bit [lower [upper]]  S:2337-2359.  range = (lower, upper), each an int or None
+        (Range.unbounded()).  As in the reference the upper bound is sent only when the lower one is bounded
+        (S:2351-2356): (None, 5) is BITPOS key bit."""
+        if range is None:
+            raise IllegalArgumentException("Range must not be null! Use Range.unbounded() instead.")
+        lower, upper = range
+        nargs = 0 if lower is None else (1 if upper is None else 2)
+        nm, _keep = L.name_struct(_key(key))
+        out = C.c_int64()
+        _check(L.lib().rbx_bitset_pos(self._client.ctx, nm, int(bool(bit)), nargs, int(lower or 0),
+                                      int(upper or 0) if nargs == 2 else 0, L.RBX_RANGE_BYTE, C.byref(out)))
+        return int(out.value)
