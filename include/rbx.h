@@ -258,7 +258,8 @@ int rbx_bitset_rename(rbx_ctx *ctx, rbx_name name, rbx_name new_name);
 /* getSigned / setSigned / incrementAndGetSigned, the Unsigned three, and the Byte / Short / Integer /
  * Long forms (i8 / i16 / i32 / i64) -- M/RedissonBitSet.java:71-254: each is one
  * BITFIELD name GET|SET|INCRBY <i|u><size> <offset> [value] with the default OVERFLOW WRAP
- * ([redis-7.2] bitops.c bitfieldGeneric).
+ * ([redis-7.2] bitops.c bitfieldGeneric).  OVERFLOW SAT / FAIL and lists of mixed sub-commands:
+ * rbx_bitset_fields_ov, rbx_bitset_bitfield and rbx_bitset_field_rule, after these entries.
  *   Layout  the field is `size` bits from bit `offset`, the bit at `offset` its most significant;
  *           `offset` is a plain bit offset, fields need not be aligned (an i64 at offset 2 covers 9 bytes).
  *   Types   is_signed: sizes 1..64, else 1..63.  A larger size is RBX_E_ILLEGAL_ARGUMENT ("Size can't
@@ -299,6 +300,60 @@ int rbx_bitset_fields_dev(rbx_ctx *ctx, rbx_name name, int op, int is_signed, in
                           const int64_t *d_values, uint64_t n, int64_t *d_replies, void *stream);
 /* GET over a host string, no context (as rbx_bitset_length_of) */
 int rbx_bitset_field_of(const uint8_t *bytes, uint64_t len, int is_signed, int size, uint64_t offset, int64_t *out);
+/* BITFIELD's OVERFLOW WRAP | SAT | FAIL, and the one bit command of Spring Data's RedissonConnection that the
+ * entries above cannot express: bitField(key, subCommands) S:2241-2291 (S/ as below), one BITFIELD whose
+ * sub-commands differ in operation, type and overflow mode.  Restated from [redis-7.2] bitops.c bitfieldGeneric /
+ * checkSignedBitfieldOverflow / checkUnsignedBitfieldOverflow; parity is unpinned, as for the HLL strings.
+ *   Range   a type <i|u><size> holds [lo, hi]: [0, 2^size - 1] unsigned, [-2^(size-1), 2^(size-1) - 1] signed.
+ *   INCRBY  t = old + value, exactly.  In range: the field and the reply are t, in every mode.  Else WRAP keeps
+ *           t mod 2^size (the entries above); SAT makes the field hi when t > hi and lo when t < lo, and replies
+ *           that; FAIL writes nothing and the reply is nil.
+ *   SET     t = value for a signed type; for an unsigned type t = value as an unsigned 64-bit number, so a
+ *           negative value overflows UPWARDS (SAT stores hi).  In range the field becomes t; else as INCRBY.  The
+ *           reply is the old value, or nil under FAIL on overflow.
+ *   GET     ignores the mode.
+ *   nil     n bytes; nil[i] = 1: reply i is nil, the field is untouched and replies[i] = 0.  Required
+ *           (RBX_E_ILLEGAL_ARGUMENT) when a sub-command runs under FAIL and `replies` is given; otherwise
+ *           nullable, and zero-filled when given.
+ *   Growth  the string is sized before the first sub-command runs, for every SET and INCRBY, those that then
+ *           fail included: INCRBY u8 0 300 under FAIL on a missing key leaves the one-byte string 00 and nil.
+ *           GETs grow nothing.
+ *   Checks  every sub-command's mode, type and offset is checked before any runs; a bad one fails the call with
+ *           nothing changed or created.  An unknown mode is RBX_E_ILLEGAL_ARGUMENT; the offset limit is the one
+ *           above (offset + size > 2^32 is RBX_E_REDIS); a key of another type is RBX_E_WRONGTYPE.
+ * rbx_bitset_fields_ov / _dev are rbx_bitset_fields / _dev under one mode; with RBX_OVERFLOW_WRAP they answer
+ * byte for byte as those (same type checks: Redisson's 63 / 64 limits, then Redis's).
+ *   Paths   aligned SAT INCRBY without replies, size a divisor of 64, every increment of one sign (>= 0 or
+ *           <= 0): one compare-and-swap loop per element with the sum clamped in the loop -- saturating sums
+ *           commute under that condition and under no weaker one; an element whose field already sits at the
+ *           bound issues no atomic.  Every other aligned SAT / FAIL batch: the grouped path, each slot's lane
+ *           applying the rule in array order.  Unaligned: one lane, serially.  rbx_tune "bitfield_sat_atomic"
+ *           0 never takes the atomic path; every setting answers the same.  The _dev form still waits once,
+ *           for the check result (now also: whether increments of both signs occur).
+ * rbx_bitset_bitfield takes a host array of sub-commands, each with the mode it runs under (Redis's
+ * OVERFLOW governs the sub-commands that follow it; the caller resolves that).  Types here get Redis's check
+ * only, as S:2241-2291 makes none: u64, i65 and size 0 are RBX_E_REDIS "ERR Invalid bitfield type...".
+ * `replies` is required when a GET is present.  Sub-commands that all share operation, type and mode run as
+ * rbx_bitset_fields_ov; any other list runs on one lane in array order (fields of different sizes may partly
+ * overlap, so the order is total).  n = 0 sends nothing.  There is no _dev form.
+ * rbx_bitset_field_rule is the rule itself on one value, no context (as rbx_bitset_field_of): old must lie in
+ * the type's range; *now = the field after, *reply = the reply (0 when *nil = 1). */
+enum { RBX_OVERFLOW_WRAP = 0, RBX_OVERFLOW_SAT = 1, RBX_OVERFLOW_FAIL = 2 };
+int rbx_bitset_fields_ov(rbx_ctx *ctx, rbx_name name, int op, int is_signed, int size, int overflow,
+                         const uint64_t *offsets, const int64_t *values, uint64_t n, int64_t *replies, uint8_t *nil);
+int rbx_bitset_fields_ov_dev(rbx_ctx *ctx, rbx_name name, int op, int is_signed, int size, int overflow,
+                             const uint64_t *d_offsets, const int64_t *d_values, uint64_t n, int64_t *d_replies,
+                             uint8_t *d_nil, void *stream);
+typedef struct {
+    uint64_t offset; /* a plain bit offset ("#N" is N * size, resolved by the caller) */
+    int64_t value;   /* SET's value, INCRBY's increment; ignored for GET */
+    uint8_t op, is_signed, size, overflow; /* RBX_FIELD_*, 0 / 1, bits, RBX_OVERFLOW_* */
+    uint8_t pad[4];
+} rbx_field_cmd; /* 24 bytes */
+int rbx_bitset_bitfield(rbx_ctx *ctx, rbx_name name, const rbx_field_cmd *cmds, uint64_t n, int64_t *replies,
+                        uint8_t *nil);
+int rbx_bitset_field_rule(int op, int is_signed, int size, int overflow, int64_t old, int64_t value, int64_t *now,
+                          int64_t *reply, int *nil);
 /* BITCOUNT key start end [BYTE|BIT] and BITPOS key bit [start [end [BYTE|BIT]]] -- the two bit commands that
  * Spring Data's RedissonConnection (S/ = redisson-spring-data/redisson-spring-data-31/src/main/java/org/
  * redisson/spring/data/connection/RedissonConnection.java) sends beside the ones above: bitCount(key, begin,

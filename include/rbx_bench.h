@@ -107,6 +107,9 @@ int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t l
  *   "host_tiny_spin"        1 (default): a one-key host add/contains (k <= 16) spins on its kernel's
  *                           completion word in the pinned block (2 ms, then a stream sync);
  *                           0: a stream sync
+ *   "bitfield_sat_atomic"   1 (default): an aligned OVERFLOW SAT INCRBY batch without replies, of a size
+ *                           dividing 64 and increments of one sign, is one compare-and-swap loop per
+ *                           element; 0: such a batch takes the grouped path like every other
  *   "bitrange_dir"          batches of ranged BITCOUNT / BITPOS (n >= 2) through a per-call directory of 4 KiB
  *                           block counts: 0 never (each wave walks its range), 1 always, 2 auto (default:
  *                           the ranges cover more bytes than the string + 8 KiB per query, or the

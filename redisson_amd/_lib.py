@@ -74,6 +74,14 @@ RBX_E_TIMEOUT = -10
 RBX_BITOP_AND, RBX_BITOP_OR, RBX_BITOP_XOR, RBX_BITOP_NOT = 0, 1, 2, 3
 RBX_FIELD_GET, RBX_FIELD_SET, RBX_FIELD_INCRBY = 0, 1, 2
 RBX_RANGE_BYTE, RBX_RANGE_BIT = 0, 1
+RBX_OVERFLOW_WRAP, RBX_OVERFLOW_SAT, RBX_OVERFLOW_FAIL = 0, 1, 2
+
+
+class RbxFieldCmd(C.Structure):
+    """struct rbx_field_cmd {offset, value, op, is_signed, size, overflow, pad[4]}: 24 bytes"""
+
+    _fields_ = [("offset", C.c_uint64), ("value", C.c_int64), ("op", C.c_uint8), ("is_signed", C.c_uint8),
+                ("size", C.c_uint8), ("overflow", C.c_uint8), ("pad", C.c_uint8 * 4)]
 
 # name -> (restype, argtypes); every function declared in include/rbx.h
 SIGNATURES = {
@@ -224,6 +232,13 @@ SIGNATURES = {
     "rbx_bitset_fields": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, u64p, i64p, C.c_uint64, i64p]),
     "rbx_bitset_fields_dev": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp, vp]),
     "rbx_bitset_field_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, i64p]),
+    "rbx_bitset_fields_ov": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, C.c_int, u64p, i64p, C.c_uint64, i64p,
+                                       u8p]),
+    "rbx_bitset_fields_ov_dev": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp, vp,
+                                           vp]),
+    "rbx_bitset_bitfield": (C.c_int, [vp, RbxName, C.POINTER(RbxFieldCmd), C.c_uint64, i64p, u8p]),
+    "rbx_bitset_field_rule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, i64p, i64p,
+                                        C.POINTER(C.c_int)]),
     "rbx_bitset_count_range": (C.c_int, [vp, RbxName, C.c_int64, C.c_int64, C.c_int, u64p]),
     "rbx_bitset_pos": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, i64p]),
     "rbx_bitset_count_ranges": (C.c_int, [vp, RbxName, i64p, i64p, C.c_uint64, C.c_int, u64p]),

@@ -480,34 +480,64 @@ class RBitSet(_Expirable):
             raise IllegalArgumentException("one value per offset")
         return a
 
-    def _fields(self, op: int, signed: bool, size: int, offsets, values, replies: bool):
-        """one BITFIELD of len(offsets) sub-commands of one operation and type (rbx_bitset_fields)"""
+    @staticmethod
+    def _overflow(overflow) -> int:
+        """BITFIELD's OVERFLOW mode: 'WRAP' / 'SAT' / 'FAIL' or an RBX_OVERFLOW_* value"""
+        modes = {"WRAP": L.RBX_OVERFLOW_WRAP, "SAT": L.RBX_OVERFLOW_SAT, "FAIL": L.RBX_OVERFLOW_FAIL}
+        if isinstance(overflow, str):
+            code = modes.get(overflow.upper())
+        else:
+            code = overflow if overflow in modes.values() else None
+        if code is None:
+            raise IllegalArgumentException(f"unknown OVERFLOW mode {overflow!r}")
+        return code
+
+    def _fields(self, op: int, signed: bool, size: int, offsets, values, replies: bool, overflow="WRAP"):
+        """one BITFIELD of len(offsets) sub-commands of one operation and type (rbx_bitset_fields, and
+        rbx_bitset_fields_ov under OVERFLOW SAT / FAIL).  FAIL returns (replies, nil)."""
+        mode = self._overflow(overflow)
         offs = self._indexes(offsets)
         vals = None if values is None else self._values(values, offs.size)
         out = np.zeros(max(offs.size, 1), np.int64) if replies else None
         nm, _keep = self._n()
-        _check(L.lib().rbx_bitset_fields(self._client.ctx, nm, op, int(signed), self._java(size, 32, "size"),
-                                         offs.ctypes.data_as(L.u64p),
-                                         None if vals is None else vals.ctypes.data_as(L.i64p), offs.size,
-                                         None if out is None else out.ctypes.data_as(L.i64p)))
-        return None if out is None else out[: offs.size]
+        args = (offs.ctypes.data_as(L.u64p), None if vals is None else vals.ctypes.data_as(L.i64p), offs.size,
+                None if out is None else out.ctypes.data_as(L.i64p))
+        size = self._java(size, 32, "size")
+        if mode == L.RBX_OVERFLOW_WRAP:
+            _check(L.lib().rbx_bitset_fields(self._client.ctx, nm, op, int(signed), size, *args))
+            return None if out is None else out[: offs.size]
+        nil = np.zeros(max(offs.size, 1), np.uint8)
+        _check(L.lib().rbx_bitset_fields_ov(self._client.ctx, nm, op, int(signed), size, mode, *args,
+                                            nil.ctypes.data_as(L.u8p)))
+        rep = None if out is None else out[: offs.size]
+        return (rep, nil[: offs.size].astype(bool)) if mode == L.RBX_OVERFLOW_FAIL else rep
 
     def getFields(self, size: int, offsets, signed: bool = True) -> np.ndarray:
         """One GET per offset, in one BITFIELD -- engine extension, like getIndexes."""
         return self._fields(L.RBX_FIELD_GET, signed, size, offsets, None, True)
 
-    def setFields(self, size: int, offsets, values, signed: bool = True, replies: bool = True):
-        """One SET per (offset, value), in array order -> the old values (int64), or None."""
-        return self._fields(L.RBX_FIELD_SET, signed, size, offsets, values, replies)
+    def setFields(self, size: int, offsets, values, signed: bool = True, replies: bool = True, overflow="WRAP"):
+        """One SET per (offset, value), in array order -> the old values (int64), or None.  overflow: 'WRAP' /
+        'SAT' / 'FAIL' (rbx.h: OVERFLOW); FAIL returns (replies, nil), nil[i] = reply i is nil (field untouched)."""
+        return self._fields(L.RBX_FIELD_SET, signed, size, offsets, values, replies, overflow)
 
-    def incrementFields(self, size: int, offsets, increments, signed: bool = True, replies: bool = True):
-        """One INCRBY per (offset, increment), in array order -> the new values (int64), or None."""
-        return self._fields(L.RBX_FIELD_INCRBY, signed, size, offsets, increments, replies)
+    def incrementFields(self, size: int, offsets, increments, signed: bool = True, replies: bool = True,
+                        overflow="WRAP"):
+        """One INCRBY per (offset, increment), in array order -> the new values (int64), or None.  overflow as
+        for setFields: SAT makes packed fields saturating counters."""
+        return self._fields(L.RBX_FIELD_INCRBY, signed, size, offsets, increments, replies, overflow)
 
-    def _fields_dev(self, op, signed, size, d_offsets, d_values, n, d_replies, stream) -> None:
+    def _fields_dev(self, op, signed, size, d_offsets, d_values, n, d_replies, stream, overflow="WRAP",
+                    d_nil=None) -> None:
         nm, _keep = self._n()
-        _check(L.lib().rbx_bitset_fields_dev(self._client.ctx, nm, op, int(signed), self._java(size, 32, "size"),
-                                             d_offsets, d_values, int(n), d_replies, stream))
+        mode = self._overflow(overflow)
+        size = self._java(size, 32, "size")
+        if mode == L.RBX_OVERFLOW_WRAP and d_nil is None:
+            _check(L.lib().rbx_bitset_fields_dev(self._client.ctx, nm, op, int(signed), size, d_offsets, d_values,
+                                                 int(n), d_replies, stream))
+        else:
+            _check(L.lib().rbx_bitset_fields_ov_dev(self._client.ctx, nm, op, int(signed), size, mode, d_offsets,
+                                                    d_values, int(n), d_replies, d_nil, stream))
 
     def getFieldsDev(self, size: int, d_offsets: int, n: int, d_replies: int, signed: bool = True,
                      stream: int | None = None) -> None:
@@ -515,15 +545,19 @@ class RBitSet(_Expirable):
         self._fields_dev(L.RBX_FIELD_GET, signed, size, d_offsets, None, n, d_replies, stream)
 
     def setFieldsDev(self, size: int, d_offsets: int, d_values: int, n: int, d_replies: int | None = None,
-                     signed: bool = True, stream: int | None = None) -> None:
-        """setFields over device arrays; d_replies (n i64) may be None."""
-        self._fields_dev(L.RBX_FIELD_SET, signed, size, d_offsets, d_values, n, d_replies, stream)
+                     signed: bool = True, stream: int | None = None, overflow="WRAP", d_nil: int | None = None) -> None:
+        """setFields over device arrays; d_replies (n i64) may be None.  d_nil (n bytes) receives the nil mask;
+        FAIL with d_replies needs it (rbx_bitset_fields_ov_dev)."""
+        self._fields_dev(L.RBX_FIELD_SET, signed, size, d_offsets, d_values, n, d_replies, stream, overflow, d_nil)
 
     def incrementFieldsDev(self, size: int, d_offsets: int, d_increments: int, n: int, d_replies: int | None = None,
-                           signed: bool = True, stream: int | None = None) -> None:
+                           signed: bool = True, stream: int | None = None, overflow="WRAP",
+                           d_nil: int | None = None) -> None:
         """incrementFields over device arrays; without d_replies an aligned batch of a size dividing 64
-        is one atomic per element (packed counters)."""
-        self._fields_dev(L.RBX_FIELD_INCRBY, signed, size, d_offsets, d_increments, n, d_replies, stream)
+        is one atomic per element (packed counters) -- under WRAP always, under SAT when every increment has
+        one sign (saturating counters).  d_nil as for setFieldsDev."""
+        self._fields_dev(L.RBX_FIELD_INCRBY, signed, size, d_offsets, d_increments, n, d_replies, stream, overflow,
+                         d_nil)
 
     # ---- whole-string reads -----------------------------------------------------------------
     def cardinality(self) -> int:

@@ -7,6 +7,8 @@
 #include "rbx_ctx.h"
 #include "tunables.h"
 
+#include "field_rule.h"  // after rbx_device.h, whose RBX_HD it then uses
+
 namespace rbx {
 
 static constexpr uint64_t kMaxBitOffset = kEngineMaxSize;  // offsets end at 2^32 - 1
@@ -115,13 +117,14 @@ static int bitset_gather(rbx_ctx *c, const std::string &name, const uint64_t *d_
 
 // ---- RBitSet's typed fields: BITFIELD GET / SET / INCRBY (M/RedissonBitSet.java:71-254) -------
 // the type's checks: Redisson's own (:72-73, :99-100), then the one Redis makes
+static const char *const kFieldTypeMsg =
+    "ERR Invalid bitfield type. Use something like i16 u8. Note that u64 is not supported but i64 is.";
+
 static int field_type_check(int op, int is_signed, int size) {
     if (op < RBX_FIELD_GET || op > RBX_FIELD_INCRBY) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITFIELD operation");
     if (is_signed && size > 64) return fail(RBX_E_ILLEGAL_ARGUMENT, "Size can't be greater than 64 bits");
     if (!is_signed && size > 63) return fail(RBX_E_ILLEGAL_ARGUMENT, "Size can't be greater than 63 bits");
-    if (size < 1)
-        return fail(RBX_E_REDIS,
-                    "ERR Invalid bitfield type. Use something like i16 u8. Note that u64 is not supported but i64 is.");
+    if (size < 1) return fail(RBX_E_REDIS, kFieldTypeMsg);
     return RBX_OK;
 }
 
@@ -143,14 +146,24 @@ static int64_t field_of_bytes(const uint8_t *bytes, uint64_t len, int is_signed,
     return (int64_t)v;
 }
 
+static int overflow_check(int mode) {
+    if (mode < RBX_OVERFLOW_WRAP || mode > RBX_OVERFLOW_FAIL)
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown OVERFLOW mode");
+    return RBX_OK;
+}
+
 // A checked batch over device arrays: mx = the largest offset, aligned = every offset is a multiple
-// of size.  GET gathers; an unaligned SET / INCRBY runs serially (partly overlapping fields make
+// of size, one_sign = no two values of opposite signs (looked at for a SAT INCRBY without replies
+// only).  GET gathers; an unaligned SET / INCRBY runs serially (partly overlapping fields make
 // the order total); an aligned INCRBY without replies whose size divides 64 is one atomic loop per
-// element; every other aligned batch is sorted by slot and walked run by run.
-static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed, int size, const uint64_t *d_offs,
-                      const int64_t *d_values, uint64_t n, int64_t *d_replies, uint64_t mx, bool aligned,
-                      hipStream_t st) {
+// element under WRAP, and under SAT when the increments have one sign (saturating sums commute then
+// and only then; FAIL never commutes); every other aligned batch is sorted by slot and walked run by
+// run.  d_nil (nullable) is zeroed here and set by the FAIL kernels.
+static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed, int size, int mode,
+                      const uint64_t *d_offs, const int64_t *d_values, uint64_t n, int64_t *d_replies, uint8_t *d_nil,
+                      uint64_t mx, bool aligned, bool one_sign, hipStream_t st) {
     std::shared_ptr<Bitmap> bm;
+    if (d_nil) HIP_TRY(hipMemsetAsync(d_nil, 0, n, st));
     if (op == RBX_FIELD_GET) {
         RBX_TRY(bitset_find(c, name, &bm));
         if (!bm) {
@@ -163,11 +176,14 @@ static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed
     }
     const uint64_t need = ((mx + size - 1) >> 3) + 1;
     RBX_TRY(bitset_for_write(c, name, need, st, &bm));
+    const bool commutes = op == RBX_FIELD_INCRBY && !d_replies && 64 % size == 0;
     if (!aligned) {
-        launch_fields_serial(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, d_offs, d_values, n, d_replies,
-                             need, st);
-    } else if (op == RBX_FIELD_INCRBY && !d_replies && 64 % size == 0) {
+        launch_fields_serial(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, mode, d_offs, d_values, n,
+                             d_replies, d_nil, need, st);
+    } else if (commutes && mode == RBX_OVERFLOW_WRAP) {
         launch_fields_incr_atomic(bm->d_words, bm->d_len, bm->cap_bytes, d_offs, d_values, n, size, need, st);
+    } else if (commutes && mode == RBX_OVERFLOW_SAT && one_sign && g_tune.bitfield_sat_atomic != 0) {
+        launch_fields_incr_sat(bm->d_words, bm->d_len, bm->cap_bytes, d_offs, d_values, n, size, is_signed, need, st);
     } else {
         // consecutive chunks of at most 2^30 elements, in order (positions are 32-bit inside a chunk)
         const uint64_t kChunk = 1ULL << 30;
@@ -179,9 +195,10 @@ static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed
         RBX_TRY(c->dev->bits.fld_sort.reserve(scratch));
         for (uint64_t i0 = 0; i0 < n; i0 += kChunk) {
             const uint32_t m = (uint32_t)std::min(kChunk, n - i0);
-            e = launch_fields_grouped(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, d_offs + i0,
-                                      d_values + i0, m, d_replies ? d_replies + i0 : nullptr, need, slot_bits,
-                                      c->dev->bits.fld_sort.p, c->dev->bits.fld_sort.cap, st);
+            e = launch_fields_grouped(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, mode, d_offs + i0,
+                                      d_values + i0, m, d_replies ? d_replies + i0 : nullptr,
+                                      d_nil ? d_nil + i0 : nullptr, need, slot_bits, c->dev->bits.fld_sort.p,
+                                      c->dev->bits.fld_sort.cap, st);
             if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
         }
     }
@@ -196,6 +213,71 @@ static int fields_args_check(rbx_ctx *c, rbx_name name, int op, int is_signed, i
     if (n && (!offs || (op != RBX_FIELD_GET && !values) || (op == RBX_FIELD_GET && !replies)))
         return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
     return RBX_OK;
+}
+
+// nil's own rule: required under FAIL when replies are asked for (a nil reply has no other form)
+static int nil_args_check(int op, int mode, uint64_t n, const void *replies, const void *nil) {
+    RBX_TRY(overflow_check(mode));
+    if (n && op != RBX_FIELD_GET && mode == RBX_OVERFLOW_FAIL && replies && !nil)
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "OVERFLOW FAIL with replies needs nil");
+    return RBX_OK;
+}
+
+// the host form of a batch whose arguments are checked: scan, upload, run, read back
+static int fields_host(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, int mode, const uint64_t *offsets,
+                       const int64_t *values, uint64_t n, int64_t *replies, uint8_t *nil) {
+    if (n == 0) return RBX_OK;  // no command is sent
+    uint64_t mx = 0;
+    bool aligned = true;
+    for (uint64_t i = 0; i < n; ++i) {
+        mx = std::max(mx, offsets[i]);
+        aligned &= offsets[i] % (uint64_t)size == 0;
+    }
+    RBX_TRY(field_range_check(mx, size));
+    bool pos = false, neg = false;
+    if (op == RBX_FIELD_INCRBY && mode == RBX_OVERFLOW_SAT && !replies)
+        for (uint64_t i = 0; i < n; ++i) {
+            pos |= values[i] > 0;
+            neg |= values[i] < 0;
+        }
+    RBX_ENTER(c, c->stream);
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.idx.reserve(n * 8));
+    HIP_TRY(hipMemcpyAsync(b.idx.p, offsets, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (op != RBX_FIELD_GET) {
+        RBX_TRY(b.fld_vals.reserve(n * 8));
+        HIP_TRY(hipMemcpyAsync(b.fld_vals.p, values, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (replies) RBX_TRY(b.fld_out.reserve(n * 8));
+    if (nil) RBX_TRY(b.fld_nil.reserve(n));
+    RBX_TRY(fields_run(c, name_of(name), op, is_signed, size, mode, b.idx.as<uint64_t>(), b.fld_vals.as<int64_t>(), n,
+                       replies ? b.fld_out.as<int64_t>() : nullptr, nil ? b.fld_nil.as<uint8_t>() : nullptr, mx, aligned,
+                       !(pos && neg), c->stream));
+    if (replies) HIP_TRY(hipMemcpyAsync(replies, b.fld_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (nil) HIP_TRY(hipMemcpyAsync(nil, b.fld_nil.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+// the device form: one wait on the stream, for the batch's check result -- the largest offset, whether
+// every offset is aligned and, for a SAT INCRBY without replies, whether increments of both signs occur
+static int fields_dev(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, int mode, const uint64_t *d_offsets,
+                      const int64_t *d_values, uint64_t n, int64_t *d_replies, uint8_t *d_nil, void *stream) {
+    if (n == 0) return RBX_OK;
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    RBX_TRY(c->dev->shared.counters.reserve(64));
+    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
+    HIP_TRY(hipMemsetAsync(d, 0, 16, st));
+    const bool signs = op == RBX_FIELD_INCRBY && mode == RBX_OVERFLOW_SAT && !d_replies;
+    launch_fields_check(d_offsets, signs ? d_values : nullptr, n, size, d, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->dev->stage.words(), d, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t mx = c->dev->stage.words()[0], flags = c->dev->stage.words()[1];
+    RBX_TRY(field_range_check(mx, size));
+    return fields_run(c, name_of(name), op, is_signed, size, mode, d_offsets, d_values, n, d_replies, d_nil, mx,
+                      (flags & 1) == 0, (flags & 6) != 6, st);
 }
 
 // ---- ranged BITCOUNT / BITPOS (S/RedissonConnection.java:638-646, :2337-2359; rules: rbx_kernels.h) ----
@@ -674,47 +756,98 @@ int rbx_bitset_field(rbx_ctx *c, rbx_name name, int op, int is_signed, int size,
 int rbx_bitset_fields(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const uint64_t *offsets,
                       const int64_t *values, uint64_t n, int64_t *replies) {
     RBX_TRY(fields_args_check(c, name, op, is_signed, size, offsets, values, n, replies));
-    if (n == 0) return RBX_OK;  // no command is sent
-    uint64_t mx = 0;
-    bool aligned = true;
-    for (uint64_t i = 0; i < n; ++i) {
-        mx = std::max(mx, offsets[i]);
-        aligned &= offsets[i] % (uint64_t)size == 0;
-    }
-    RBX_TRY(field_range_check(mx, size));
-    RBX_ENTER(c, c->stream);
-    RBX_TRY(c->dev->bits.idx.reserve(n * 8));
-    HIP_TRY(hipMemcpyAsync(c->dev->bits.idx.p, offsets, n * 8, hipMemcpyHostToDevice, c->stream));
-    if (op != RBX_FIELD_GET) {
-        RBX_TRY(c->dev->bits.fld_vals.reserve(n * 8));
-        HIP_TRY(hipMemcpyAsync(c->dev->bits.fld_vals.p, values, n * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    if (replies) RBX_TRY(c->dev->bits.fld_out.reserve(n * 8));
-    RBX_TRY(fields_run(c, name_of(name), op, is_signed, size, c->dev->bits.idx.as<uint64_t>(), c->dev->bits.fld_vals.as<int64_t>(), n,
-                       replies ? c->dev->bits.fld_out.as<int64_t>() : nullptr, mx, aligned, c->stream));
-    if (replies) HIP_TRY(hipMemcpyAsync(replies, c->dev->bits.fld_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RBX_OK;
+    return fields_host(c, name, op, is_signed, size, RBX_OVERFLOW_WRAP, offsets, values, n, replies, nullptr);
 }
 
 int rbx_bitset_fields_dev(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, const uint64_t *d_offsets,
                           const int64_t *d_values, uint64_t n, int64_t *d_replies, void *stream) {
     RBX_TRY(fields_args_check(c, name, op, is_signed, size, d_offsets, d_values, n, d_replies));
-    if (n == 0) return RBX_OK;
-    hipStream_t st = pick_stream(c, stream);
-    RBX_ENTER(c, st);
-    // the batch's check result: the largest offset and whether every offset is aligned (one wait)
-    RBX_TRY(c->dev->shared.counters.reserve(64));
-    auto *d = c->dev->shared.counters.as<unsigned long long>() + 1;
-    HIP_TRY(hipMemsetAsync(d, 0, 16, st));
-    launch_fields_check(d_offsets, n, size, d, st);
+    return fields_dev(c, name, op, is_signed, size, RBX_OVERFLOW_WRAP, d_offsets, d_values, n, d_replies, nullptr,
+                      stream);
+}
+
+int rbx_bitset_fields_ov(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, int overflow,
+                         const uint64_t *offsets, const int64_t *values, uint64_t n, int64_t *replies, uint8_t *nil) {
+    RBX_TRY(fields_args_check(c, name, op, is_signed, size, offsets, values, n, replies));
+    RBX_TRY(nil_args_check(op, overflow, n, replies, nil));
+    return fields_host(c, name, op, is_signed, size, overflow, offsets, values, n, replies, nil);
+}
+
+int rbx_bitset_fields_ov_dev(rbx_ctx *c, rbx_name name, int op, int is_signed, int size, int overflow,
+                             const uint64_t *d_offsets, const int64_t *d_values, uint64_t n, int64_t *d_replies,
+                             uint8_t *d_nil, void *stream) {
+    RBX_TRY(fields_args_check(c, name, op, is_signed, size, d_offsets, d_values, n, d_replies));
+    RBX_TRY(nil_args_check(op, overflow, n, d_replies, d_nil));
+    return fields_dev(c, name, op, is_signed, size, overflow, d_offsets, d_values, n, d_replies, d_nil, stream);
+}
+
+int rbx_bitset_bitfield(rbx_ctx *c, rbx_name name, const rbx_field_cmd *cmds, uint64_t n, int64_t *replies,
+                        uint8_t *nil) {
+    if (!c || bad_name(name) || (n && !cmds)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n == 0) return RBX_OK;  // no command is sent
+    // every sub-command's checks before any effect; the growth is that of the writes, failing ones included
+    bool same = true, writes = false, gets = false, fails = false;
+    uint64_t need = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const rbx_field_cmd &k = cmds[i];
+        if (k.op > RBX_FIELD_INCRBY) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITFIELD operation");
+        RBX_TRY(overflow_check(k.overflow));
+        if (k.is_signed > 1) return fail(RBX_E_ILLEGAL_ARGUMENT, "is_signed is 0 or 1");
+        if (k.size < 1 || k.size > (k.is_signed ? 64 : 63)) return fail(RBX_E_REDIS, kFieldTypeMsg);
+        RBX_TRY(field_range_check(k.offset, k.size));
+        same &= k.op == cmds[0].op && k.is_signed == cmds[0].is_signed && k.size == cmds[0].size &&
+                (k.op == RBX_FIELD_GET || k.overflow == cmds[0].overflow);
+        if (k.op == RBX_FIELD_GET) {
+            gets = true;
+        } else {
+            writes = true;
+            fails |= k.overflow == RBX_OVERFLOW_FAIL;
+            need = std::max<uint64_t>(need, ((k.offset + k.size - 1) >> 3) + 1);
+        }
+    }
+    if (gets && !replies) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (fails && replies && !nil) return fail(RBX_E_ILLEGAL_ARGUMENT, "OVERFLOW FAIL with replies needs nil");
+    if (same) {  // one operation, type and mode: the batch paths
+        std::vector<uint64_t> offs(n);
+        std::vector<int64_t> vals(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            offs[i] = cmds[i].offset;
+            vals[i] = cmds[i].value;
+        }
+        return fields_host(c, name, cmds[0].op, cmds[0].is_signed, cmds[0].size, cmds[0].overflow, offs.data(),
+                           vals.data(), n, replies, nil);
+    }
+    RBX_ENTER(c, c->stream);
+    BitsetScratch &b = c->dev->bits;
+    std::shared_ptr<Bitmap> bm;
+    if (writes)
+        RBX_TRY(bitset_for_write(c, name_of(name), need, c->stream, &bm));
+    else
+        RBX_TRY(bitset_find(c, name_of(name), &bm));
+    RBX_TRY(b.fld_cmds.reserve(n * sizeof(rbx_field_cmd)));
+    RBX_TRY(b.fld_out.reserve(n * 8));
+    RBX_TRY(b.fld_nil.reserve(n));
+    HIP_TRY(hipMemcpyAsync(b.fld_cmds.p, cmds, n * sizeof(rbx_field_cmd), hipMemcpyHostToDevice, c->stream));
+    launch_bitfield_serial(bm ? bm->d_words : nullptr, bm ? bm->d_len : nullptr, bm ? bm->cap_bytes : 0,
+                           b.fld_cmds.as<rbx_field_cmd>(), n, b.fld_out.as<int64_t>(), b.fld_nil.as<uint8_t>(), need,
+                           c->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->dev->stage.words(), d, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t mx = c->dev->stage.words()[0];
-    const bool aligned = c->dev->stage.words()[1] == 0;
-    RBX_TRY(field_range_check(mx, size));
-    return fields_run(c, name_of(name), op, is_signed, size, d_offsets, d_values, n, d_replies, mx, aligned, st);
+    if (replies) HIP_TRY(hipMemcpyAsync(replies, b.fld_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (nil) HIP_TRY(hipMemcpyAsync(nil, b.fld_nil.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RBX_OK;
+}
+
+int rbx_bitset_field_rule(int op, int is_signed, int size, int overflow, int64_t old, int64_t value, int64_t *now,
+                          int64_t *reply, int *nil) {
+    if (!now || !reply || !nil) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (op < RBX_FIELD_GET || op > RBX_FIELD_INCRBY) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITFIELD operation");
+    RBX_TRY(overflow_check(overflow));
+    if (size < 1 || size > (is_signed ? 64 : 63)) return fail(RBX_E_REDIS, kFieldTypeMsg);
+    if (field_typed((uint64_t)old, size, is_signed) != old)
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "old is outside the type's range");
+    *nil = field_rule(op, is_signed ? 1 : 0, size, overflow, old, value, now, reply) ? 1 : 0;
+    return RBX_OK;
 }
 
 }  // extern "C"

@@ -317,6 +317,7 @@ static const TuneRow kTuneRows[] = {
     {"bitrange_pos_chunk", POW2(4096, 1 << 20), false, FIELD(bitrange_pos_chunk)},
     {"bitrange_chain_max", RANGE(0, kIntMax), false, FIELD(bitrange_chain_max)},
     {"bitrange_dir", RANGE(0, 2), false, FIELD(bitrange_dir)},
+    {"bitfield_sat_atomic", RANGE(0, 1), false, FIELD(bitfield_sat_atomic)},
 };
 #undef RANGE
 #undef ONE_OF

@@ -363,6 +363,7 @@ struct HllPool {
 struct BitsetScratch {
     DevBuf idx, bitop_srcs;             // uploaded indexes, the BITOP source table
     DevBuf fld_vals, fld_out, fld_sort;  // BITFIELD: uploaded values, replies, the grouped path's sort scratch
+    DevBuf fld_nil, fld_cmds;            // BITFIELD: the nil mask, the uploaded sub-commands of a mixed list
     DevBuf rng_args, rng_out, rng_dir;   // ranged BITCOUNT / BITPOS batches: starts | ends, replies, the block directory
     DevBuf rng_pos;                      // the single search's running minimum and chunk ticket
 };

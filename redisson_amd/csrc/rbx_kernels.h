@@ -7,6 +7,7 @@
 
 #include <type_traits>
 
+#include "../../include/rbx.h"
 #include "rbx_device.h"
 
 namespace rbx {
@@ -313,26 +314,38 @@ void launch_bits_set_one(uint32_t *words, unsigned long long *len, uint64_t bit,
                          hipStream_t st);
 // bitfield_kernels.hip -- BITFIELD GET / SET / INCRBY (RBX_FIELD_* of rbx.h) on fields of one type;
 // `words` / cap_bytes: a bitmap's allocation, which already holds every field written
-// d_out2[0] = max(d_out2[0], max offset), d_out2[1] |= 1 when an offset is no multiple of size
-void launch_fields_check(const uint64_t *d_offs, uint64_t n, int size, unsigned long long *d_out2, hipStream_t st);
+// d_out2[0] = max(d_out2[0], max offset), d_out2[1] |= 1 when an offset is no multiple of size; with
+// d_vals (nullable; k_fields_check_signs) also |= 2 when a value is > 0 and |= 4 when one is < 0
+void launch_fields_check(const uint64_t *d_offs, const int64_t *d_vals, uint64_t n, int size,
+                         unsigned long long *d_out2, hipStream_t st);
 // d_out[i] = GET at d_offs[i], any offsets (bits at or past the allocation read as zero)
 void launch_fields_get(const uint32_t *words, uint64_t cap_bytes, const uint64_t *d_offs, uint64_t n, int size,
                        int is_signed, int64_t *d_out, hipStream_t st);
 // INCRBY without replies; offsets multiples of size, size a divisor of 64; *len = max(*len, new_len)
 void launch_fields_incr_atomic(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, const uint64_t *d_offs,
                                const int64_t *d_incs, uint64_t n, int size, uint64_t new_len, hipStream_t st);
+// the same under OVERFLOW SAT; every increment has one sign (>= 0 or <= 0)
+void launch_fields_incr_sat(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, const uint64_t *d_offs,
+                            const int64_t *d_incs, uint64_t n, int size, int is_signed, uint64_t new_len,
+                            hipStream_t st);
 // SET / INCRBY in array order on offsets that are multiples of size, n <= 2^30: a stable sort by
 // slot (slot_bits = the significant bits of the largest offset / size), then one lane per slot.
-// d_replies nullable.  The scratch size for n elements comes from fields_grouped_scratch_bytes.
+// d_replies nullable.  mode = RBX_OVERFLOW_*; under FAIL d_nil[i] (nullable) = reply i is nil.  The
+// scratch size for n elements comes from fields_grouped_scratch_bytes.
 // Both return 0 or a hipError_t.
 int fields_grouped_scratch_bytes(uint32_t n, int slot_bits, size_t *bytes);
 int launch_fields_grouped(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed,
-                          int size, const uint64_t *d_offs, const int64_t *d_values, uint32_t n, int64_t *d_replies,
-                          uint64_t new_len, int slot_bits, void *d_scratch, size_t scratch_bytes, hipStream_t st);
+                          int size, int mode, const uint64_t *d_offs, const int64_t *d_values, uint32_t n,
+                          int64_t *d_replies, uint8_t *d_nil, uint64_t new_len, int slot_bits, void *d_scratch,
+                          size_t scratch_bytes, hipStream_t st);
 // SET / INCRBY in array order at any offsets, one lane (exact for partly overlapping fields)
 void launch_fields_serial(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
-                          const uint64_t *d_offs, const int64_t *d_values, uint64_t n, int64_t *d_replies,
-                          uint64_t new_len, hipStream_t st);
+                          int mode, const uint64_t *d_offs, const int64_t *d_values, uint64_t n, int64_t *d_replies,
+                          uint8_t *d_nil, uint64_t new_len, hipStream_t st);
+// n sub-commands of any operations, types and modes in array order, one lane; d_replies and d_nil
+// get one entry each.  words = null with cap_bytes = 0 and new_len = 0: a missing key under GETs only
+void launch_bitfield_serial(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, const rbx_field_cmd *d_cmds,
+                            uint64_t n, int64_t *d_replies, uint8_t *d_nil, uint64_t new_len, hipStream_t st);
 // one SET / INCRBY; *d_reply = its reply
 void launch_field_one(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed, int size,
                       uint64_t offset, int64_t value, int64_t *d_reply, uint64_t new_len, hipStream_t st);

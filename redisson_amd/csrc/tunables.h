@@ -79,6 +79,11 @@ struct Tunables {
     // "bitrange_dir": batches of >= 2 queries through the block directory 0 never, 1 always, 2 (default) by
     // the read-bytes and chain-length rules (ranges_run)
     std::atomic<int> bitrange_dir{2};
+
+    // ---- BITFIELD overflow modes (api_bitset.cpp) ----
+    // "bitfield_sat_atomic": 1 (default) = an aligned SAT INCRBY without replies whose size divides 64 and whose
+    // increments have one sign takes k_fields_incr_sat, 0 = the grouped path (tests run both on one input)
+    std::atomic<int> bitfield_sat_atomic{1};
 };
 
 extern Tunables g_tune;

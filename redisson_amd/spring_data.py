@@ -8,7 +8,8 @@ StringCodec pass the bytes through), PFADD's integer reply as a Long.
 
 The bit commands mirror redisson-spring-data-31's RedissonConnection (S/ = redisson-spring-data/
 redisson-spring-data-31/src/main/java/org/redisson/spring/data/connection/RedissonConnection.java): getBit /
-setBit S:628-636, bitCount S:638-646, bitOp S:650-661, strLen S:663-666, bitPos S:2337-2359.
+setBit S:628-636, bitCount S:638-646, bitOp S:650-661, strLen S:663-666, bitField S:2241-2291,
+bitPos S:2337-2359.
 
 Keys are binary-safe: they travel as (bytes, length) pairs through the *_n entry points
 (rbx_hll_add_multi_n / rbx_hll_count_n / rbx_hll_merge_n), so a key may hold any byte, zero
@@ -30,6 +31,68 @@ def _key(k) -> bytes:
     if k is None:
         raise IllegalArgumentException("Keys must not contain 'null'.")
     return bytes(k)
+
+
+# ---- BitFieldSubCommands (org.springframework.data.redis.connection.BitFieldSubCommands) ------------
+class BitFieldType:
+    """BitFieldSubCommands.BitFieldType: INT_8 is BitFieldType(True, 8); asString() is 'i8' (S:2262-2266)"""
+
+    def __init__(self, signed: bool, bits: int):
+        self.signed, self.bits = bool(signed), int(bits)
+
+    def asString(self) -> str:
+        return ("i" if self.signed else "u") + str(self.bits)
+
+    as_string = asString
+
+
+class Offset:
+    """BitFieldSubCommands.Offset: zero_based sends the plain bit offset, otherwise '#N' = N * bits (S:2256-2260)"""
+
+    def __init__(self, value: int, zero_based: bool = True):
+        self.value, self.zero_based = int(value), bool(zero_based)
+
+    def asString(self) -> str:
+        return str(self.value) if self.zero_based else "#" + str(self.value)
+
+    as_string = asString
+
+
+def _offset(offset) -> Offset:
+    return offset if isinstance(offset, Offset) else Offset(offset)
+
+
+class BitFieldGet:
+    def __init__(self, type: BitFieldType, offset):
+        self.type, self.offset = type, _offset(offset)
+
+
+class BitFieldSet:
+    def __init__(self, type: BitFieldType, offset, value: int):
+        self.type, self.offset, self.value = type, _offset(offset), int(value)
+
+
+class BitFieldIncrBy:
+    """overflow: None, 'WRAP', 'SAT' or 'FAIL' (BitFieldIncrBy.Overflow)"""
+
+    def __init__(self, type: BitFieldType, offset, value: int, overflow: str | None = None):
+        self.type, self.offset, self.value = type, _offset(offset), int(value)
+        self.overflow = None if overflow is None else str(overflow).upper()
+        if self.overflow not in (None, "WRAP", "SAT", "FAIL"):
+            raise IllegalArgumentException(f"unknown OVERFLOW mode {overflow!r}")
+
+
+def resolve_overflow(subCommands) -> list:
+    """The OVERFLOW mode each sub-command of bitField runs under, as 'WRAP' / 'SAT' / 'FAIL'.  S:2272-2283
+    appends `OVERFLOW <mode>` AFTER the INCRBY that carries it, and in Redis an OVERFLOW governs the SET /
+    INCRBY sub-commands that FOLLOW it: an INCRBY runs under the mode of the previous INCRBY that carried
+    one (the first under WRAP), and its own mode holds from the next sub-command on.  Needs no library."""
+    mode, out = "WRAP", []
+    for cmd in subCommands:
+        out.append(mode)
+        if isinstance(cmd, BitFieldIncrBy) and cmd.overflow is not None:
+            mode = cmd.overflow
+    return out
 
 
 class RedissonConnection:
@@ -112,6 +175,44 @@ class RedissonConnection:
         out = C.c_uint64()
         _check(L.lib().rbx_bitset_size(self._client.ctx, nm, C.byref(out)))
         return int(out.value) // 8
+
+    def bitField(self, key: bytes, subCommands) -> list:
+        """BITFIELD key sub-commands -> one reply each, None for nil  S:2241-2291.  subCommands: BitFieldGet /
+        BitFieldSet / BitFieldIncrBy in order.  A non-zero-based Offset is sent as '#N' = N * bits
+        (S:2256-2260); the type travels as 'i' | 'u' + bits with no size check of Redisson's own (S:2262-2266),
+        so u64 or i65 is Redis's "ERR Invalid bitfield type".  An INCRBY's overflow is appended after it
+        (S:2272-2283) and so governs the sub-commands that follow (resolve_overflow).  An empty list returns []."""
+        cmds = list(subCommands)
+        if not cmds:
+            return []
+        modes = {"WRAP": L.RBX_OVERFLOW_WRAP, "SAT": L.RBX_OVERFLOW_SAT, "FAIL": L.RBX_OVERFLOW_FAIL}
+        arr = (L.RbxFieldCmd * len(cmds))()
+        for a, cmd, mode in zip(arr, cmds, resolve_overflow(cmds)):
+            if isinstance(cmd, BitFieldGet):
+                a.op = L.RBX_FIELD_GET
+            elif isinstance(cmd, BitFieldSet):
+                a.op = L.RBX_FIELD_SET
+            elif isinstance(cmd, BitFieldIncrBy):
+                a.op = L.RBX_FIELD_INCRBY
+            else:
+                raise IllegalArgumentException(f"unknown BITFIELD sub-command {cmd!r}")
+            bits = cmd.type.bits
+            offset = cmd.offset.value if cmd.offset.zero_based else cmd.offset.value * bits
+            if not -(1 << 63) <= getattr(cmd, "value", 0) < 1 << 63:
+                raise IllegalArgumentException("field values are Java longs")
+            a.offset = offset if 0 <= offset < 1 << 64 else (1 << 64) - 1  # past the limit either way
+            a.value = getattr(cmd, "value", 0)
+            a.is_signed = int(cmd.type.signed)
+            a.size = bits if 0 <= bits <= 255 else 0  # no such type: Redis's error
+            a.overflow = modes[mode]
+        replies = np.zeros(len(cmds), np.int64)
+        nil = np.zeros(len(cmds), np.uint8)
+        nm, _keep = L.name_struct(_key(key))
+        _check(L.lib().rbx_bitset_bitfield(self._client.ctx, nm, arr, len(cmds), replies.ctypes.data_as(L.i64p),
+                                           nil.ctypes.data_as(L.u8p)))
+        return [None if z else int(r) for r, z in zip(replies, nil)]
+
+    bit_field = bitField
 
     def bitPos(self, key: bytes, bit: bool, range=(None, None)) -> int:
         """BITPOS key bit [lower [upper]]  S:2337-2359.  range = (lower, upper), each an int or None

@@ -15,6 +15,19 @@ baseline alternate inside one loop; the median of the repetitions is reported.  
 operation's time over its baseline's (above 1: slower than the baseline).  Writes one JSON document
 (default profiles/bitset/bitfield_bench.json).
 
+--overflow measures OVERFLOW SAT instead, for u4 and u16 counters over the same 128 MiB, each
+row from a freshly imported string, and writes profiles/bitset/bitfield_overflow_bench.json:
+
+  e  SAT +1 on an all-zero string, re-imported before every call, no replies (k_fields_incr_sat; nothing
+     saturates)
+                                     vs WRAP incrementFieldsDev of the same arrays (row a's path)
+  f  SAT +1 on a string whose counters all sit at the maximum (every element a load, no atomic)   vs row e
+  g  SAT with increments of both signs, no replies (the grouped path)
+                                     vs WRAP with replies (the grouped path, row b's)
+
+Row e carries a bound: the baseline's median plus the baseline's own spread (p90 - p10 of its calls); the
+document says whether the operation's median lies within it.  Rows f and g carry none.
+
 --only b runs row b's operation alone, for a kernel trace that splits it into its sort and apply
 parts (rocprofv3 --kernel-trace --stats -- python tools/bitfield_bench.py --only b): the sort is
 k_fields_slots plus rocPRIM's kernels, the apply is k_fields_runs.  --kernel-split SORT_MS APPLY_MS
@@ -43,6 +56,98 @@ SIZE = 16
 SLOTS = NBYTES * 8 // SIZE  # 2^26
 
 
+def overflow_rows(a):
+    """rows e-g: the saturating paths against the wrapping ones, operation and baseline alternating"""
+    client = RedissonClient(0)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0xB17F1E1D)
+    n = a.n
+    names = ("bench:sat", "bench:wrap")
+    sat, wrap = (client.getBitSet(nm) for nm in names)
+
+    bufs = {b: torch.full((NBYTES,), b, dtype=torch.uint8, device="cuda") for b in (0, 0xFF)}
+    torch.cuda.synchronize()
+
+    def fill(nm, byte):
+        assert L.lib().rbx_bloom_import_dev(client.ctx, nm.encode(), bufs[byte].data_ptr(), NBYTES, None) == 0
+        client.synchronize()
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        fn()
+        return time.perf_counter() - t0
+
+    rows = []
+    for size in (4, 16):
+        slots = NBYTES * 8 // size
+        offs = torch.randint(0, slots, (n,), dtype=torch.int64, device="cuda", generator=g) * size
+        ones = torch.ones(n, dtype=torch.int64, device="cuda")
+        signs = torch.randint(0, 2, (n,), dtype=torch.int64, device="cuda", generator=g) * 2 - 1
+        rep = torch.empty(n, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+
+        def run(bs, vals, replies, overflow):
+            bs.incrementFieldsDev(size, offs.data_ptr(), vals.data_ptr(), n, rep.data_ptr() if replies else None,
+                                  signed=False, overflow=overflow)
+            client.synchronize()
+
+        def sat_ones():
+            run(sat, ones, False, "SAT")
+
+        def wrap_ones():
+            run(wrap, ones, False, "WRAP")
+
+        def sat_full():  # the string under bench:wrap here: every counter at its maximum
+            run(wrap, ones, False, "SAT")
+
+        def sat_mixed():
+            run(sat, signs, False, "SAT")
+
+        def wrap_replies():
+            run(wrap, signs, True, "WRAP")
+
+        for row, label, op, base_label, base, start in (
+                ("e", "SAT +1, no replies, all-zero string (atomic)", sat_ones, "WRAP, the same arrays (row a's path)",
+                 wrap_ones, (0, 0)),
+                ("f", "SAT +1, no replies, every counter at its maximum (loads only)", sat_full, "row e", sat_ones,
+                 (0, 0xFF)),
+                ("g", "SAT, both signs, no replies (grouped)", sat_mixed, "WRAP with replies (grouped, row b's path)",
+                 wrap_replies, (0, 0))):
+            fill(names[0], start[0])
+            fill(names[1], start[1])
+            assert sat.size() == 8 * NBYTES and wrap.size() == 8 * NBYTES
+            t_op, t_base = [], []
+            for i in range(a.warmup + a.reps):
+                if row != "g":  # the same arrays every call would saturate the u4 counters by the 15th: start afresh
+                    fill(names[0], 0)
+                x, y = clock(op), clock(base)
+                if i >= a.warmup:
+                    t_op.append(x)
+                    t_base.append(y)
+            m_op, m_base = statistics.median(t_op), statistics.median(t_base)
+            q = statistics.quantiles(t_base, n=10)
+            r = {"row": row, "field": "u%d" % size, "operation": label, "elements": n, "slots": slots,
+                 "call_ms_median": m_op * 1e3, "call_ms_min": min(t_op) * 1e3, "call_ms_max": max(t_op) * 1e3,
+                 "M_elements_per_s": n / m_op / 1e6, "baseline": base_label, "baseline_ms_median": m_base * 1e3,
+                 "baseline_ms_min": min(t_base) * 1e3, "baseline_ms_max": max(t_base) * 1e3,
+                 "baseline_ms_p10": q[0] * 1e3, "baseline_ms_p90": q[-1] * 1e3, "ratio": m_op / m_base, "reps": a.reps}
+            if row == "e":
+                r["bound_ms"] = (m_base + q[-1] - q[0]) * 1e3
+                r["within"] = "yes" if m_op * 1e3 <= r["bound_ms"] else "no"
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    doc = {"bench": "bitfield_overflow", "device": torch.cuda.get_device_name(0),
+           "timing": "host clock, call + stream synchronise", "counter_array_bytes": NBYTES,
+           "bound": "row e: baseline median + (baseline p90 - p10)", "results": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    sat.delete()
+    wrap.delete()
+    client.shutdown()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -50,8 +155,14 @@ def main():
     ap.add_argument("--n", type=int, default=1 << 24, help="elements per batch of rows a-c")
     ap.add_argument("--only", choices=["b"], default=None)
     ap.add_argument("--kernel-split", type=float, nargs=2, metavar=("SORT_MS", "APPLY_MS"), default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bitset", "bitfield_bench.json"))
+    ap.add_argument("--overflow", action="store_true", help="rows e-g (OVERFLOW SAT) instead of rows a-d")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "bitset",
+                             "bitfield_overflow_bench.json" if a.overflow else "bitfield_bench.json")
+    if a.overflow:
+        return overflow_rows(a)
 
     client = RedissonClient(0)
     g = torch.Generator(device="cuda")
