@@ -228,6 +228,36 @@ int rbx_bitset_get_indexes_dev(rbx_ctx *ctx, rbx_name name, const uint64_t *d_in
  * [from, to), in order  :442-454.  from >= to sends nothing.  to > 2^32 applies [from, 2^32) and
  * then returns RBX_E_REDIS (the pipelined-batch rule of RBX_E_REDIS above). */
 int rbx_bitset_set_range(rbx_ctx *ctx, rbx_name name, uint64_t from, uint64_t to, int value);
+/* An ordered stream of GETBIT / SETBIT commands over many keys in one call: what a batch queues through
+ * RBatch.getBitSet(name) (M/RedissonBatch.java:182-184), executes in submission order
+ * (M/command/CommandBatchService.java:115-134,335) and answers in that order (BatchResult.getResponses(),
+ * M/api/BatchResult.java:41); Spring Data reaches the same shape with getBit / setBit between openPipeline()
+ * and closePipeline() (redisson-spring-data-32 RedissonConnection.java:139-160, :629-636).
+ *   Commands  command i is (cmd_key[i], cmd_op[i], cmd_index[i]): an entry of `names`, 0 = GETBIT /
+ *             1 = SETBIT index 0 / 2 = SETBIT index 1, and the bit offset.  Two entries of `names` with equal
+ *             bytes are the same key.
+ *   Result    exactly that of n calls of rbx_bitset_get / rbx_bitset_set in array order: replies[i]
+ *             (nullable array) is the bit for a GETBIT and the bit before for a SETBIT, and a GETBIT sees
+ *             every earlier SETBIT of its key.  A SETBIT grows the string to (index >> 3) + 1 bytes
+ *             whatever it writes, creates a missing key and keeps the key's timeout; a GETBIT creates and
+ *             grows nothing (a missing key, or an index past the end, reads 0).
+ *   Failures  the pipelined-batch rule of RBX_E_REDIS above: a command whose index is >= 2^32
+ *             (RBX_E_REDIS "ERR bit offset is not an integer or out of range") or whose key holds
+ *             another type (RBX_E_WRONGTYPE: a {name}:config hash, an HLL) fails alone.  It changes
+ *             nothing -- a key whose only SETBITs failed is not created -- and its reply is 0xFF;
+ *             every other command takes effect and gets its exact reply.  The call returns the code of the
+ *             first failing command in array order, its message in rbx_last_error().
+ *   Caller    cmd_key[i] >= nkeys, cmd_op[i] > 2 or a NULL array with n > 0 is RBX_E_ILLEGAL_ARGUMENT with
+ *             nothing changed and nothing created.  n = 0 sends nothing.
+ * `names` is host memory in both forms.  The _dev form takes device command arrays and enqueues on
+ * `stream` (NULL: the context's); like rbx_bitset_set_indexes_dev it is an exception to the *_dev
+ * convention: it waits once on the stream, for the batch's summary (the keys to create or grow, the
+ * failed commands and the return code are host decisions). */
+int rbx_bitset_stream(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                      const uint8_t *cmd_op, const uint64_t *cmd_index, uint64_t n, uint8_t *replies);
+int rbx_bitset_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                          const uint8_t *d_cmd_op, const uint64_t *d_cmd_index, uint64_t n, uint8_t *d_replies,
+                          void *stream);
 /* and / or / xor (:362-388) and not (:462-464) = BITOP op dest src_0 .. src_{nsrc-1} ([redis-7.2]
  * bitops.c bitopCommand): the result is as long as the longest source, a shorter source reads as
  * zero past its end and a missing one is the empty string.  dest may be any of the sources

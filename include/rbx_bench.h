@@ -118,6 +118,13 @@ int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t l
  *                           (default 128 KiB)
  *   "bitrange_pos_chunk"    bytes per chunk of the single BITPOS search, a power of two in
  *                           4 KiB .. 1 MiB (default 256 KiB)
+ *   "bitstream_path"        rbx_bitset_stream: 0 auto (default: a batch of GETBITs is one gather, SETBITs of one
+ *                           value without replies one scatter, anything else one lane in array order up to
+ *                           bitstream_serial_max commands and sorted by (key, bit) past it), 1 always the
+ *                           one lane, 2 always the sort; every setting gives the same answers
+ *   "bitstream_serial_max"  the auto rule's largest batch for the one lane (default 64)
+ *   "bitstream_chunk"       commands per chunk of the sorted path, 1 .. 2^30 (default 2^25: 36 bytes of sort
+ *                           scratch per command, 1.125 GiB)
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

@@ -1,10 +1,11 @@
 """redisson_amd -- MI355X-native batched sketch engine for Redisson's probabilistic
 structures (RBloomFilter / RHyperLogLog), behind a C ABI (include/rbx.h, librbx.so).
 
-Host mirror of the reference API: RedissonClient.getBloomFilter / getHyperLogLog / getBitSet.
+Host mirror of the reference API: RedissonClient.getBloomFilter / getHyperLogLog / getBitSet / createBatch.
 """
-from .client import (BloomHandle, RBitSet, RBloomFilter, RedissonClient, RHyperLogLog, bloom_add_multi, bloom_stream,
-                     bloom_contains_multi, calc_slot, crc16, hll_add_multi, hll_count_each, slot_to_gpu)
+from .client import (BatchResult, BloomHandle, RBatch, RBitSet, RBloomFilter, RedissonClient, RHyperLogLog,
+                     bitset_stream, bitset_stream_dev, bloom_add_multi, bloom_stream, bloom_contains_multi, calc_slot,
+                     crc16, hll_add_multi, hll_count_each, slot_to_gpu)
 from .codec import ByteArrayCodec, StringCodec
 from .exceptions import (ArithmeticException, DeviceError, IllegalArgumentException, IllegalStateException,
                          RedisException, UnsupportedOperationException)
@@ -13,8 +14,9 @@ from .keys import Arena, device_keys
 Redisson = RedissonClient
 
 __all__ = [
-    "Arena", "ArithmeticException", "BloomHandle", "bloom_stream", "ByteArrayCodec", "DeviceError", "IllegalArgumentException",
-    "IllegalStateException", "RBitSet", "RBloomFilter", "RHyperLogLog", "RedisException", "Redisson", "RedissonClient",
-    "StringCodec", "UnsupportedOperationException", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
+    "Arena", "ArithmeticException", "BatchResult", "BloomHandle", "bloom_stream", "ByteArrayCodec", "DeviceError",
+    "IllegalArgumentException", "IllegalStateException", "RBatch", "RBitSet", "RBloomFilter", "RHyperLogLog",
+    "RedisException", "Redisson", "RedissonClient", "StringCodec", "UnsupportedOperationException", "bitset_stream",
+    "bitset_stream_dev", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
     "hll_add_multi", "hll_count_each", "slot_to_gpu",
 ]

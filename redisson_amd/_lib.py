@@ -220,6 +220,8 @@ SIGNATURES = {
     "rbx_bitset_set_indexes_dev": (C.c_int, [vp, RbxName, vp, C.c_uint64, C.c_int, vp]),
     "rbx_bitset_get_indexes_dev": (C.c_int, [vp, RbxName, vp, C.c_uint64, vp, vp]),
     "rbx_bitset_set_range": (C.c_int, [vp, RbxName, C.c_uint64, C.c_uint64, C.c_int]),
+    "rbx_bitset_stream": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, u8p, u64p, C.c_uint64, u8p]),
+    "rbx_bitset_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp]),
     "rbx_bitset_op": (C.c_int, [vp, C.c_int, RbxName, C.POINTER(RbxName), C.c_uint32, u64p]),
     "rbx_bitset_cardinality": (C.c_int, [vp, RbxName, u64p]),
     "rbx_bitset_size": (C.c_int, [vp, RbxName, u64p]),

@@ -19,7 +19,8 @@ import numpy as np
 
 from . import _lib as L
 from .codec import DEFAULT_CODEC, Codec
-from .exceptions import IllegalArgumentException, raise_for
+from .exceptions import (IllegalArgumentException, IllegalStateException, RedisException, RedissonAmdError,
+                         raise_for)
 from .keys import Arena, _OneKey
 
 
@@ -61,6 +62,10 @@ class RedissonClient:
         """M/api/RedissonClient.java getBitSet(name)"""
         return RBitSet(self, name)
 
+    def createBatch(self) -> "RBatch":
+        """M/api/RedissonClient.java createBatch()"""
+        return RBatch(self)
+
     def shutdown(self) -> None:
         if self._ctx:
             _check(L.lib().rbx_shutdown(self._ctx))
@@ -75,6 +80,7 @@ class RedissonClient:
     get_bloom_filter = getBloomFilter
     get_hyper_log_log = getHyperLogLog
     get_bit_set = getBitSet
+    create_batch = createBatch
 
     def __enter__(self):
         return self
@@ -758,6 +764,228 @@ class RBitSet(_Expirable):
     increment_fields_dev = incrementFieldsDev
     to_byte_array = toByteArray
     is_exists = isExists
+
+
+# ---- RBatch: queued commands, executed in submission order (M/RedissonBatch.java, M/api/RBatch.java) --------
+GETBIT, SETBIT0, SETBIT1 = 0, 1, 2  # cmd_op of rbx_bitset_stream
+_FAILED_REPLY = 0xFF
+_BIT_OFFSET_LIMIT = 1 << 32
+
+
+def bitset_stream_call(client: RedissonClient, names, cmd_key, cmd_op, cmd_index, replies: bool = True):
+    """rbx_bitset_stream over host arrays without raising: (rc, message, replies).  names: str or bytes keys;
+    replies is a uint8 array (0xFF = that command failed alone) or None when not asked for."""
+    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+    op = np.ascontiguousarray(cmd_op, dtype=np.uint8).reshape(-1)
+    idx = np.ascontiguousarray(cmd_index, dtype=np.uint64).reshape(-1)
+    if not key.size == op.size == idx.size:
+        raise IllegalArgumentException("cmd_key, cmd_op and cmd_index have one entry per command")
+    arr, _keep = L.names_array(names)
+    out = np.zeros(max(key.size, 1), np.uint8) if replies else None
+    rc = L.lib().rbx_bitset_stream(client.ctx, arr, len(names), key.ctypes.data_as(L.u32p), op.ctypes.data_as(L.u8p),
+                                   idx.ctypes.data_as(L.u64p), key.size, out.ctypes.data_as(L.u8p) if replies else None)
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), (out[: key.size] if replies else None)
+
+
+def bitset_stream(client: RedissonClient, names, cmd_key, cmd_op, cmd_index, replies: bool = True):
+    """An ordered stream of GETBIT (0) / SETBIT 0 (1) / SETBIT 1 (2) commands over many keys in one call
+    (rbx_bitset_stream): the replies, in order.  Raises the first failing command's exception after every
+    other command has run."""
+    rc, msg, out = bitset_stream_call(client, names, cmd_key, cmd_op, cmd_index, replies)
+    raise_for(rc, msg)
+    return out
+
+
+def bitset_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmd_op: int, d_cmd_index: int, n: int,
+                      d_replies: int | None = None, stream: int | None = None) -> None:
+    """bitset_stream over device arrays (u32 keys, u8 ops, u64 indexes, u8 replies), enqueued on `stream`."""
+    arr, _keep = L.names_array(names)
+    _check(L.lib().rbx_bitset_stream_dev(client.ctx, arr, len(names), d_cmd_key, d_cmd_op, d_cmd_index, int(n),
+                                         d_replies, stream))
+
+
+class BatchFuture:
+    """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
+    methods), or raises what the command failed with."""
+
+    def __init__(self):
+        self._done, self._value, self._error = False, None, None
+
+    def _set(self, value=None, error=None) -> None:
+        self._done, self._value, self._error = True, value, error
+
+    def isDone(self) -> bool:
+        return self._done
+
+    def get(self):
+        if not self._done:
+            raise IllegalStateException("the batch has not been executed")
+        if self._error is not None:
+            raise self._error
+        return self._value
+
+    is_done = isDone
+
+
+class _Queued:
+    """One queued command: a bit command (name, op, index) that coalesces, or a callable that runs singly."""
+
+    __slots__ = ("name", "op", "index", "fn", "future")
+
+    def __init__(self, name=None, op=None, index=0, fn=None):
+        self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
+
+
+def _bit_index(index) -> int:
+    i = int(index)
+    if i < 0:
+        raise IllegalArgumentException("bit indexes are non-negative integers")
+    return min(i, (1 << 64) - 1)  # past the offset limit either way
+
+
+def _bit_error(q: _Queued) -> RedissonAmdError:
+    """what a bit command that failed alone failed with: the offset is checked first, as in the single calls"""
+    if q.index >= _BIT_OFFSET_LIMIT:
+        return RedisException("ERR bit offset is not an integer or out of range")
+    return RedisException("WRONGTYPE Operation against a key holding the wrong kind of value")
+
+
+def run_queue(queue, stream_call):
+    """Executes queued commands in submission order: every maximal run of consecutive bit commands, over any
+    keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies); every other command
+    runs through its own call at its position.  Each command's future is set; returns (responses, first error)."""
+    first_error = None
+    i = 0
+    while i < len(queue):
+        q = queue[i]
+        if q.op is None:
+            try:
+                q.future._set(q.fn())
+            except RedissonAmdError as e:
+                q.future._set(error=e)
+                first_error = first_error or e
+            i += 1
+            continue
+        j = i
+        while j < len(queue) and queue[j].op is not None:
+            j += 1
+        run = queue[i:j]
+        ids: dict = {}
+        keys = [ids.setdefault(c.name, len(ids)) for c in run]
+        rc, msg, replies = stream_call(list(ids), keys, [c.op for c in run], [c.index for c in run])
+        whole = None  # the run as a whole was refused
+        if rc not in (L.RBX_OK, L.RBX_E_REDIS, L.RBX_E_WRONGTYPE):
+            try:
+                raise_for(rc, msg)
+            except RedissonAmdError as e:
+                whole = e
+        for c, r in zip(run, replies if whole is None else [0] * len(run)):
+            if whole is not None:
+                c.future._set(error=whole)
+            elif int(r) == _FAILED_REPLY:
+                c.future._set(error=_bit_error(c))
+            else:
+                c.future._set(bool(r))
+            first_error = first_error or c.future._error
+        i = j
+    return [None if c.future._error is not None else c.future._value for c in queue], first_error
+
+
+class BatchResult:
+    """M/api/BatchResult.java: the replies in submission order"""
+
+    def __init__(self, responses: list):
+        self._responses = responses
+
+    def getResponses(self) -> list:
+        """:41"""
+        return self._responses
+
+    get_responses = getResponses
+
+
+class RBatchBitSet:
+    """RBatch.getBitSet(name) (M/RedissonBatch.java:182-184): RBitSetAsync, every method queued.  get / set /
+    clearBit of consecutive commands travel together; the others run through RBitSet's own call."""
+
+    def __init__(self, batch: "RBatch", name: str):
+        self._batch, self._name = batch, name
+
+    def _single(self, method: str, *args) -> BatchFuture:
+        bitset = self._batch._bitset(self._name)
+        return self._batch._add(_Queued(fn=lambda: getattr(bitset, method)(*args)))
+
+    def getAsync(self, bitIndex: int) -> BatchFuture:
+        return self._batch._add(_Queued(self._name, GETBIT, _bit_index(bitIndex)))
+
+    def setAsync(self, bitIndex: int, value: bool = True) -> BatchFuture:
+        return self._batch._add(_Queued(self._name, SETBIT1 if value else SETBIT0, _bit_index(bitIndex)))
+
+    def clearBitAsync(self, bitIndex: int) -> BatchFuture:
+        return self.setAsync(bitIndex, False)
+
+    def setRangeAsync(self, fromIndex: int, toIndex: int, value: bool = True) -> BatchFuture:
+        return self._single("setRange", fromIndex, toIndex, value)
+
+    def clearRangeAsync(self, fromIndex: int, toIndex: int) -> BatchFuture:
+        return self._single("clearRange", fromIndex, toIndex)
+
+    def cardinalityAsync(self) -> BatchFuture:
+        return self._single("cardinality")
+
+    def sizeAsync(self) -> BatchFuture:
+        return self._single("size")
+
+    def clearAsync(self) -> BatchFuture:
+        return self._single("clear")
+
+    get_async = getAsync
+    set_async = setAsync
+    clear_bit_async = clearBitAsync
+    set_range_async = setRangeAsync
+    clear_range_async = clearRangeAsync
+    cardinality_async = cardinalityAsync
+    size_async = sizeAsync
+    clear_async = clearAsync
+
+
+class RBatch:
+    """RedissonClient.createBatch() (M/RedissonBatch.java): commands queue across any number of keys, execute()
+    runs them in submission order (M/command/CommandBatchService.java:115-134,335) and returns their replies
+    in that order.  stream_call / bitset replace the engine's calls (tests)."""
+
+    def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None):
+        self._client = client
+        self._stream_call = stream_call or (lambda *a: bitset_stream_call(client, *a))
+        self._bitset = bitset or (lambda name: RBitSet(client, name))
+        self._queue: list = []
+        self._executed = False
+
+    def _add(self, q: _Queued) -> BatchFuture:
+        if self._executed:
+            raise IllegalStateException("Batch already executed!")
+        self._queue.append(q)
+        return q.future
+
+    def getBitSet(self, name: str) -> RBatchBitSet:
+        return RBatchBitSet(self, name)
+
+    def execute(self) -> BatchResult:
+        """Every command runs, the ones after a failed one too; then the first failure is raised."""
+        if self._executed:
+            raise IllegalStateException("Batch already executed!")
+        self._executed = True
+        responses, error = run_queue(self._queue, self._stream_call)
+        if error is not None:
+            raise error
+        return BatchResult(responses)
+
+    def discard(self) -> None:
+        if self._executed:
+            raise IllegalStateException("Batch already executed!")
+        self._queue.clear()
+
+    get_bit_set = getBitSet
 
 
 class BloomHandle:

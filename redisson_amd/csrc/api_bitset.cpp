@@ -452,6 +452,127 @@ static int range_of(const uint8_t *bytes, uint64_t len, int missing, bool pos, i
     return RBX_OK;
 }
 
+// ---- the ordered GETBIT / SETBIT stream over many keys (RBatch.getBitSet, M/RedissonBatch.java:182-184) ----
+static int significant_bits(uint64_t v) {
+    int b = 0;
+    while (v >> b) ++b;
+    return b;
+}
+
+static int stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const void *key, const void *op,
+                             const void *index, uint64_t n) {
+    if (!c || (nkeys && !names) || (n && (!key || !op || !index))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (uint32_t i = 0; i < nkeys; ++i)
+        if (bad_name(names[i])) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
+    // a cell is (key id, index) in 64 bits, one of them the failed commands'
+    if (nkeys > (1u << 31)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes at most 2^31 keys");
+    return RBX_OK;
+}
+
+// A batch of n > 0 commands over device arrays inside the caller's scope on `st`; d_replies nullable.
+// *failed = RBX_OK, or the code of the first command in array order that failed alone (the caller
+// reports it once the replies are where they belong).  Three steps: the summary pass (names resolved
+// once, lookup only; one wait for what the batch needs), the host's decisions (create or grow every
+// written key, build the key table, pick the path), the execution kernels and the lengths.
+static int stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_key, const uint8_t *d_op,
+                      const uint64_t *d_idx, uint64_t n, uint8_t *d_replies, hipStream_t st, int *failed) {
+    *failed = RBX_OK;
+    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys");
+    BitsetScratch &b = c->dev->bits;
+    // equal names are one key, known by its first entry; a key of another type fails its commands
+    std::vector<std::string> nm(nkeys);
+    std::vector<uint8_t> kinfo((size_t)nkeys * 5);  // canonical ids | wrong-type flags
+    uint32_t *canon = (uint32_t *)kinfo.data();
+    uint8_t *wrong = kinfo.data() + (size_t)nkeys * 4;
+    {
+        std::unordered_map<std::string, uint32_t> first;
+        first.reserve(nkeys);
+        for (uint32_t i = 0; i < nkeys; ++i) {
+            nm[i] = name_of(names[i]);
+            canon[i] = first.emplace(nm[i], i).first->second;
+            const Entry *e = canon[i] == i ? c->ks.find(nm[i]) : nullptr;
+            wrong[i] = canon[i] == i ? (uint8_t)(e && e->type != KType::Bitmap) : wrong[canon[i]];
+        }
+    }
+    RBX_TRY(b.bst_keys.reserve(kinfo.size()));
+    HIP_TRY(hipMemcpyAsync(b.bst_keys.p, kinfo.data(), kinfo.size(), hipMemcpyHostToDevice, st));
+    const size_t sum_bytes = (kBsSummaryWords + (size_t)nkeys) * 8;
+    RBX_TRY(b.bst_sum.reserve(sum_bytes));
+    auto *d_sum = b.bst_sum.as<unsigned long long>(), *d_keymax = d_sum + kBsSummaryWords;
+    HIP_TRY(hipMemsetAsync(d_sum, 0xFF, 16, st));
+    HIP_TRY(hipMemsetAsync(d_sum + 2, 0, sum_bytes - 16, st));
+    launch_bitstream_summary(d_key, d_op, d_idx, n, nkeys, b.bst_keys.as<uint32_t>(),
+                             b.bst_keys.as<uint8_t>() + (size_t)nkeys * 4, d_sum, d_keymax, st);
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> sum(kBsSummaryWords + (size_t)nkeys);
+    HIP_TRY(hipMemcpyAsync(sum.data(), d_sum, sum_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the one wait
+    const uint64_t first_oob = sum[kBsFirstOob], first_wrong = sum[kBsFirstWrong];
+    const uint32_t flags = (uint32_t)sum[kBsFlags];
+    if (flags & kBsIllegal) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys, or its op not 0, 1 or 2");
+    const bool has_failed = (first_oob & first_wrong) != ~0ULL;
+    const bool gets = flags & kBsHasGet, sets = flags & (kBsHasSet0 | kBsHasSet1);
+    const bool one_value = (flags & (kBsHasSet0 | kBsHasSet1)) != (kBsHasSet0 | kBsHasSet1);
+
+    // the strings the batch writes, then the table over their final allocations
+    std::vector<BitKey> tab(nkeys);
+    bool writes = false;
+    for (uint32_t i = 0; i < nkeys; ++i) {
+        BitKey &k = tab[i];
+        if (canon[i] != i) {
+            k = tab[canon[i]];
+            continue;
+        }
+        k = BitKey{nullptr, 0, nullptr, wrong[i] ? kBitKeyWrong : 0u, i};
+        if (wrong[i]) continue;
+        std::shared_ptr<Bitmap> bm;
+        const uint64_t mx1 = sum[kBsSummaryWords + i];  // 1 + the key's largest SETBIT index that runs
+        if (mx1) {
+            RBX_TRY(bitset_for_write(c, nm[i], ((mx1 - 1) >> 3) + 1, st, &bm));
+            writes = true;
+        } else {
+            RBX_TRY(bitset_find(c, nm[i], &bm));
+        }
+        if (bm) k = BitKey{bm->d_words, bm->cap_bytes * 8, bm->d_len, 0u, i};
+    }
+    const BitKey *d_tab = b.bst_table.sync(tab, st);
+    if (!d_tab) return b.bst_table.err;
+
+    const int path = g_tune.bitstream_path;
+    if (path == 0 && !sets) {
+        if (d_replies) launch_bitstream_gather(d_tab, d_key, d_idx, n, d_replies, st);
+    } else if (path == 0 && !gets && one_value && !d_replies) {
+        launch_bitstream_scatter(d_tab, d_key, d_idx, n, (flags & kBsHasSet1) != 0, st);
+    } else if (path == 1 || (path == 0 && n <= g_tune.bitstream_serial_max)) {
+        launch_bitstream_serial(d_tab, d_key, d_op, d_idx, n, d_replies, st);
+    } else {
+        // consecutive chunks in order; a cell that spans two of them is read again by the second
+        const uint64_t chunk = g_tune.bitstream_chunk;
+        const int index_bits = std::max(1, significant_bits(sum[kBsMaxIndex]));
+        const int key_bits = significant_bits((uint64_t)nkeys - 1);
+        size_t scratch = 0;
+        int e = bitstream_grouped_scratch_bytes((uint32_t)std::min(n, chunk), index_bits + key_bits + (has_failed ? 1 : 0),
+                                                &scratch);
+        if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        RBX_TRY(b.bst_sort.reserve(scratch));
+        for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
+            const uint32_t m = (uint32_t)std::min(chunk, n - i0);
+            e = launch_bitstream_grouped(d_tab, d_key + i0, d_op + i0, d_idx + i0, m, d_replies ? d_replies + i0 : nullptr,
+                                         index_bits, key_bits, has_failed, b.bst_sort.p, b.bst_sort.cap, st);
+            if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        }
+    }
+    if (writes) launch_bitstream_lengths(d_tab, d_keymax, nkeys, st);
+    HIP_TRY(hipGetLastError());
+    if (has_failed) *failed = first_oob < first_wrong ? RBX_E_REDIS : RBX_E_WRONGTYPE;
+    return RBX_OK;
+}
+
+static int stream_failed(int code) {
+    if (code == RBX_OK) return RBX_OK;
+    return fail(code, code == RBX_E_REDIS ? kBitOffsetMsg : kWrongTypeMsg);
+}
+
 }  // namespace rbx
 
 using namespace rbx;
@@ -541,6 +662,40 @@ int rbx_bitset_get_indexes_dev(rbx_ctx *c, rbx_name name, const uint64_t *d_inde
     uint64_t mx;
     RBX_TRY(max_index_dev(c, d_indexes, n, st, &mx));
     return bitset_gather(c, name_of(name), d_indexes, n, d_out, st);
+}
+
+int rbx_bitset_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                          const uint8_t *d_cmd_op, const uint64_t *d_cmd_index, uint64_t n, uint8_t *d_replies,
+                          void *stream) {
+    RBX_TRY(stream_args_check(c, names, nkeys, d_cmd_key, d_cmd_op, d_cmd_index, n));
+    if (n == 0) return RBX_OK;  // no command is sent
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    int failed;
+    RBX_TRY(stream_run(c, names, nkeys, d_cmd_key, d_cmd_op, d_cmd_index, n, d_replies, st, &failed));
+    return stream_failed(failed);
+}
+
+int rbx_bitset_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key, const uint8_t *cmd_op,
+                      const uint64_t *cmd_index, uint64_t n, uint8_t *replies) {
+    RBX_TRY(stream_args_check(c, names, nkeys, cmd_key, cmd_op, cmd_index, n));
+    if (n == 0) return RBX_OK;
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.bst_cmds.reserve(n * 5));  // keys | ops
+    RBX_TRY(b.idx.reserve(n * 8));
+    if (replies) RBX_TRY(c->dev->stage.out_bytes.reserve(n));
+    uint32_t *d_key = b.bst_cmds.as<uint32_t>();
+    uint8_t *d_op = b.bst_cmds.as<uint8_t>() + n * 4, *d_replies = replies ? c->dev->stage.out_bytes.as<uint8_t>() : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_key, cmd_key, n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_op, cmd_op, n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b.idx.p, cmd_index, n * 8, hipMemcpyHostToDevice, st));
+    int failed;
+    RBX_TRY(stream_run(c, names, nkeys, d_key, d_op, b.idx.as<uint64_t>(), n, d_replies, st, &failed));
+    if (replies) HIP_TRY(hipMemcpyAsync(replies, d_replies, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return stream_failed(failed);
 }
 
 int rbx_bitset_set_range(rbx_ctx *c, rbx_name name, uint64_t from, uint64_t to, int value) {

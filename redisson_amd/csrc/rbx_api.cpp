@@ -318,6 +318,9 @@ static const TuneRow kTuneRows[] = {
     {"bitrange_chain_max", RANGE(0, kIntMax), false, FIELD(bitrange_chain_max)},
     {"bitrange_dir", RANGE(0, 2), false, FIELD(bitrange_dir)},
     {"bitfield_sat_atomic", RANGE(0, 1), false, FIELD(bitfield_sat_atomic)},
+    {"bitstream_path", RANGE(0, 2), false, FIELD(bitstream_path)},
+    {"bitstream_serial_max", RANGE(0, kIntMax), false, FIELD(bitstream_serial_max)},
+    {"bitstream_chunk", RANGE(1, 1 << 30), false, FIELD(bitstream_chunk)},  // positions in a chunk are 32-bit
 };
 #undef RANGE
 #undef ONE_OF

@@ -366,6 +366,10 @@ struct BitsetScratch {
     DevBuf fld_nil, fld_cmds;            // BITFIELD: the nil mask, the uploaded sub-commands of a mixed list
     DevBuf rng_args, rng_out, rng_dir;   // ranged BITCOUNT / BITPOS batches: starts | ends, replies, the block directory
     DevBuf rng_pos;                      // the single search's running minimum and chunk ticket
+    // the GETBIT / SETBIT stream: the host form's uploaded keys | ops, canonical ids | wrong-type flags, the
+    // summary words | per-key maxima, the grouped path's sort scratch, and the key table
+    DevBuf bst_cmds, bst_keys, bst_sum, bst_sort;
+    CachedTable<rbx::BitKey> bst_table;
 };
 
 // Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).

@@ -408,6 +408,52 @@ void launch_bits_count_ranges(const uint32_t *words, uint64_t len, const int64_t
 void launch_bits_pos_ranges(const uint32_t *words, uint64_t len, int bit, const int64_t *d_starts, const int64_t *d_ends,
                             uint64_t n, int unit, const unsigned long long *d_dir, int64_t *d_out, hipStream_t st);
 
+// ---- bitstream_kernels.hip
+// The ordered GETBIT / SETBIT stream over many strings (rbx_bitset_stream).  Commands are
+// (key, op, index) with op 0 = GETBIT, 1 = SETBIT index 0, 2 = SETBIT index 1; a reply is the bit, the bit
+// before, or 0xFF for a command that failed alone.
+// One string of the batch as the kernels see it, one record per entry of `names` (a missing key that is
+// only read: words = len = null, cap_bits = 0, and every bit reads 0).
+struct alignas(32) BitKey {
+    uint32_t *words;
+    uint64_t cap_bits;        // 8 * the allocation's bytes: every SETBIT of the batch lies below it
+    unsigned long long *len;  // device word: Redis string length in bytes
+    uint32_t flags;           // kBitKeyWrong
+    uint32_t canon;           // the first entry of `names` with this entry's bytes (its own index if none is earlier)
+};
+static_assert(sizeof(BitKey) == 32, "one half line");
+constexpr uint32_t kBitKeyWrong = 1;  // the key holds another type: its commands fail
+// the summary words (u64) and the bits of the flags word
+enum { kBsFirstOob = 0, kBsFirstWrong = 1, kBsFlags = 2, kBsMaxIndex = 3, kBsSummaryWords = 4 };
+constexpr uint32_t kBsIllegal = 1, kBsHasGet = 2, kBsHasSet0 = 4, kBsHasSet1 = 8;
+// One pass before anything is written.  d_sum (the caller sets words 0 and 1 to ~0, 2 and 3 to 0):
+// [kBsFirstOob] the first position whose index is >= 2^32, [kBsFirstWrong] the first position on a key
+// with d_wrong set (and an index below 2^32), [kBsFlags] kBsIllegal = some key >= nkeys or op > 2, kBsHas*
+// = the legal commands' operations, [kBsMaxIndex] the largest index of a command that does not fail.
+// d_keymax (nkeys words, zeroed): per canonical key, 1 + its largest SETBIT index among those.
+void launch_bitstream_summary(const uint32_t *d_key, const uint8_t *d_op, const uint64_t *d_idx, uint64_t n,
+                              uint32_t nkeys, const uint32_t *d_canon, const uint8_t *d_wrong,
+                              unsigned long long *d_sum, unsigned long long *d_keymax, hipStream_t st);
+// a batch of GETBITs
+void launch_bitstream_gather(const BitKey *d_tab, const uint32_t *d_key, const uint64_t *d_idx, uint64_t n,
+                             uint8_t *d_replies, hipStream_t st);
+// a batch of SETBITs of one value whose replies are not wanted
+void launch_bitstream_scatter(const BitKey *d_tab, const uint32_t *d_key, const uint64_t *d_idx, uint64_t n, bool value,
+                              hipStream_t st);
+// any batch in array order, one lane; d_replies nullable
+void launch_bitstream_serial(const BitKey *d_tab, const uint32_t *d_key, const uint8_t *d_op, const uint64_t *d_idx,
+                             uint64_t n, uint8_t *d_replies, hipStream_t st);
+// any batch of n <= 2^30 commands: a stable sort by cell = canon << index_bits | index, then one lane per
+// cell.  index_bits: the significant bits of the largest index (1..32); key_bits: those of nkeys - 1 (<= 31);
+// has_failed: some command of the batch fails.  The scratch size comes from bitstream_grouped_scratch_bytes
+// with cell_bits = index_bits + key_bits + has_failed.  Both return 0 or a hipError_t.
+int bitstream_grouped_scratch_bytes(uint32_t n, int cell_bits, size_t *bytes);
+int launch_bitstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const uint8_t *d_op, const uint64_t *d_idx,
+                             uint32_t n, uint8_t *d_replies, int index_bits, int key_bits, bool has_failed,
+                             void *d_scratch, size_t scratch_bytes, hipStream_t st);
+// *len = max(*len, bytes up to the key's largest SETBIT) for every key with an entry in d_keymax
+void launch_bitstream_lengths(const BitKey *d_tab, const unsigned long long *d_keymax, uint32_t nkeys, hipStream_t st);
+
 // ---- bench_kernels.hip
 // Roofline probes (api_bench.cpp only).
 // region-local gathers: 6 loads per lane inside XCD-assigned regions (partitioned-probe roofline)

@@ -84,6 +84,17 @@ struct Tunables {
     // "bitfield_sat_atomic": 1 (default) = an aligned SAT INCRBY without replies whose size divides 64 and whose
     // increments have one sign takes k_fields_incr_sat, 0 = the grouped path (tests run both on one input)
     std::atomic<int> bitfield_sat_atomic{1};
+
+    // ---- the ordered GETBIT / SETBIT stream (api_bitset.cpp) ----
+    // "bitstream_path": 0 (default) = gather for a batch of GETBITs, scatter for SETBITs of one value without
+    // replies, else serial up to bitstream_serial_max commands and grouped past it; 1 = always serial, 2 = always
+    // grouped.  All exact.
+    std::atomic<int> bitstream_path{0};
+    // "bitstream_serial_max": the auto rule's largest batch for the one-lane walk
+    std::atomic<uint64_t> bitstream_serial_max{64};
+    // "bitstream_chunk": commands per chunk of the grouped path (36 bytes of sort scratch per command: 2^25
+    // commands are 1.125 GiB)
+    std::atomic<uint64_t> bitstream_chunk{1 << 25};
 };
 
 extern Tunables g_tune;

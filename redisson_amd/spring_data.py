@@ -18,11 +18,12 @@ bytes included, exactly as a Redis key can.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
 from . import _lib as L
-from .client import RedissonClient, _check
+from .client import GETBIT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued, bitset_stream_call, run_queue
 from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
 
@@ -95,10 +96,58 @@ def resolve_overflow(subCommands) -> list:
     return out
 
 
+def _pipelined(fn=None, *, bit=None):
+    """A command method of RedissonConnection: while a pipeline is open it queues itself and returns None
+    (the result comes back from closePipeline); bit = (key, op, index) of a GETBIT / SETBIT, which travels with
+    its neighbours in one rbx_bitset_stream call."""
+
+    def wrap(f):
+        @functools.wraps(f)
+        def method(self, *args, **kwargs):
+            if self._pipeline is None:
+                return f(self, *args, **kwargs)
+            if bit is not None:
+                key, op, index = bit(*args, **kwargs)
+                self._pipeline.append(_Queued(_key(key), op, _bit_index(index)))
+            else:
+                self._pipeline.append(_Queued(fn=lambda: f(self, *args, **kwargs)))
+            return None
+
+        return method
+
+    return wrap(fn) if fn is not None else wrap
+
+
 class RedissonConnection:
     def __init__(self, client: RedissonClient):
         self._client = client
+        self._pipeline = None  # the queued commands while a pipeline is open
 
+    # ---- pipelining (redisson-spring-data-32 RedissonConnection.java:118-163) ----------------------
+    def isPipelined(self) -> bool:
+        return self._pipeline is not None
+
+    def openPipeline(self) -> None:
+        """:139-143 -- an IN_MEMORY batch: commands queue until closePipeline"""
+        self._pipeline = []
+
+    def closePipeline(self) -> list:
+        """:146-163 -- runs the queued commands in order and returns their results; [] outside a pipeline.
+        Consecutive getBit / setBit commands, over any keys, are one rbx_bitset_stream call.  Every command
+        runs; then the first failure is raised."""
+        if self._pipeline is None:
+            return []
+        queue, self._pipeline = self._pipeline, None
+        results, error = run_queue(queue, lambda *a: bitset_stream_call(self._client, *a))
+        if error is not None:
+            raise error
+        return results
+
+    is_pipelined = isPipelined
+    open_pipeline = openPipeline
+    close_pipeline = closePipeline
+
+    @_pipelined
     def pfAdd(self, key: bytes, *values: bytes) -> int:
         """PFADD key v1..vn -> 1 if the HLL was created or a register changed, else 0."""
         a = Arena([bytes(v) for v in values])
@@ -109,6 +158,7 @@ class RedissonConnection:
                                            ch.ctypes.data_as(L.u8p)))
         return int(ch[0])
 
+    @_pipelined
     def pfCount(self, *keys: bytes) -> int:
         """PFCOUNT k1..kn (union when n > 1)."""
         if not keys:
@@ -120,6 +170,7 @@ class RedissonConnection:
         _check(L.lib().rbx_hll_count_n(self._client.ctx, names, len(keys), C.byref(out)))
         return int(out.value)
 
+    @_pipelined
     def pfMerge(self, destinationKey: bytes, *sourceKeys: bytes) -> None:
         """PFMERGE dest s1..sn (dest's own registers included)."""
         srcs, keep = L.names_array([_key(k) for k in sourceKeys])
@@ -127,6 +178,7 @@ class RedissonConnection:
         _check(L.lib().rbx_hll_merge_n(self._client.ctx, dest, srcs, len(sourceKeys)))
 
     # ---- bit commands on strings (rbx_bitset_*, binary names) ---------------------------------
+    @_pipelined(bit=lambda key, offset: (key, GETBIT, offset))
     def getBit(self, key: bytes, offset: int) -> bool:
         """GETBIT key offset  S:628-631"""
         nm, _keep = L.name_struct(_key(key))
@@ -134,6 +186,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_get(self._client.ctx, nm, int(offset), C.byref(bit)))
         return bool(bit.value)
 
+    @_pipelined(bit=lambda key, offset, value: (key, SETBIT1 if value else SETBIT0, offset))
     def setBit(self, key: bytes, offset: int, value: bool) -> bool:
         """SETBIT key offset value -> the bit before  S:633-636"""
         nm, _keep = L.name_struct(_key(key))
@@ -141,6 +194,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_set(self._client.ctx, nm, int(offset), int(bool(value)), C.byref(old)))
         return bool(old.value)
 
+    @_pipelined
     def bitCount(self, key: bytes, begin: int | None = None, end: int | None = None) -> int:
         """BITCOUNT key  S:638-641, BITCOUNT key begin end  S:643-646 (bytes, both inclusive)"""
         nm, _keep = L.name_struct(_key(key))
@@ -154,6 +208,7 @@ class RedissonConnection:
                                                   C.byref(out)))
         return int(out.value)
 
+    @_pipelined
     def bitOp(self, op, destination: bytes, *keys: bytes) -> int:
         """BITOP op destination k1..kn -> the result's length  S:650-661.  op: AND / OR / XOR / NOT (a name or
         an RBX_BITOP_* value).  NOT with more than one source fails before any command is sent (S:652-654)."""
@@ -169,6 +224,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_op(self._client.ctx, code, dest, srcs, len(keys), C.byref(out)))
         return int(out.value)
 
+    @_pipelined
     def strLen(self, key: bytes) -> int:
         """STRLEN key  S:663-666"""
         nm, _keep = L.name_struct(_key(key))
@@ -176,6 +232,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_size(self._client.ctx, nm, C.byref(out)))
         return int(out.value) // 8
 
+    @_pipelined
     def bitField(self, key: bytes, subCommands) -> list:
         """BITFIELD key sub-commands -> one reply each, None for nil  S:2241-2291.  subCommands: BitFieldGet /
         BitFieldSet / BitFieldIncrBy in order.  A non-zero-based Offset is sent as '#N' = N * bits
@@ -214,6 +271,7 @@ class RedissonConnection:
 
     bit_field = bitField
 
+    @_pipelined
     def bitPos(self, key: bytes, bit: bool, range=(None, None)) -> int:
         """BITPOS key bit [lower [upper]]  S:2337-2359.  range = (lower, upper), each an int or None
         (Range.unbounded()).  As in the reference the upper bound is sent only when the lower one is bounded
