@@ -384,6 +384,46 @@ int rbx_bitset_bitfield(rbx_ctx *ctx, rbx_name name, const rbx_field_cmd *cmds, 
                         uint8_t *nil);
 int rbx_bitset_field_rule(int op, int is_signed, int size, int overflow, int64_t old, int64_t value, int64_t *now,
                           int64_t *reply, int *nil);
+/* An ordered stream of single-sub-command BITFIELDs over many keys in one call: what a batch queues through the
+ * typed-field methods of RBatch.getBitSet(name) (M/api/RBitSetAsync.java:36-206: get / set / incrementAndGet x
+ * Signed, Unsigned, Byte, Short, Integer, Long) and what a Spring Data pipeline of one-sub-command bitField
+ * calls sends -- a few packed counters per user, updated for many users at once.  rbx_bitset_stream's shape
+ * with rbx_bitset_bitfield's commands.
+ *   Commands  command i is BITFIELD names[cmd_key[i]] [OVERFLOW m] GET|SET|INCRBY <i|u><size> <offset> [value],
+ *             written as cmds[i] (`pad` is ignored).  Two entries of `names` with equal bytes are the same key.
+ *   Result    exactly that of n calls of rbx_bitset_bitfield(ctx, name, &cmds[i], 1, ...) in array order:
+ *             replies[i] (nullable array) is what call i returns, and a command sees every earlier write of
+ *             its key.  A SET / INCRBY grows the string to ((offset + size - 1) >> 3) + 1 bytes, also when it
+ *             ends nil under FAIL, creates a missing key, works in place when the allocation suffices and
+ *             keeps the key's timeout; a GET creates and grows nothing.
+ *   status    (nullable array) status[i] = 0: the reply is valid; 1: nil (OVERFLOW FAIL), the field is
+ *             untouched and replies[i] = 0; 0xFF: the command failed alone, replies[i] = 0.  Required
+ *             (RBX_E_ILLEGAL_ARGUMENT) when `replies` is given and a SET / INCRBY that runs is under FAIL --
+ *             rbx_bitset_fields_ov's rule for `nil`.
+ *   Failures  the pipelined-batch rule of RBX_E_REDIS above.  A command fails alone on Redis's type check
+ *             (u64, i65, size 0: RBX_E_REDIS "ERR Invalid bitfield type..."), on the offset limit (offset >=
+ *             2^32 or offset + size > 2^32: RBX_E_REDIS "ERR bit offset..."), or on a key of another type
+ *             (RBX_E_WRONGTYPE), looked at in this order, which is the single call's.  It changes nothing -- a
+ *             key whose only writes failed is not created -- and every other command takes effect with its
+ *             exact reply.  The call returns the code of the first failing command in array order, its
+ *             message in rbx_last_error().
+ *   Caller    cmd_key[i] >= nkeys, an op or overflow mode above 2, is_signed above 1, or a NULL array with
+ *             n > 0 is RBX_E_ILLEGAL_ARGUMENT with nothing changed and nothing created.  n = 0 sends nothing.
+ *   Paths     one summary pass, one wait, then: a batch without SET / INCRBY is one gather; INCRBYs under WRAP
+ *             of one size dividing 64, each at a multiple of it, replies not asked for, are one compare-and-
+ *             swap loop per command (not so for mixed sizes: a u8 inside a u16 does not commute with it); any
+ *             other batch of at most fieldstream_serial_max commands runs on one lane; a longer one is sorted
+ *             by (key, aligned 64-bit word) when every field lies inside one such word -- every mix of the
+ *             Byte / Short / Integer / Long methods at multiples of their sizes does -- with one lane per word,
+ *             and by key otherwise, one lane per key.  One cell repeated n times runs on one lane: not
+ *             bounded.  rbx_tune "fieldstream_path" forces a path; every setting answers the same.
+ * `names` is host memory in both forms.  The _dev form takes device arrays and enqueues on `stream` (NULL: the
+ * context's); like rbx_bitset_stream_dev it waits once on the stream, for the batch's summary. */
+int rbx_bitset_field_stream(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                            const rbx_field_cmd *cmds, uint64_t n, int64_t *replies, uint8_t *status);
+int rbx_bitset_field_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                                const rbx_field_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
+                                void *stream);
 /* BITCOUNT key start end [BYTE|BIT] and BITPOS key bit [start [end [BYTE|BIT]]] -- the two bit commands that
  * Spring Data's RedissonConnection (S/ = redisson-spring-data/redisson-spring-data-31/src/main/java/org/
  * redisson/spring/data/connection/RedissonConnection.java) sends beside the ones above: bitCount(key, begin,

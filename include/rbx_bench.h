@@ -47,6 +47,9 @@ int rbx_bench_stream_geometry(rbx_ctx *ctx, uint64_t *out);
  * "bitrange_chain_max" as they stand: 0 = each wave walks its range, 1 = the block directory.  The rule
  * the batch calls themselves apply; no context, no device. */
 int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t longest);
+/* The execution path the last rbx_bitset_field_stream[_dev] call of this process took: 0 none yet, 1 one lane,
+ * 2 sorted by (key, word), 3 sorted by key, 4 gather, 5 the compare-and-swap loop. */
+int rbx_bench_fieldstream_last_path(void);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -125,6 +128,16 @@ int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t l
  *   "bitstream_serial_max"  the auto rule's largest batch for the one lane (default 64)
  *   "bitstream_chunk"       commands per chunk of the sorted path, 1 .. 2^30 (default 2^25: 36 bytes of sort
  *                           scratch per command, 1.125 GiB)
+ *   "fieldstream_path"      rbx_bitset_field_stream: 0 auto (default: a batch without SET / INCRBY is one gather;
+ *                           WRAP INCRBYs of one size dividing 64, each at a multiple of it, without replies are
+ *                           one compare-and-swap loop per command; anything else runs on one lane in array order
+ *                           up to fieldstream_serial_max commands, past it sorted by (key, 64-bit word) when
+ *                           every field lies inside one aligned word and by key otherwise), 1 always the one
+ *                           lane, 2 always the sort by word (by key when a field straddles two words), 3 always
+ *                           the sort by key; every setting gives the same answers
+ *   "fieldstream_serial_max" the auto rule's largest batch for the one lane (default 64, bitstream_serial_max's
+ *                           value; the crossover is not measured)
+ *   "fieldstream_chunk"     commands per chunk of the sorted paths, 1 .. 2^30 (default 2^25)
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

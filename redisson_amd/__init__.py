@@ -4,7 +4,7 @@ structures (RBloomFilter / RHyperLogLog), behind a C ABI (include/rbx.h, librbx.
 Host mirror of the reference API: RedissonClient.getBloomFilter / getHyperLogLog / getBitSet / createBatch.
 """
 from .client import (BatchResult, BloomHandle, RBatch, RBitSet, RBloomFilter, RedissonClient, RHyperLogLog,
-                     bitset_stream, bitset_stream_dev, bloom_add_multi, bloom_stream, bloom_contains_multi, calc_slot,
+                     bitset_field_stream, bitset_field_stream_dev, bitset_stream, bitset_stream_dev, bloom_add_multi, bloom_stream, bloom_contains_multi, calc_slot,
                      crc16, hll_add_multi, hll_count_each, slot_to_gpu)
 from .codec import ByteArrayCodec, StringCodec
 from .exceptions import (ArithmeticException, DeviceError, IllegalArgumentException, IllegalStateException,
@@ -16,7 +16,7 @@ Redisson = RedissonClient
 __all__ = [
     "Arena", "ArithmeticException", "BatchResult", "BloomHandle", "bloom_stream", "ByteArrayCodec", "DeviceError",
     "IllegalArgumentException", "IllegalStateException", "RBatch", "RBitSet", "RBloomFilter", "RHyperLogLog",
-    "RedisException", "Redisson", "RedissonClient", "StringCodec", "UnsupportedOperationException", "bitset_stream",
-    "bitset_stream_dev", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
+    "RedisException", "Redisson", "RedissonClient", "StringCodec", "UnsupportedOperationException",
+    "bitset_field_stream", "bitset_field_stream_dev", "bitset_stream", "bitset_stream_dev", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
     "hll_add_multi", "hll_count_each", "slot_to_gpu",
 ]

@@ -239,6 +239,9 @@ SIGNATURES = {
     "rbx_bitset_fields_ov_dev": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp, vp,
                                            vp]),
     "rbx_bitset_bitfield": (C.c_int, [vp, RbxName, C.POINTER(RbxFieldCmd), C.c_uint64, i64p, u8p]),
+    "rbx_bitset_field_stream": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, C.POINTER(RbxFieldCmd), C.c_uint64,
+                                          i64p, u8p]),
+    "rbx_bitset_field_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp]),
     "rbx_bitset_field_rule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, i64p, i64p,
                                         C.POINTER(C.c_int)]),
     "rbx_bitset_count_range": (C.c_int, [vp, RbxName, C.c_int64, C.c_int64, C.c_int, u64p]),
@@ -253,6 +256,7 @@ SIGNATURES = {
     "rbx_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "rbx_bench_stream_geometry": (C.c_int, [vp, u64p]),
     "rbx_bench_bitrange_path": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "rbx_bench_fieldstream_last_path": (C.c_int, []),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

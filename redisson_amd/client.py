@@ -804,6 +804,53 @@ def bitset_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmd_op: i
                                          d_replies, stream))
 
 
+FIELD_FAILED = 0xFF  # status of a field-stream command that failed alone; 1 = nil (OVERFLOW FAIL)
+_FIELD_TYPE_MSG = "ERR Invalid bitfield type. Use something like i16 u8. Note that u64 is not supported but i64 is."
+
+
+def _field_cmds_array(cmds):
+    """rows of (op, signed, size, overflow, offset, value) -> an array of rbx_field_cmd"""
+    arr = (L.RbxFieldCmd * max(len(cmds), 1))()
+    for a, (op, signed, size, overflow, offset, value) in zip(arr, cmds):
+        a.op, a.is_signed, a.size, a.overflow, a.offset, a.value = op, int(signed), size, overflow, offset, value
+    return arr
+
+
+def bitset_field_stream_call(client: RedissonClient, names, cmd_key, cmds, replies: bool = True):
+    """rbx_bitset_field_stream over host arrays without raising: (rc, message, replies, status).  cmds: rows of
+    (op, signed, size, overflow, offset, value) with RBX_FIELD_* / RBX_OVERFLOW_* codes, or an array of
+    RbxFieldCmd.  replies: int64; status: uint8 with 0 = valid, 1 = nil, 0xFF = that command failed alone."""
+    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+    arr = cmds if isinstance(cmds, C.Array) else _field_cmds_array(list(cmds))
+    n = key.size
+    if len(arr) < n or (not isinstance(cmds, C.Array) and len(cmds) != n):
+        raise IllegalArgumentException("cmd_key and cmds have one entry per command")
+    names_arr, _keep = L.names_array(names)
+    out = np.zeros(max(n, 1), np.int64) if replies else None
+    status = np.zeros(max(n, 1), np.uint8)
+    rc = L.lib().rbx_bitset_field_stream(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p), arr, n,
+                                         out.ctypes.data_as(L.i64p) if replies else None, status.ctypes.data_as(L.u8p))
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), (out[:n] if replies else None), status[:n]
+
+
+def bitset_field_stream(client: RedissonClient, names, cmd_key, cmds, replies: bool = True):
+    """An ordered stream of single-sub-command BITFIELDs over many keys in one call (rbx_bitset_field_stream):
+    (replies, status) in order.  Raises the first failing command's exception after every other command ran."""
+    rc, msg, out, status = bitset_field_stream_call(client, names, cmd_key, cmds, replies)
+    raise_for(rc, msg)
+    return out, status
+
+
+def bitset_field_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmds: int, n: int,
+                            d_replies: int | None = None, d_status: int | None = None,
+                            stream: int | None = None) -> None:
+    """bitset_field_stream over device arrays (u32 keys, 24-byte rbx_field_cmd records, i64 replies, u8 status),
+    enqueued on `stream`."""
+    arr, _keep = L.names_array(names)
+    _check(L.lib().rbx_bitset_field_stream_dev(client.ctx, arr, len(names), d_cmd_key, d_cmds, int(n), d_replies,
+                                               d_status, stream))
+
+
 class BatchFuture:
     """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
     methods), or raises what the command failed with."""
@@ -828,12 +875,24 @@ class BatchFuture:
 
 
 class _Queued:
-    """One queued command: a bit command (name, op, index) that coalesces, or a callable that runs singly."""
+    """One queued command: a bit command (name, op, index) that coalesces, a field command (name, field =
+    (op, signed, size, overflow, offset, value), fn) that coalesces where a field stream call is at hand and
+    runs through fn otherwise, or a callable that runs singly.  convert: applied to a field command's reply."""
 
-    __slots__ = ("name", "op", "index", "fn", "future")
+    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert")
 
-    def __init__(self, name=None, op=None, index=0, fn=None):
+    def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None):
         self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
+        self.field, self.convert = field, convert
+
+    def as_field(self):
+        """the command as a BITFIELD sub-command: GETBIT / SETBIT are GET / SET of a u1, which leave the same
+        string and the same growth"""
+        if self.field is not None:
+            return self.field
+        if self.op == GETBIT:
+            return (L.RBX_FIELD_GET, 0, 1, L.RBX_OVERFLOW_WRAP, self.index, 0)
+        return (L.RBX_FIELD_SET, 0, 1, L.RBX_OVERFLOW_WRAP, self.index, 1 if self.op == SETBIT1 else 0)
 
 
 def _bit_index(index) -> int:
@@ -850,15 +909,57 @@ def _bit_error(q: _Queued) -> RedissonAmdError:
     return RedisException("WRONGTYPE Operation against a key holding the wrong kind of value")
 
 
-def run_queue(queue, stream_call):
-    """Executes queued commands in submission order: every maximal run of consecutive bit commands, over any
-    keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies); every other command
-    runs through its own call at its position.  Each command's future is set; returns (responses, first error)."""
+def _field_error(q: _Queued) -> RedissonAmdError:
+    """what a field command that failed alone failed with: the type, the offset limit, the key's type, in the
+    order of the single call"""
+    _op, signed, size, _mode, offset, _value = q.field
+    if size < 1 or size > (64 if signed else 63):
+        return RedisException(_FIELD_TYPE_MSG)
+    if offset >= _BIT_OFFSET_LIMIT or offset + size > _BIT_OFFSET_LIMIT:
+        return RedisException("ERR bit offset is not an integer or out of range")
+    return RedisException("WRONGTYPE Operation against a key holding the wrong kind of value")
+
+
+def _run_fields(run, field_stream_call):
+    """one field stream call for a run of bit and field commands; sets every future, returns the first error"""
+    ids: dict = {}
+    keys = [ids.setdefault(c.name, len(ids)) for c in run]
+    rc, msg, replies, status = field_stream_call(list(ids), keys, [c.as_field() for c in run])
+    if rc not in (L.RBX_OK, L.RBX_E_REDIS, L.RBX_E_WRONGTYPE):  # the run as a whole was refused
+        try:
+            raise_for(rc, msg)
+        except RedissonAmdError as e:
+            for c in run:
+                c.future._set(error=e)
+            return e
+    first_error = None
+    for c, r, s in zip(run, replies, status):
+        if int(s) == FIELD_FAILED:
+            c.future._set(error=_bit_error(c) if c.field is None else _field_error(c))
+        elif c.field is None:
+            c.future._set(bool(r))
+        else:
+            value = None if int(s) == 1 else int(r)  # nil
+            c.future._set(c.convert(value) if c.convert else value)
+        first_error = first_error or c.future._error
+    return first_error
+
+
+def run_queue(queue, stream_call, field_stream_call=None):
+    """Executes queued commands in submission order.  Every maximal run of consecutive bit commands, over any
+    keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies).  With a
+    field_stream_call, field commands join the runs, and a run that holds at least one of them is ONE
+    field_stream_call(names, cmd_key, cmds) -> (rc, message, replies, status) in which the bit commands travel as
+    u1 GET / SET.  Every other command runs through its own call at its position.  Each command's future is
+    set; returns (responses, first error)."""
+    def joins(q):
+        return q.op is not None or (q.field is not None and field_stream_call is not None)
+
     first_error = None
     i = 0
     while i < len(queue):
         q = queue[i]
-        if q.op is None:
+        if not joins(q):
             try:
                 q.future._set(q.fn())
             except RedissonAmdError as e:
@@ -867,9 +968,13 @@ def run_queue(queue, stream_call):
             i += 1
             continue
         j = i
-        while j < len(queue) and queue[j].op is not None:
+        while j < len(queue) and joins(queue[j]):
             j += 1
         run = queue[i:j]
+        if any(c.field is not None for c in run):
+            first_error = first_error or _run_fields(run, field_stream_call)
+            i = j
+            continue
         ids: dict = {}
         keys = [ids.setdefault(c.name, len(ids)) for c in run]
         rc, msg, replies = stream_call(list(ids), keys, [c.op for c in run], [c.index for c in run])
@@ -906,7 +1011,9 @@ class BatchResult:
 
 class RBatchBitSet:
     """RBatch.getBitSet(name) (M/RedissonBatch.java:182-184): RBitSetAsync, every method queued.  get / set /
-    clearBit of consecutive commands travel together; the others run through RBitSet's own call."""
+    clearBit and the typed-field methods of consecutive commands travel together (one rbx_bitset_stream call,
+    or one rbx_bitset_field_stream call when a field command is among them); the others run through RBitSet's
+    own call."""
 
     def __init__(self, batch: "RBatch", name: str):
         self._batch, self._name = batch, name
@@ -923,6 +1030,78 @@ class RBatchBitSet:
 
     def clearBitAsync(self, bitIndex: int) -> BatchFuture:
         return self.setAsync(bitIndex, False)
+
+    # ---- typed fields (M/api/RBitSetAsync.java:36-206): one BITFIELD sub-command each, travelling together --
+    def _field(self, method: str, op: int, signed: bool, size: int, offset: int, value: int = 0,
+               bits: int = 64) -> BatchFuture:
+        """Queues `method`'s BITFIELD.  Redisson's own argument checks fire now, as in the synchronous methods
+        (M/RedissonBitSet.java:72-73, :99-100); what Redis checks fails the command when the batch runs."""
+        size = RBitSet._java(size, 32, "size")
+        if size > (64 if signed else 63):
+            raise IllegalArgumentException(f"Size can't be greater than {64 if signed else 63} bits")
+        off = RBitSet._java(offset, 64, "offset") & 0xFFFFFFFFFFFFFFFF  # a negative long is past the limit too
+        value = RBitSet._java(RBitSet._java(value, bits, "value"), 64, "value")
+        args = (offset,) if op == L.RBX_FIELD_GET else (offset, value)
+        if method.endswith("igned"):  # the Signed / Unsigned forms take the size as their first argument
+            args = (size, *args)
+        bitset = self._batch._bitset
+        name = self._name
+        return self._batch._add(_Queued(name, fn=lambda: getattr(bitset(name), method)(*args),
+                                        field=(op, int(signed), max(size, 0), L.RBX_OVERFLOW_WRAP, off, value)))
+
+    def getSignedAsync(self, size: int, offset: int) -> BatchFuture:
+        return self._field("getSigned", L.RBX_FIELD_GET, True, size, offset)
+
+    def setSignedAsync(self, size: int, offset: int, value: int) -> BatchFuture:
+        return self._field("setSigned", L.RBX_FIELD_SET, True, size, offset, value)
+
+    def incrementAndGetSignedAsync(self, size: int, offset: int, increment: int) -> BatchFuture:
+        return self._field("incrementAndGetSigned", L.RBX_FIELD_INCRBY, True, size, offset, increment)
+
+    def getUnsignedAsync(self, size: int, offset: int) -> BatchFuture:
+        return self._field("getUnsigned", L.RBX_FIELD_GET, False, size, offset)
+
+    def setUnsignedAsync(self, size: int, offset: int, value: int) -> BatchFuture:
+        return self._field("setUnsigned", L.RBX_FIELD_SET, False, size, offset, value)
+
+    def incrementAndGetUnsignedAsync(self, size: int, offset: int, increment: int) -> BatchFuture:
+        return self._field("incrementAndGetUnsigned", L.RBX_FIELD_INCRBY, False, size, offset, increment)
+
+    def getByteAsync(self, offset: int) -> BatchFuture:
+        return self._field("getByte", L.RBX_FIELD_GET, True, 8, offset)
+
+    def setByteAsync(self, offset: int, value: int) -> BatchFuture:
+        return self._field("setByte", L.RBX_FIELD_SET, True, 8, offset, value, 8)
+
+    def incrementAndGetByteAsync(self, offset: int, increment: int) -> BatchFuture:
+        return self._field("incrementAndGetByte", L.RBX_FIELD_INCRBY, True, 8, offset, increment, 8)
+
+    def getShortAsync(self, offset: int) -> BatchFuture:
+        return self._field("getShort", L.RBX_FIELD_GET, True, 16, offset)
+
+    def setShortAsync(self, offset: int, value: int) -> BatchFuture:
+        return self._field("setShort", L.RBX_FIELD_SET, True, 16, offset, value, 16)
+
+    def incrementAndGetShortAsync(self, offset: int, increment: int) -> BatchFuture:
+        return self._field("incrementAndGetShort", L.RBX_FIELD_INCRBY, True, 16, offset, increment, 16)
+
+    def getIntegerAsync(self, offset: int) -> BatchFuture:
+        return self._field("getInteger", L.RBX_FIELD_GET, True, 32, offset)
+
+    def setIntegerAsync(self, offset: int, value: int) -> BatchFuture:
+        return self._field("setInteger", L.RBX_FIELD_SET, True, 32, offset, value, 32)
+
+    def incrementAndGetIntegerAsync(self, offset: int, increment: int) -> BatchFuture:
+        return self._field("incrementAndGetInteger", L.RBX_FIELD_INCRBY, True, 32, offset, increment, 32)
+
+    def getLongAsync(self, offset: int) -> BatchFuture:
+        return self._field("getLong", L.RBX_FIELD_GET, True, 64, offset)
+
+    def setLongAsync(self, offset: int, value: int) -> BatchFuture:
+        return self._field("setLong", L.RBX_FIELD_SET, True, 64, offset, value)
+
+    def incrementAndGetLongAsync(self, offset: int, increment: int) -> BatchFuture:
+        return self._field("incrementAndGetLong", L.RBX_FIELD_INCRBY, True, 64, offset, increment)
 
     def setRangeAsync(self, fromIndex: int, toIndex: int, value: bool = True) -> BatchFuture:
         return self._single("setRange", fromIndex, toIndex, value)
@@ -942,6 +1121,24 @@ class RBatchBitSet:
     get_async = getAsync
     set_async = setAsync
     clear_bit_async = clearBitAsync
+    get_signed_async = getSignedAsync
+    set_signed_async = setSignedAsync
+    increment_and_get_signed_async = incrementAndGetSignedAsync
+    get_unsigned_async = getUnsignedAsync
+    set_unsigned_async = setUnsignedAsync
+    increment_and_get_unsigned_async = incrementAndGetUnsignedAsync
+    get_byte_async = getByteAsync
+    set_byte_async = setByteAsync
+    increment_and_get_byte_async = incrementAndGetByteAsync
+    get_short_async = getShortAsync
+    set_short_async = setShortAsync
+    increment_and_get_short_async = incrementAndGetShortAsync
+    get_integer_async = getIntegerAsync
+    set_integer_async = setIntegerAsync
+    increment_and_get_integer_async = incrementAndGetIntegerAsync
+    get_long_async = getLongAsync
+    set_long_async = setLongAsync
+    increment_and_get_long_async = incrementAndGetLongAsync
     set_range_async = setRangeAsync
     clear_range_async = clearRangeAsync
     cardinality_async = cardinalityAsync
@@ -952,11 +1149,15 @@ class RBatchBitSet:
 class RBatch:
     """RedissonClient.createBatch() (M/RedissonBatch.java): commands queue across any number of keys, execute()
     runs them in submission order (M/command/CommandBatchService.java:115-134,335) and returns their replies
-    in that order.  stream_call / bitset replace the engine's calls (tests)."""
+    in that order.  stream_call / bitset / field_stream_call replace the engine's calls (tests); without a
+    client and without a field_stream_call, field commands run singly through bitset(name)."""
 
-    def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None):
+    def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None, field_stream_call=None):
         self._client = client
         self._stream_call = stream_call or (lambda *a: bitset_stream_call(client, *a))
+        if field_stream_call is None and client is not None:
+            field_stream_call = lambda *a: bitset_field_stream_call(client, *a)  # noqa: E731
+        self._field_stream_call = field_stream_call
         self._bitset = bitset or (lambda name: RBitSet(client, name))
         self._queue: list = []
         self._executed = False
@@ -975,7 +1176,7 @@ class RBatch:
         if self._executed:
             raise IllegalStateException("Batch already executed!")
         self._executed = True
-        responses, error = run_queue(self._queue, self._stream_call)
+        responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call)
         if error is not None:
             raise error
         return BatchResult(responses)

@@ -455,8 +455,70 @@ static int range_of(const uint8_t *bytes, uint64_t len, int missing, bool pos, i
 // ---- the ordered GETBIT / SETBIT stream over many keys (RBatch.getBitSet, M/RedissonBatch.java:182-184) ----
 static int significant_bits(uint64_t v) {
     int b = 0;
-    while (v >> b) ++b;
+    while (b < 64 && (v >> b)) ++b;  // (a shift by 64 is undefined: a value with bit 63 set ends at b = 64)
     return b;
+}
+
+// The keys of one stream call.  Equal names are one key, known by its first entry (its canonical id); a key
+// of another type fails its commands.
+struct StreamKeys {
+    uint32_t nkeys = 0;
+    std::vector<std::string> nm;
+    std::vector<uint8_t> kinfo;  // canonical ids | wrong-type flags, as the summary kernels read them
+    uint32_t *canon() { return (uint32_t *)kinfo.data(); }
+    uint8_t *wrong() { return kinfo.data() + (size_t)nkeys * 4; }
+};
+
+// resolves the names once (lookup only) and uploads canonical ids | wrong-type flags to bst_keys
+static int stream_keys_resolve(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, hipStream_t st, StreamKeys *sk) {
+    sk->nkeys = nkeys;
+    sk->nm.resize(nkeys);
+    sk->kinfo.assign((size_t)nkeys * 5, 0);
+    uint32_t *canon = sk->canon();
+    uint8_t *wrong = sk->wrong();
+    std::unordered_map<std::string, uint32_t> first;
+    first.reserve(nkeys);
+    for (uint32_t i = 0; i < nkeys; ++i) {
+        sk->nm[i] = name_of(names[i]);
+        canon[i] = first.emplace(sk->nm[i], i).first->second;
+        const Entry *e = canon[i] == i ? c->ks.find(sk->nm[i]) : nullptr;
+        wrong[i] = canon[i] == i ? (uint8_t)(e && e->type != KType::Bitmap) : wrong[canon[i]];
+    }
+    DevBuf &d = c->dev->bits.bst_keys;
+    RBX_TRY(d.reserve(sk->kinfo.size()));
+    HIP_TRY(hipMemcpyAsync(d.p, sk->kinfo.data(), sk->kinfo.size(), hipMemcpyHostToDevice, st));
+    return RBX_OK;
+}
+
+// Creates or grows every string the batch writes -- keymax[i] = 1 + the last bit a command that runs writes
+// on canonical key i, 0 = none -- then uploads the table over the final allocations.  *writes = some key is
+// written (its length word is to be raised).
+static int stream_keys_table(rbx_ctx *c, StreamKeys &sk, const unsigned long long *keymax, hipStream_t st,
+                             const BitKey **d_tab, bool *writes) {
+    const uint32_t *canon = sk.canon();
+    const uint8_t *wrong = sk.wrong();
+    std::vector<BitKey> tab(sk.nkeys);
+    *writes = false;
+    for (uint32_t i = 0; i < sk.nkeys; ++i) {
+        BitKey &k = tab[i];
+        if (canon[i] != i) {
+            k = tab[canon[i]];
+            continue;
+        }
+        k = BitKey{nullptr, 0, nullptr, wrong[i] ? kBitKeyWrong : 0u, i};
+        if (wrong[i]) continue;
+        std::shared_ptr<Bitmap> bm;
+        const uint64_t mx1 = keymax[i];
+        if (mx1) {
+            RBX_TRY(bitset_for_write(c, sk.nm[i], ((mx1 - 1) >> 3) + 1, st, &bm));
+            *writes = true;
+        } else {
+            RBX_TRY(bitset_find(c, sk.nm[i], &bm));
+        }
+        if (bm) k = BitKey{bm->d_words, bm->cap_bytes * 8, bm->d_len, 0u, i};
+    }
+    *d_tab = c->dev->bits.bst_table.sync(tab, st);
+    return *d_tab ? RBX_OK : c->dev->bits.bst_table.err;
 }
 
 static int stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const void *key, const void *op,
@@ -479,23 +541,8 @@ static int stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const u
     *failed = RBX_OK;
     if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys");
     BitsetScratch &b = c->dev->bits;
-    // equal names are one key, known by its first entry; a key of another type fails its commands
-    std::vector<std::string> nm(nkeys);
-    std::vector<uint8_t> kinfo((size_t)nkeys * 5);  // canonical ids | wrong-type flags
-    uint32_t *canon = (uint32_t *)kinfo.data();
-    uint8_t *wrong = kinfo.data() + (size_t)nkeys * 4;
-    {
-        std::unordered_map<std::string, uint32_t> first;
-        first.reserve(nkeys);
-        for (uint32_t i = 0; i < nkeys; ++i) {
-            nm[i] = name_of(names[i]);
-            canon[i] = first.emplace(nm[i], i).first->second;
-            const Entry *e = canon[i] == i ? c->ks.find(nm[i]) : nullptr;
-            wrong[i] = canon[i] == i ? (uint8_t)(e && e->type != KType::Bitmap) : wrong[canon[i]];
-        }
-    }
-    RBX_TRY(b.bst_keys.reserve(kinfo.size()));
-    HIP_TRY(hipMemcpyAsync(b.bst_keys.p, kinfo.data(), kinfo.size(), hipMemcpyHostToDevice, st));
+    StreamKeys sk;
+    RBX_TRY(stream_keys_resolve(c, names, nkeys, st, &sk));
     const size_t sum_bytes = (kBsSummaryWords + (size_t)nkeys) * 8;
     RBX_TRY(b.bst_sum.reserve(sum_bytes));
     auto *d_sum = b.bst_sum.as<unsigned long long>(), *d_keymax = d_sum + kBsSummaryWords;
@@ -514,29 +561,10 @@ static int stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const u
     const bool gets = flags & kBsHasGet, sets = flags & (kBsHasSet0 | kBsHasSet1);
     const bool one_value = (flags & (kBsHasSet0 | kBsHasSet1)) != (kBsHasSet0 | kBsHasSet1);
 
-    // the strings the batch writes, then the table over their final allocations
-    std::vector<BitKey> tab(nkeys);
-    bool writes = false;
-    for (uint32_t i = 0; i < nkeys; ++i) {
-        BitKey &k = tab[i];
-        if (canon[i] != i) {
-            k = tab[canon[i]];
-            continue;
-        }
-        k = BitKey{nullptr, 0, nullptr, wrong[i] ? kBitKeyWrong : 0u, i};
-        if (wrong[i]) continue;
-        std::shared_ptr<Bitmap> bm;
-        const uint64_t mx1 = sum[kBsSummaryWords + i];  // 1 + the key's largest SETBIT index that runs
-        if (mx1) {
-            RBX_TRY(bitset_for_write(c, nm[i], ((mx1 - 1) >> 3) + 1, st, &bm));
-            writes = true;
-        } else {
-            RBX_TRY(bitset_find(c, nm[i], &bm));
-        }
-        if (bm) k = BitKey{bm->d_words, bm->cap_bytes * 8, bm->d_len, 0u, i};
-    }
-    const BitKey *d_tab = b.bst_table.sync(tab, st);
-    if (!d_tab) return b.bst_table.err;
+    // the strings the batch writes (keymax: 1 + the key's largest SETBIT index that runs), then the table
+    const BitKey *d_tab;
+    bool writes;
+    RBX_TRY(stream_keys_table(c, sk, sum.data() + kBsSummaryWords, st, &d_tab, &writes));
 
     const int path = g_tune.bitstream_path;
     if (path == 0 && !sets) {
@@ -573,9 +601,114 @@ static int stream_failed(int code) {
     return fail(code, code == RBX_E_REDIS ? kBitOffsetMsg : kWrongTypeMsg);
 }
 
+// ---- the ordered BITFIELD stream over many keys (RBatch.getBitSet's typed fields, M/api/RBitSetAsync.java:36-206) ----
+enum { kFsPathNone = 0, kFsPathSerial = 1, kFsPathWords = 2, kFsPathKeys = 3, kFsPathGather = 4, kFsPathAtomic = 5 };
+static std::atomic<int> g_fieldstream_last_path{kFsPathNone};  // rbx_bench_fieldstream_last_path shows it
+
+static int field_stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const void *key,
+                                   const void *cmds, uint64_t n) {
+    if (!c || (nkeys && !names) || (n && (!key || !cmds))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (uint32_t i = 0; i < nkeys; ++i)
+        if (bad_name(names[i])) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
+    if (nkeys > (1u << 31)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes at most 2^31 keys");
+    return RBX_OK;
+}
+
+// A batch of n > 0 commands over device arrays inside the caller's scope on `st`; d_replies and d_status
+// nullable.  *failed = 0, or the failure kind (kFs*) of the first command in array order that failed alone.
+// stream_run's steps: the summary pass (names resolved once; one wait), the host's decisions (the caller's
+// errors, every written key created or grown, the key table, the path), one execution path, the lengths.
+static int field_stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_key,
+                            const rbx_field_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
+                            hipStream_t st, int *failed) {
+    *failed = 0;
+    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys");
+    BitsetScratch &b = c->dev->bits;
+    StreamKeys sk;
+    RBX_TRY(stream_keys_resolve(c, names, nkeys, st, &sk));
+    const size_t sum_bytes = (kFsSummaryWords + (size_t)nkeys) * 8;
+    RBX_TRY(b.bst_sum.reserve(sum_bytes));
+    auto *d_sum = b.bst_sum.as<unsigned long long>(), *d_keymax = d_sum + kFsSummaryWords;
+    HIP_TRY(hipMemsetAsync(d_sum, 0xFF, kFsFlags * 8, st));
+    HIP_TRY(hipMemsetAsync(d_sum + kFsFlags, 0, sum_bytes - kFsFlags * 8, st));
+    launch_fieldstream_summary(d_key, d_cmds, n, nkeys, b.bst_keys.as<uint32_t>(),
+                               b.bst_keys.as<uint8_t>() + (size_t)nkeys * 4, d_sum, d_keymax, st);
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> sum(kFsSummaryWords + (size_t)nkeys);
+    HIP_TRY(hipMemcpyAsync(sum.data(), d_sum, sum_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the one wait
+    const uint32_t flags = (uint32_t)sum[kFsFlags];
+    if (flags & kFsIllegal)
+        return fail(RBX_E_ILLEGAL_ARGUMENT,
+                    "a command's key is not below nkeys, or its op, overflow mode or is_signed is unknown");
+    if ((flags & kFsFail) && d_replies && !d_status)
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "OVERFLOW FAIL with replies needs status");
+    const uint64_t first[3] = {sum[kFsFirstType], sum[kFsFirstOffset], sum[kFsFirstWrong]};
+    const uint64_t first_failed = std::min(first[0], std::min(first[1], first[2]));
+    const bool has_failed = first_failed != ~0ULL;
+
+    const BitKey *d_tab;
+    bool writes;
+    RBX_TRY(stream_keys_table(c, sk, sum.data() + kFsSummaryWords, st, &d_tab, &writes));
+
+    const bool sets = flags & (kFsHasSet | kFsHasIncr), straddles = flags & kFsStraddles;
+    const uint64_t sizes = sum[kFsSizes];
+    const int one_size = sizes && !(sizes & (sizes - 1)) ? significant_bits(sizes) : 0;  // 0: several sizes occur
+    // sums modulo 2^size commute, and equal-or-disjoint fields keep them apart: not so for mixed sizes
+    // (fieldstream_kernels.hip section 3)
+    const bool commutes = (flags & (kFsHasGet | kFsHasSet | kFsHasIncr)) == kFsHasIncr && !(flags & (kFsSat | kFsFail)) &&
+                          !d_replies && one_size && 64 % one_size == 0 && !(flags & kFsUnaligned);
+    const int tuned = g_tune.fieldstream_path;
+    int path;
+    if (tuned == 0)
+        path = !sets ? kFsPathGather
+               : commutes ? kFsPathAtomic
+               : n <= g_tune.fieldstream_serial_max ? kFsPathSerial
+               : straddles ? kFsPathKeys : kFsPathWords;
+    else
+        path = tuned == 2 && straddles ? kFsPathKeys : tuned;
+    g_fieldstream_last_path = path;
+    if (path == kFsPathGather) {
+        if (d_replies || d_status) launch_fieldstream_gather(d_tab, d_key, d_cmds, n, d_replies, d_status, st);
+    } else if (path == kFsPathAtomic) {
+        launch_fieldstream_incr_atomic(d_tab, d_key, d_cmds, n, d_status, st);
+    } else if (path == kFsPathSerial) {
+        launch_fieldstream_serial(d_tab, d_key, d_cmds, n, d_replies, d_status, st);
+    } else {
+        // consecutive chunks in order; a cell that spans two of them is read again by the second
+        const uint64_t chunk = g_tune.fieldstream_chunk;
+        const int word_bits = path == kFsPathWords ? std::max(1, significant_bits(sum[kFsMaxWord])) : 0;
+        const int key_bits = std::max(1, significant_bits((uint64_t)nkeys - 1));
+        size_t scratch = 0;
+        int e = fieldstream_grouped_scratch_bytes((uint32_t)std::min(n, chunk), word_bits + key_bits + (has_failed ? 1 : 0),
+                                                  &scratch);
+        if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        RBX_TRY(b.bst_sort.reserve(scratch));
+        for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
+            const uint32_t m = (uint32_t)std::min(chunk, n - i0);
+            e = launch_fieldstream_grouped(d_tab, d_key + i0, d_cmds + i0, m, d_replies ? d_replies + i0 : nullptr,
+                                           d_status ? d_status + i0 : nullptr, word_bits, key_bits, has_failed,
+                                           b.bst_sort.p, b.bst_sort.cap, st);
+            if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+        }
+    }
+    if (writes) launch_bitstream_lengths(d_tab, d_keymax, nkeys, st);
+    HIP_TRY(hipGetLastError());
+    if (has_failed) *failed = first_failed == first[0] ? kFsBadType : (first_failed == first[1] ? kFsBadOffset : kFsWrongType);
+    return RBX_OK;
+}
+
+static int field_stream_failed(int kind) {
+    if (kind == 0) return RBX_OK;
+    if (kind == kFsWrongType) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    return fail(RBX_E_REDIS, kind == kFsBadType ? kFieldTypeMsg : kBitOffsetMsg);
+}
+
 }  // namespace rbx
 
 using namespace rbx;
+
+extern "C" int rbx_bench_fieldstream_last_path(void) { return g_fieldstream_last_path; }
 
 extern "C" int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t longest) {
     return ranges_take_directory(len, n, total, longest) ? 1 : 0;
@@ -696,6 +829,42 @@ int rbx_bitset_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const u
     if (replies) HIP_TRY(hipMemcpyAsync(replies, d_replies, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return stream_failed(failed);
+}
+
+int rbx_bitset_field_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                                const rbx_field_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
+                                void *stream) {
+    RBX_TRY(field_stream_args_check(c, names, nkeys, d_cmd_key, d_cmds, n));
+    if (n == 0) return RBX_OK;  // no command is sent
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    int failed;
+    RBX_TRY(field_stream_run(c, names, nkeys, d_cmd_key, d_cmds, n, d_replies, d_status, st, &failed));
+    return field_stream_failed(failed);
+}
+
+int rbx_bitset_field_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                            const rbx_field_cmd *cmds, uint64_t n, int64_t *replies, uint8_t *status) {
+    RBX_TRY(field_stream_args_check(c, names, nkeys, cmd_key, cmds, n));
+    if (n == 0) return RBX_OK;
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.fst_cmds.reserve(n * (sizeof(rbx_field_cmd) + 4)));  // commands | keys
+    if (replies) RBX_TRY(b.fld_out.reserve(n * 8));
+    if (status) RBX_TRY(b.fld_nil.reserve(n));
+    rbx_field_cmd *d_cmds = b.fst_cmds.as<rbx_field_cmd>();
+    uint32_t *d_key = (uint32_t *)(d_cmds + n);
+    int64_t *d_replies = replies ? b.fld_out.as<int64_t>() : nullptr;
+    uint8_t *d_status = status ? b.fld_nil.as<uint8_t>() : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_cmds, cmds, n * sizeof(rbx_field_cmd), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_key, cmd_key, n * 4, hipMemcpyHostToDevice, st));
+    int failed;
+    RBX_TRY(field_stream_run(c, names, nkeys, d_key, d_cmds, n, d_replies, d_status, st, &failed));
+    if (replies) HIP_TRY(hipMemcpyAsync(replies, d_replies, n * 8, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return field_stream_failed(failed);
 }
 
 int rbx_bitset_set_range(rbx_ctx *c, rbx_name name, uint64_t from, uint64_t to, int value) {
@@ -948,8 +1117,8 @@ int rbx_bitset_bitfield(rbx_ctx *c, rbx_name name, const rbx_field_cmd *cmds, ui
         if (k.op > RBX_FIELD_INCRBY) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITFIELD operation");
         RBX_TRY(overflow_check(k.overflow));
         if (k.is_signed > 1) return fail(RBX_E_ILLEGAL_ARGUMENT, "is_signed is 0 or 1");
-        if (k.size < 1 || k.size > (k.is_signed ? 64 : 63)) return fail(RBX_E_REDIS, kFieldTypeMsg);
-        RBX_TRY(field_range_check(k.offset, k.size));
+        const int bad = field_cmd_check(k.is_signed, k.size, k.offset);  // the type, then the offset limit
+        if (bad) return fail(RBX_E_REDIS, bad == kFieldCmdBadType ? kFieldTypeMsg : kBitOffsetMsg);
         same &= k.op == cmds[0].op && k.is_signed == cmds[0].is_signed && k.size == cmds[0].size &&
                 (k.op == RBX_FIELD_GET || k.overflow == cmds[0].overflow);
         if (k.op == RBX_FIELD_GET) {

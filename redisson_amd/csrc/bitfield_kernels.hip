@@ -5,65 +5,21 @@
 // mode is a template parameter of the writing kernels: the WRAP instantiations are the modular
 // arithmetic below, SAT and FAIL go through field_rule (field_rule.h).
 //
-// The bitmap is addressed here as aligned 64-bit words.  A word's bytes are the string's bytes in
-// order, so the byte-swapped word holds string bit 64q + j at position 63 - j: a field is a run of
-// adjacent bits of at most two byte-swapped words, and integer arithmetic on that run is arithmetic
-// on the field.  The allocation is a multiple of 256 bytes, so an aligned word lies inside it or
-// wholly past it; the kernels keep the bytes from the string's length to the allocation's end zero
-// (they write only inside fields the host sized the string for).
+// The bitmap is addressed here as aligned 64-bit words (field_device.h has the layout and the loads and
+// stores); the kernels keep the bytes from the string's length to the allocation's end zero (they write
+// only inside fields the host sized the string for).
 // M/ = /root/reference/redisson/src/main/java/org/redisson/
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/rbx.h"
 #include "bloom_common.h"
-#include "field_rule.h"
+#include "field_device.h"  // field_load / field_store / field_apply_ov; field_rule.h
 #include "rbx_kernels.h"
 
 namespace rbx {
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 field_mask(uint32_t size) { return size >= 64 ? ~0ULL : (1ULL << size) - 1; }
-
-// the reply form of a field's bits: sign-extended for i<size>, as they are for u<size>
-__device__ __forceinline__ int64_t field_extend(u64 v, uint32_t size, uint32_t is_signed) {
-    if (is_signed && size < 64 && ((v >> (size - 1)) & 1)) v |= ~0ULL << size;
-    return (int64_t)v;
-}
-
-// word q of the string in big-endian bit order; zero at or past the allocation
-__device__ __forceinline__ u64 ld_be(const u64 *w, uint64_t q, uint64_t cap_words) {
-    return q < cap_words ? __builtin_bswap64(w[q]) : 0ULL;
-}
-
-// the field's bits, zero-extended
-__device__ __forceinline__ u64 field_load(const u64 *w, uint64_t cap_words, uint64_t off, uint32_t size) {
-    const uint64_t q = off >> 6;
-    const uint32_t sh = (uint32_t)(off & 63);
-    u64 hi = ld_be(w, q, cap_words) << sh;
-    if (sh + size > 64) hi |= ld_be(w, q + 1, cap_words) >> (64 - sh);  // sh >= 1 here
-    return hi >> (64 - size);
-}
-
-// field := v (already below 2^size), the field inside the allocation.  ATOMIC: other lanes write
-// other fields of the same words at the same time, so the bits go out as atomicAnd + atomicOr.
-template <bool ATOMIC> __device__ __forceinline__ void word_put(u64 *p, u64 m, u64 bits) {
-    if (ATOMIC) {
-        atomicAnd(p, __builtin_bswap64(~m));
-        atomicOr(p, __builtin_bswap64(bits));
-    } else {
-        *p = __builtin_bswap64((__builtin_bswap64(*p) & ~m) | bits);
-    }
-}
-
-template <bool ATOMIC> __device__ __forceinline__ void field_store(u64 *w, uint64_t off, uint32_t size, u64 v) {
-    const uint64_t q = off >> 6;
-    const uint32_t sh = (uint32_t)(off & 63);
-    const u64 m = field_mask(size) << (64 - size), top = v << (64 - size);  // the field at a word's top
-    word_put<ATOMIC>(w + q, m >> sh, top >> sh);
-    if (sh + size > 64) word_put<ATOMIC>(w + q + 1, m << (64 - sh), top << (64 - sh));
-}
 
 // one sub-command on the field at `off`: the reply, the field updated in place
 template <bool ATOMIC>
@@ -74,16 +30,6 @@ __device__ __forceinline__ int64_t field_apply(u64 *w, uint64_t cap_words, int o
     const u64 now = (op == RBX_FIELD_SET ? (u64)value : old + (u64)value) & field_mask(size);
     field_store<ATOMIC>(w, off, size, now);
     return field_extend(op == RBX_FIELD_SET ? old : now, size, is_signed);
-}
-
-// the same under an overflow mode (field_rule): *nil = the reply is nil and the field untouched
-__device__ __forceinline__ int64_t field_apply_ov(u64 *w, uint64_t cap_words, int op, uint32_t is_signed, uint32_t size,
-                                                  int mode, uint64_t off, int64_t value, bool *nil) {
-    const int64_t old = field_extend(field_load(w, cap_words, off, size), size, is_signed);
-    int64_t now, reply;
-    *nil = field_rule(op, (int)is_signed, (int)size, mode, old, value, &now, &reply);
-    if (op != RBX_FIELD_GET && !*nil) field_store<false>(w, off, size, (u64)now & field_mask(size));
-    return reply;
 }
 
 // ---------------------------------------------------------------------------------

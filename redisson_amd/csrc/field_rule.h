@@ -1,8 +1,9 @@
 // field_rule.h -- what one BITFIELD sub-command does to one field under OVERFLOW WRAP / SAT / FAIL
 // ([redis-7.2] bitops.c bitfieldGeneric, checkSignedBitfieldOverflow, checkUnsignedBitfieldOverflow,
-// restated in DESIGN section 11.3).  One function for the kernels (bitfield_kernels.hip), the host
-// entry point rbx_bitset_field_rule (api_bitset.cpp) and the stand-alone sanitizer program
-// (tests/c/field_rule_test.cpp): it includes <stdint.h> only and compiles without HIP.
+// restated in DESIGN section 11.3), and the check of one sub-command's type and offset.  One function each for the
+// kernels (bitfield_kernels.hip, fieldstream_kernels.hip), the host entry points (api_bitset.cpp) and the
+// stand-alone sanitizer programs (tests/c/field_rule_test.cpp, tests/c/field_cmd_check_test.cpp): it
+// includes <stdint.h> only and compiles without HIP.
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +20,19 @@ namespace rbx {
 // the values of RBX_FIELD_* and RBX_OVERFLOW_* (include/rbx.h), restated so this header stands alone
 enum { kFieldGet = 0, kFieldSet = 1, kFieldIncrBy = 2 };
 enum { kOverflowWrap = 0, kOverflowSat = 1, kOverflowFail = 2 };
+
+// The checks Redis makes on one sub-command's type and offset, in the order rbx_bitset_bitfield applies
+// them: the type first (u64, i65 and size 0 are "ERR Invalid bitfield type"), then the offset limit (the
+// whole field lies below bit 2^32: "ERR bit offset is not an integer or out of range").  One rule for the
+// single call, the field stream's summary pass and its execution kernels (fieldstream_kernels.hip) and
+// the stand-alone program tests/c/field_cmd_check_test.cpp.
+enum { kFieldCmdOk = 0, kFieldCmdBadType = 1, kFieldCmdBadOffset = 2 };
+RBX_HD int field_cmd_check(int is_signed, int size, uint64_t offset) {
+    if (size < 1 || size > (is_signed ? 64 : 63)) return kFieldCmdBadType;
+    const uint64_t limit = 1ULL << 32;
+    if (offset >= limit || offset + (uint64_t)size > limit) return kFieldCmdBadOffset;
+    return kFieldCmdOk;
+}
 
 // the low `size` bits of v as a value of the type: sign-extended for i<size>, as they are for u<size>
 RBX_HD int64_t field_typed(uint64_t v, int size, int is_signed) {

@@ -321,6 +321,9 @@ static const TuneRow kTuneRows[] = {
     {"bitstream_path", RANGE(0, 2), false, FIELD(bitstream_path)},
     {"bitstream_serial_max", RANGE(0, kIntMax), false, FIELD(bitstream_serial_max)},
     {"bitstream_chunk", RANGE(1, 1 << 30), false, FIELD(bitstream_chunk)},  // positions in a chunk are 32-bit
+    {"fieldstream_path", RANGE(0, 3), false, FIELD(fieldstream_path)},
+    {"fieldstream_serial_max", RANGE(0, kIntMax), false, FIELD(fieldstream_serial_max)},
+    {"fieldstream_chunk", RANGE(1, 1 << 30), false, FIELD(fieldstream_chunk)},  // positions in a chunk are 32-bit
 };
 #undef RANGE
 #undef ONE_OF

@@ -370,6 +370,9 @@ struct BitsetScratch {
     // summary words | per-key maxima, the grouped path's sort scratch, and the key table
     DevBuf bst_cmds, bst_keys, bst_sum, bst_sort;
     CachedTable<rbx::BitKey> bst_table;
+    // the BITFIELD stream shares bst_keys, bst_sum, bst_sort and bst_table (one call at a time holds them);
+    // its host form uploads commands | keys here and answers through fld_out and fld_nil
+    DevBuf fst_cmds;
 };
 
 // Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).

@@ -454,6 +454,51 @@ int launch_bitstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const u
 // *len = max(*len, bytes up to the key's largest SETBIT) for every key with an entry in d_keymax
 void launch_bitstream_lengths(const BitKey *d_tab, const unsigned long long *d_keymax, uint32_t nkeys, hipStream_t st);
 
+// ---- fieldstream_kernels.hip
+// The ordered stream of single-sub-command BITFIELDs over many strings (rbx_bitset_field_stream, DESIGN
+// §11.6).  Command i is (key[i], cmds[i]); a reply is what rbx_bitset_bitfield with that one sub-command
+// returns, a status 0, 1 (nil) or 0xFF (the command failed alone; its reply is 0).  The strings are reached
+// through the BitKey table above.
+// a command's failure kinds: field_rule.h's kFieldCmdBadType / kFieldCmdBadOffset, then the key's type
+constexpr int kFsBadType = 1, kFsBadOffset = 2, kFsWrongType = 3;
+// the summary words (u64) and the bits of the flags word
+enum { kFsFirstType = 0, kFsFirstOffset = 1, kFsFirstWrong = 2, kFsFlags = 3, kFsSizes = 4, kFsMaxWord = 5,
+       kFsSummaryWords = 6 };
+constexpr uint32_t kFsIllegal = 1, kFsHasGet = 2, kFsHasSet = 4, kFsHasIncr = 8;  // kFsHasGet << op
+constexpr uint32_t kFsWrap = 16, kFsSat = 32, kFsFail = 64;                         // kFsWrap << overflow
+constexpr uint32_t kFsStraddles = 128, kFsUnaligned = 256;
+// One pass before anything is written.  d_sum (the caller sets words 0..2 to ~0, the others to 0):
+// [kFsFirst*] the first position of each failure kind, [kFsFlags] kFsIllegal = some key >= nkeys, op or
+// overflow > 2 or is_signed > 1; and over the commands that run: kFsHas* their operations, kFsWrap / Sat /
+// Fail the modes of their SETs and INCRBYs, kFsStraddles = some field crosses an aligned 64-bit word,
+// kFsUnaligned = some offset is no multiple of its size; [kFsSizes] bit size - 1 per size that occurs;
+// [kFsMaxWord] the largest 64-bit word index a field reaches.  d_keymax (nkeys words, zeroed): per canonical
+// key the largest offset + size among its SETs and INCRBYs that run, which is what
+// launch_bitstream_lengths takes (1 + the last bit written).
+void launch_fieldstream_summary(const uint32_t *d_key, const rbx_field_cmd *d_cmds, uint64_t n, uint32_t nkeys,
+                                const uint32_t *d_canon, const uint8_t *d_wrong, unsigned long long *d_sum,
+                                unsigned long long *d_keymax, hipStream_t st);
+// d_replies and d_status are nullable everywhere below.
+// a batch whose running commands are all GETs
+void launch_fieldstream_gather(const BitKey *d_tab, const uint32_t *d_key, const rbx_field_cmd *d_cmds, uint64_t n,
+                               int64_t *d_replies, uint8_t *d_status, hipStream_t st);
+// a batch whose running commands are all INCRBYs under WRAP of ONE size dividing 64 at multiples of it, the
+// replies not wanted: any order
+void launch_fieldstream_incr_atomic(const BitKey *d_tab, const uint32_t *d_key, const rbx_field_cmd *d_cmds, uint64_t n,
+                                    uint8_t *d_status, hipStream_t st);
+// any batch in array order, one lane
+void launch_fieldstream_serial(const BitKey *d_tab, const uint32_t *d_key, const rbx_field_cmd *d_cmds, uint64_t n,
+                               int64_t *d_replies, uint8_t *d_status, hipStream_t st);
+// any batch of n <= 2^30 commands: a stable sort by cell, then one lane per cell.  word_bits > 0: cell = canon
+// << word_bits | offset >> 6 (word_bits = the significant bits of [kFsMaxWord], at least 1; the batch must not
+// have kFsStraddles); word_bits = 0: cell = canon.  key_bits: the significant bits of nkeys - 1, at least 1;
+// has_failed: some command of the batch fails.  The scratch size comes from fieldstream_grouped_scratch_bytes
+// with cell_bits = word_bits + key_bits + has_failed.  Both return 0 or a hipError_t.
+int fieldstream_grouped_scratch_bytes(uint32_t n, int cell_bits, size_t *bytes);
+int launch_fieldstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const rbx_field_cmd *d_cmds, uint32_t n,
+                               int64_t *d_replies, uint8_t *d_status, int word_bits, int key_bits, bool has_failed,
+                               void *d_scratch, size_t scratch_bytes, hipStream_t st);
+
 // ---- bench_kernels.hip
 // Roofline probes (api_bench.cpp only).
 // region-local gathers: 6 loads per lane inside XCD-assigned regions (partitioned-probe roofline)

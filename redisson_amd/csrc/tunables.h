@@ -95,6 +95,20 @@ struct Tunables {
     // "bitstream_chunk": commands per chunk of the grouped path (36 bytes of sort scratch per command: 2^25
     // commands are 1.125 GiB)
     std::atomic<uint64_t> bitstream_chunk{1 << 25};
+
+    // ---- the ordered BITFIELD stream (api_bitset.cpp) ----
+    // "fieldstream_path": 0 (default) = gather for a batch without SET / INCRBY, one compare-and-swap loop per
+    // command for WRAP INCRBYs of one size dividing 64 at multiples of it without replies, else serial up to
+    // fieldstream_serial_max commands, past it grouped by word when every command lies inside one aligned
+    // 64-bit word and by key otherwise; 1 = always serial, 2 = always grouped by word (by key when a field
+    // straddles words), 3 = always grouped by key.  All exact.
+    std::atomic<int> fieldstream_path{0};
+    // "fieldstream_serial_max": the auto rule's largest batch for the one-lane walk.  bitstream_serial_max's
+    // value, taken over from DESIGN 11.5: the crossover is NOT measured for fields.
+    std::atomic<uint64_t> fieldstream_serial_max{64};
+    // "fieldstream_chunk": commands per chunk of the grouped paths (24 bytes of sort scratch per command plus
+    // rocPRIM's own; positions inside a chunk are 32-bit)
+    std::atomic<uint64_t> fieldstream_chunk{1 << 25};
 };
 
 extern Tunables g_tune;

@@ -23,7 +23,8 @@ import functools
 import numpy as np
 
 from . import _lib as L
-from .client import GETBIT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued, bitset_stream_call, run_queue
+from .client import (GETBIT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued, bitset_field_stream_call,
+                     bitset_stream_call, run_queue)
 from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
 
@@ -96,10 +97,43 @@ def resolve_overflow(subCommands) -> list:
     return out
 
 
-def _pipelined(fn=None, *, bit=None):
+_MODES = {"WRAP": L.RBX_OVERFLOW_WRAP, "SAT": L.RBX_OVERFLOW_SAT, "FAIL": L.RBX_OVERFLOW_FAIL}
+
+
+def _field_row(cmd, mode: str) -> tuple:
+    """one sub-command of bitField under `mode` as (op, signed, size, overflow, offset, value) of rbx_field_cmd"""
+    if isinstance(cmd, BitFieldGet):
+        op = L.RBX_FIELD_GET
+    elif isinstance(cmd, BitFieldSet):
+        op = L.RBX_FIELD_SET
+    elif isinstance(cmd, BitFieldIncrBy):
+        op = L.RBX_FIELD_INCRBY
+    else:
+        raise IllegalArgumentException(f"unknown BITFIELD sub-command {cmd!r}")
+    bits = cmd.type.bits
+    offset = cmd.offset.value if cmd.offset.zero_based else cmd.offset.value * bits
+    value = getattr(cmd, "value", 0)
+    if not -(1 << 63) <= value < 1 << 63:
+        raise IllegalArgumentException("field values are Java longs")
+    return (op, int(cmd.type.signed), bits if 0 <= bits <= 255 else 0,  # no such type: Redis's error
+            _MODES[mode], offset if 0 <= offset < 1 << 64 else (1 << 64) - 1,  # past the limit either way
+            value)
+
+
+def _one_sub_command(key, subCommands):
+    """(key, row, convert) for a pipelined bitField of exactly one sub-command (it runs under WRAP: an OVERFLOW
+    governs what follows it), whose result is [reply] or [None]; None for any other list"""
+    cmds = list(subCommands)
+    if len(cmds) != 1:
+        return None
+    return key, _field_row(cmds[0], "WRAP"), lambda reply: [reply]
+
+
+def _pipelined(fn=None, *, bit=None, field=None):
     """A command method of RedissonConnection: while a pipeline is open it queues itself and returns None
     (the result comes back from closePipeline); bit = (key, op, index) of a GETBIT / SETBIT, which travels with
-    its neighbours in one rbx_bitset_stream call."""
+    its neighbours in one rbx_bitset_stream call; field = (key, row, convert) of a BITFIELD with one sub-command
+    (or None for any other), which travels with its bit and field neighbours in one rbx_bitset_field_stream call."""
 
     def wrap(f):
         @functools.wraps(f)
@@ -109,8 +143,17 @@ def _pipelined(fn=None, *, bit=None):
             if bit is not None:
                 key, op, index = bit(*args, **kwargs)
                 self._pipeline.append(_Queued(_key(key), op, _bit_index(index)))
+                return None
+            single = lambda: f(self, *args, **kwargs)  # noqa: E731
+            try:
+                row = field(*args, **kwargs) if field is not None else None
+            except IllegalArgumentException:
+                row = None  # the single call raises it at its position
+            if row is not None:
+                key, cmd, convert = row
+                self._pipeline.append(_Queued(_key(key), fn=single, field=cmd, convert=convert))
             else:
-                self._pipeline.append(_Queued(fn=lambda: f(self, *args, **kwargs)))
+                self._pipeline.append(_Queued(fn=single))
             return None
 
         return method
@@ -133,12 +176,14 @@ class RedissonConnection:
 
     def closePipeline(self) -> list:
         """:146-163 -- runs the queued commands in order and returns their results; [] outside a pipeline.
-        Consecutive getBit / setBit commands, over any keys, are one rbx_bitset_stream call.  Every command
-        runs; then the first failure is raised."""
+        Consecutive getBit / setBit commands, over any keys, are one rbx_bitset_stream call; with a bitField of
+        exactly one sub-command among them they are one rbx_bitset_field_stream call.  Every command runs; then
+        the first failure is raised."""
         if self._pipeline is None:
             return []
         queue, self._pipeline = self._pipeline, None
-        results, error = run_queue(queue, lambda *a: bitset_stream_call(self._client, *a))
+        results, error = run_queue(queue, lambda *a: bitset_stream_call(self._client, *a),
+                                   lambda *a: bitset_field_stream_call(self._client, *a))
         if error is not None:
             raise error
         return results
@@ -232,7 +277,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_size(self._client.ctx, nm, C.byref(out)))
         return int(out.value) // 8
 
-    @_pipelined
+    @_pipelined(field=lambda key, subCommands: _one_sub_command(key, subCommands))
     def bitField(self, key: bytes, subCommands) -> list:
         """BITFIELD key sub-commands -> one reply each, None for nil  S:2241-2291.  subCommands: BitFieldGet /
         BitFieldSet / BitFieldIncrBy in order.  A non-zero-based Offset is sent as '#N' = N * bits
@@ -242,26 +287,9 @@ class RedissonConnection:
         cmds = list(subCommands)
         if not cmds:
             return []
-        modes = {"WRAP": L.RBX_OVERFLOW_WRAP, "SAT": L.RBX_OVERFLOW_SAT, "FAIL": L.RBX_OVERFLOW_FAIL}
         arr = (L.RbxFieldCmd * len(cmds))()
         for a, cmd, mode in zip(arr, cmds, resolve_overflow(cmds)):
-            if isinstance(cmd, BitFieldGet):
-                a.op = L.RBX_FIELD_GET
-            elif isinstance(cmd, BitFieldSet):
-                a.op = L.RBX_FIELD_SET
-            elif isinstance(cmd, BitFieldIncrBy):
-                a.op = L.RBX_FIELD_INCRBY
-            else:
-                raise IllegalArgumentException(f"unknown BITFIELD sub-command {cmd!r}")
-            bits = cmd.type.bits
-            offset = cmd.offset.value if cmd.offset.zero_based else cmd.offset.value * bits
-            if not -(1 << 63) <= getattr(cmd, "value", 0) < 1 << 63:
-                raise IllegalArgumentException("field values are Java longs")
-            a.offset = offset if 0 <= offset < 1 << 64 else (1 << 64) - 1  # past the limit either way
-            a.value = getattr(cmd, "value", 0)
-            a.is_signed = int(cmd.type.signed)
-            a.size = bits if 0 <= bits <= 255 else 0  # no such type: Redis's error
-            a.overflow = modes[mode]
+            a.op, a.is_signed, a.size, a.overflow, a.offset, a.value = _field_row(cmd, mode)
         replies = np.zeros(len(cmds), np.int64)
         nil = np.zeros(len(cmds), np.uint8)
         nm, _keep = L.name_struct(_key(key))
