@@ -542,7 +542,8 @@ int rbx_bloom_stream(rbx_ctx *ctx, rbx_bloom *const *filters, uint32_t nfilters,
  * *changed = 1 iff the key was created or any register changed. */
 int rbx_hll_add(rbx_ctx *ctx, const char *name, const rbx_keys *elements, int *changed);
 /* A batch of PFADD commands: segment s adds elements [seg_offsets[s], seg_offsets[s+1])
- * to names[s]; out_changed[s] is the reply of command s (commands apply in order). */
+ * to names[s]; out_changed[s] is the reply of command s (commands apply in order).  A name that holds a key
+ * of another type fails the whole call with RBX_E_WRONGTYPE before any command runs or any key is created. */
 int rbx_hll_add_multi(rbx_ctx *ctx, const char *const *names, uint32_t nseg,
                       const uint64_t *seg_offsets, const rbx_keys *elements, uint8_t *out_changed);
 /* count / countWith -> PFCOUNT k1..kn (union when n > 1)  :84-94 */

@@ -1393,9 +1393,12 @@ class RHyperLogLog(_Expirable):
         if encoding not in self._ENCODINGS:
             raise IllegalArgumentException("encoding must be one of %s" % sorted(self._ENCODINGS))
         n = C.c_uint64()
-        buf = np.zeros(16 + 12288, np.uint8)
+        # a sparse string can be longer than the dense one: the fewest-bytes form of a dense key has up to one opcode
+        # byte per register, a SET string up to 16384 opcodes of two bytes
+        buf = np.zeros(16 + 2 * 16384, np.uint8)
         _check(L.lib().rbx_hll_export_enc(self._client.ctx, self._name.encode(), self._ENCODINGS[encoding],
                                           buf.ctypes.data_as(L.u8p), buf.size, C.byref(n)))
+        assert n.value <= buf.size, "a sparse HLL string holds at most 16384 opcodes"
         return buf[: n.value].tobytes()
 
     def importString(self, data: bytes) -> None:

@@ -226,12 +226,21 @@ int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint6
     std::vector<HllState *> hl(nseg);
     std::vector<std::shared_ptr<HllState>> keep(nseg);
     std::vector<uint8_t> created(nseg, 0);
+    // type-check every name first, as hll_merge does its sources: the call has one return code, so a key of
+    // another type fails it before any missing key is created (the keys named before it were left behind empty)
+    std::vector<uint32_t> missing;
     for (uint32_t s = 0; s < nseg; ++s) {
+        const Entry *e = c->ks.find(names[s]);
+        if (!e) missing.push_back(s);
+        else if (e->type != KType::Hll) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+        else keep[s] = e->hll;
+    }
+    for (uint32_t s : missing) {  // (a missing name given twice: the second finds the key the first created)
         bool cr;
         RBX_TRY(hll_get(c, names[s], true, c->stream, &keep[s], &cr));
-        hl[s] = keep[s].get();
         created[s] = cr;
     }
+    for (uint32_t s = 0; s < nseg; ++s) hl[s] = keep[s].get();
     std::vector<uint32_t> ch(nseg);  // each tier's changed words end up here
     auto reply = [&]() {
         for (uint32_t s = 0; s < nseg; ++s) {
