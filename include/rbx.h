@@ -580,6 +580,48 @@ int rbx_hll_count_n(rbx_ctx *ctx, const rbx_name *names, uint32_t n, uint64_t *o
 int rbx_hll_merge_n(rbx_ctx *ctx, rbx_name dest, const rbx_name *srcs, uint32_t nsrc);
 int rbx_hll_export_enc_n(rbx_ctx *ctx, rbx_name name, int encoding, uint8_t *out, uint64_t cap, uint64_t *len);
 int rbx_hll_import_n(rbx_ctx *ctx, rbx_name name, const uint8_t *bytes, uint64_t len);
+/* An ordered stream of PFADD / single-key PFCOUNT commands over many keys in one call: what a batch queues
+ * through RBatch.getHyperLogLog(name) (M/RedissonBatch.java:57-64, M/api/RBatch.java:213-215: addAsync,
+ * addAllAsync, countAsync), executes in submission order and answers in that order; Spring Data reaches the
+ * same shape with pfAdd / pfCount between openPipeline() and closePipeline().
+ *   Commands  command i is (names[cmd_key[i]], cmd_op[i]).  A PFADD carries the elements [cmd_elem[i],
+ *             cmd_elem[i + 1]) of `elements` (cmd_elem has n + 1 entries; the range may be empty); a PFCOUNT
+ *             names one key and its range is empty.  Two entries of `names` with equal bytes are one key.
+ *   Result    exactly that of n single calls in array order -- rbx_hll_add_multi_n with one segment for a PFADD,
+ *             rbx_hll_count_n with one key for a PFCOUNT.  replies[i] (nullable array) is 1 for a PFADD iff the
+ *             key was created or a register changed, and the cardinality for a PFCOUNT.  A PFADD sees every
+ *             earlier PFADD of its key; the first PFADD that runs on a missing key creates it and replies 1,
+ *             also without elements.  The header's cached cardinality is PFCOUNT's and PFADD's: a PFCOUNT
+ *             returns a valid cache as it stands and stores a recount; a PFADD sets the invalid bit only when
+ *             a register changed, and the low 63 bits stay.  A sparse string takes its key's elements through
+ *             hllSparseSet in command order across all of that key's commands (promotion is sticky, at the
+ *             first value above 32 or at growth past hll-sparse-max-bytes).  Timeouts are kept.
+ *   Failures  the pipelined-batch rule of RBX_E_REDIS above: a command whose key holds another type (a bit
+ *             string, a {name}:config hash) fails alone.  status[i] (nullable array) is 0xFF and its reply 0;
+ *             it changes and creates nothing.  Every other command runs (status 0) with its exact reply.  The
+ *             call returns RBX_E_WRONGTYPE, the code of the first failing command in array order, with the
+ *             HLL wrong-type message in rbx_last_error().
+ *   Caller    cmd_key[i] >= nkeys, cmd_op[i] > 1, offsets that do not ascend or do not span [0, elements->n],
+ *             a PFCOUNT with elements, or a NULL array with n > 0 is RBX_E_ILLEGAL_ARGUMENT with nothing
+ *             changed and nothing created.  n = 0 sends nothing.
+ *   Cost      the host splits the stream into phases: a phase is a maximal stretch in which no PFCOUNT names a
+ *             key that an earlier PFADD of the stretch names.  A phase's PFCOUNTs run first, as one pass over
+ *             the state before it, then its PFADDs as one add run, whose launch count does not depend on how
+ *             often keys repeat.  Adds followed by counts are two phases; add, count, add, count
+ *             on one key is one phase per pair -- a PFCOUNT is a 16,384-register scan either way.
+ *   Scope     multi-key PFCOUNT and PFMERGE stay single calls.  The node router and the Java shim do not
+ *             carry this call.  There is no point-in-time PFCOUNT from inside one launch: a count that must
+ *             see an earlier add of its key closes the phase.
+ * The command arrays, `names`, `replies` and `status` are host memory in both forms: the host must know the
+ * commands to create the keys (as rbx_hll_add_multi_dev's h_seg_offsets).  The _dev form takes `elements` in
+ * device memory and enqueues on `stream` (NULL: the context's); like the two bit streams it is an exception to
+ * the *_dev convention: it waits on the stream, once per add run and count pass and at its end. */
+enum { RBX_HLL_PFADD = 0, RBX_HLL_PFCOUNT = 1 };
+int rbx_hll_stream(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key, const uint8_t *cmd_op,
+                   const uint64_t *cmd_elem, uint64_t n, const rbx_keys *elements, uint64_t *replies, uint8_t *status);
+int rbx_hll_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                       const uint8_t *cmd_op, const uint64_t *cmd_elem, uint64_t n, const rbx_keys *d_elements,
+                       uint64_t *replies, uint8_t *status, void *stream);
 
 /* ---- HLL handles and the device-resident path ------------------------------------- */
 /* Opens (creating an empty HLL if absent and create != 0). */

@@ -50,6 +50,9 @@ int rbx_bench_bitrange_path(uint64_t len, uint64_t n, uint64_t total, uint64_t l
 /* The execution path the last rbx_bitset_field_stream[_dev] call of this process took: 0 none yet, 1 one lane,
  * 2 sorted by (key, word), 3 sorted by key, 4 gather, 5 the compare-and-swap loop. */
 int rbx_bench_fieldstream_last_path(void);
+/* What the last rbx_hll_stream[_dev] call of this process did: out[0] = phases, out[1] = add runs taken by rounds,
+ * out[2] = add runs taken grouped, out[3] = grouped chunks. */
+int rbx_bench_hllstream_last(uint32_t out[4]);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -138,6 +141,14 @@ int rbx_bench_fieldstream_last_path(void);
  *   "fieldstream_serial_max" the auto rule's largest batch for the one lane (default 64, bitstream_serial_max's
  *                           value; the crossover is not measured)
  *   "fieldstream_chunk"     commands per chunk of the sorted paths, 1 .. 2^30 (default 2^25)
+ *   "hllstream_path"        rbx_hll_stream's add runs: 0 auto (default: by rounds, one PFADD launch per maximal run
+ *                           of commands on distinct keys, when the run's rounds R are at most max(1, elements /
+ *                           hllstream_elems_per_round); else grouped, one sort by (key, register) per chunk),
+ *                           1 always by rounds, 2 always grouped; every setting gives the same answers
+ *   "hllstream_chunk"       elements per chunk of the grouped path, 1 .. 2^30 (default 2^25: 36.125 bytes of sort
+ *                           scratch per element, 1.129 GiB); a command with more elements runs by rounds, alone
+ *   "hllstream_elems_per_round"  the auto rule's cost of one round in grouped elements (default 1137, from
+ *                           10.2 us per round and 8.97 ns per grouped element, DESIGN 11.7 row d)
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

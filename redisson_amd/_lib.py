@@ -75,6 +75,7 @@ RBX_BITOP_AND, RBX_BITOP_OR, RBX_BITOP_XOR, RBX_BITOP_NOT = 0, 1, 2, 3
 RBX_FIELD_GET, RBX_FIELD_SET, RBX_FIELD_INCRBY = 0, 1, 2
 RBX_RANGE_BYTE, RBX_RANGE_BIT = 0, 1
 RBX_OVERFLOW_WRAP, RBX_OVERFLOW_SAT, RBX_OVERFLOW_FAIL = 0, 1, 2
+RBX_HLL_PFADD, RBX_HLL_PFCOUNT = 0, 1  # cmd_op of rbx_hll_stream
 
 
 class RbxFieldCmd(C.Structure):
@@ -206,6 +207,10 @@ SIGNATURES = {
     "rbx_pexpire_n": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rbx_hll_add_multi_n": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u64p, C.POINTER(RbxKeys), u8p]),
     "rbx_hll_count_n": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u64p]),
+    "rbx_hll_stream": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, u8p, u64p, C.c_uint64, C.POINTER(RbxKeys),
+                                 u64p, u8p]),
+    "rbx_hll_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, u8p, u64p, C.c_uint64,
+                                     C.POINTER(RbxKeys), u64p, u8p, vp]),
     "rbx_hll_merge_n": (C.c_int, [vp, RbxName, C.POINTER(RbxName), C.c_uint32]),
     "rbx_hll_export_enc_n": (C.c_int, [vp, RbxName, C.c_int, u8p, C.c_uint64, u64p]),
     "rbx_hll_import_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64]),
@@ -257,6 +262,7 @@ SIGNATURES = {
     "rbx_bench_stream_geometry": (C.c_int, [vp, u64p]),
     "rbx_bench_bitrange_path": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "rbx_bench_fieldstream_last_path": (C.c_int, []),
+    "rbx_bench_hllstream_last": (C.c_int, [u32p]),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

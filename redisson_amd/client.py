@@ -851,6 +851,71 @@ def bitset_field_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmd
                                                d_status, stream))
 
 
+PFADD, PFCOUNT = L.RBX_HLL_PFADD, L.RBX_HLL_PFCOUNT  # cmd_op of rbx_hll_stream
+HLL_FAILED = 0xFF  # status of an HLL-stream command that failed alone
+_HLL_WRONGTYPE_MSG = "WRONGTYPE Key is not a valid HyperLogLog string value."
+
+
+def hll_stream_call(client: RedissonClient, names, cmd_key, cmd_op, seg, arena):
+    """rbx_hll_stream over host arrays without raising: (rc, message, replies, status).  names: str or bytes keys;
+    command i is cmd_op[i] (PFADD / PFCOUNT) on names[cmd_key[i]] with the elements [seg[i], seg[i + 1]) of
+    `arena` (an Arena, or a list of bytes).  replies: uint64 (1 / 0 for a PFADD, the cardinality for a PFCOUNT);
+    status: uint8 with 0 = the command ran, 0xFF = it failed alone."""
+    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+    op = np.ascontiguousarray(cmd_op, dtype=np.uint8).reshape(-1)
+    offs = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1)
+    n = key.size
+    if op.size != n or offs.size != n + 1:
+        raise IllegalArgumentException("cmd_key and cmd_op have one entry per command, seg one more")
+    a = arena if isinstance(arena, (Arena, _OneKey)) else Arena([bytes(e) for e in arena])
+    names_arr, _keep = L.names_array(names)
+    out = np.zeros(max(n, 1), np.uint64)
+    status = np.zeros(max(n, 1), np.uint8)
+    rc = L.lib().rbx_hll_stream(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p), op.ctypes.data_as(L.u8p),
+                                offs.ctypes.data_as(L.u64p), n, a.ptr(), out.ctypes.data_as(L.u64p),
+                                status.ctypes.data_as(L.u8p))
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), out[:n], status[:n]
+
+
+_engine_hll_stream_call = hll_stream_call  # (RBatch.__init__ has a parameter of that name)
+
+
+def hll_stream(client: RedissonClient, names, cmd_key, cmd_op, seg, arena):
+    """An ordered stream of PFADD (0) / single-key PFCOUNT (1) commands over many keys in one call
+    (rbx_hll_stream): (replies, status) in order.  Raises the first failing command's exception after every other
+    command has run."""
+    rc, msg, out, status = hll_stream_call(client, names, cmd_key, cmd_op, seg, arena)
+    raise_for(rc, msg)
+    return out, status
+
+
+def hll_stream_dev_call(client: RedissonClient, names, cmd_key, cmd_op, seg, d_elements: L.RbxKeys,
+                        stream: int | None = None):
+    """rbx_hll_stream_dev without raising: (rc, message, replies, status) over device-resident elements
+    (device_keys); the command arrays stay host arrays."""
+    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+    op = np.ascontiguousarray(cmd_op, dtype=np.uint8).reshape(-1)
+    offs = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1)
+    n = key.size
+    if op.size != n or offs.size != n + 1:
+        raise IllegalArgumentException("cmd_key and cmd_op have one entry per command, seg one more")
+    names_arr, _keep = L.names_array(names)
+    out = np.zeros(max(n, 1), np.uint64)
+    status = np.zeros(max(n, 1), np.uint8)
+    rc = L.lib().rbx_hll_stream_dev(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p),
+                                    op.ctypes.data_as(L.u8p), offs.ctypes.data_as(L.u64p), n, C.byref(d_elements),
+                                    out.ctypes.data_as(L.u64p), status.ctypes.data_as(L.u8p), stream)
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), out[:n], status[:n]
+
+
+def hll_stream_dev(client: RedissonClient, names, cmd_key, cmd_op, seg, d_elements: L.RbxKeys,
+                   stream: int | None = None):
+    """hll_stream over device-resident elements: (replies, status); raises as hll_stream does."""
+    rc, msg, out, status = hll_stream_dev_call(client, names, cmd_key, cmd_op, seg, d_elements, stream)
+    raise_for(rc, msg)
+    return out, status
+
+
 class BatchFuture:
     """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
     methods), or raises what the command failed with."""
@@ -877,13 +942,15 @@ class BatchFuture:
 class _Queued:
     """One queued command: a bit command (name, op, index) that coalesces, a field command (name, field =
     (op, signed, size, overflow, offset, value), fn) that coalesces where a field stream call is at hand and
-    runs through fn otherwise, or a callable that runs singly.  convert: applied to a field command's reply."""
+    runs through fn otherwise, an HLL command (name, hll = (PFADD, [element bytes]) or (PFCOUNT, []), fn) that
+    coalesces where an HLL stream call is at hand and runs through fn otherwise, or a callable that runs singly.
+    convert: applied to a field or HLL command's reply."""
 
-    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert")
+    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll")
 
-    def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None):
+    def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None):
         self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
-        self.field, self.convert = field, convert
+        self.field, self.convert, self.hll = field, convert, hll
 
     def as_field(self):
         """the command as a BITFIELD sub-command: GETBIT / SETBIT are GET / SET of a u1, which leave the same
@@ -945,20 +1012,60 @@ def _run_fields(run, field_stream_call):
     return first_error
 
 
-def run_queue(queue, stream_call, field_stream_call=None):
+def _run_hll(run, hll_stream_call):
+    """one HLL stream call for a run of PFADD / PFCOUNT commands; sets every future, returns the first error"""
+    ids: dict = {}
+    keys = [ids.setdefault(c.name, len(ids)) for c in run]
+    seg, elements = [0], []
+    for c in run:
+        elements.extend(c.hll[1])
+        seg.append(len(elements))
+    rc, msg, replies, status = hll_stream_call(list(ids), keys, [c.hll[0] for c in run], seg, elements)
+    if rc not in (L.RBX_OK, L.RBX_E_WRONGTYPE):  # the run as a whole was refused
+        try:
+            raise_for(rc, msg)
+        except RedissonAmdError as e:
+            for c in run:
+                c.future._set(error=e)
+            return e
+    first_error = None
+    for c, r, s in zip(run, replies, status):
+        if int(s) == HLL_FAILED:
+            c.future._set(error=RedisException(_HLL_WRONGTYPE_MSG))
+        else:
+            value = bool(r) if c.hll[0] == PFADD else int(r)
+            c.future._set(c.convert(value) if c.convert else value)
+        first_error = first_error or c.future._error
+    return first_error
+
+
+def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None):
     """Executes queued commands in submission order.  Every maximal run of consecutive bit commands, over any
     keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies).  With a
     field_stream_call, field commands join the runs, and a run that holds at least one of them is ONE
     field_stream_call(names, cmd_key, cmds) -> (rc, message, replies, status) in which the bit commands travel as
-    u1 GET / SET.  Every other command runs through its own call at its position.  Each command's future is
-    set; returns (responses, first error)."""
+    u1 GET / SET.  With an hll_stream_call, every maximal run of consecutive PFADD / single-key PFCOUNT commands,
+    over any keys, is ONE hll_stream_call(names, cmd_key, cmd_op, seg, elements) -> (rc, message, replies,
+    status); bit and field runs and HLL runs never mix, and each closes the other.  Every other command runs
+    through its own call at its position.  Each command's future is set; returns (responses, first error)."""
     def joins(q):
         return q.op is not None or (q.field is not None and field_stream_call is not None)
+
+    def joins_hll(q):
+        return q.hll is not None and hll_stream_call is not None
 
     first_error = None
     i = 0
     while i < len(queue):
         q = queue[i]
+        if joins_hll(q):
+            j = i
+            while j < len(queue) and joins_hll(queue[j]):
+                j += 1
+            error = _run_hll(queue[i:j], hll_stream_call)  # (runs whether or not an earlier command failed)
+            first_error = first_error or error
+            i = j
+            continue
         if not joins(q):
             try:
                 q.future._set(q.fn())
@@ -1146,18 +1253,65 @@ class RBatchBitSet:
     clear_async = clearAsync
 
 
+class RBatchHyperLogLog:
+    """RBatch.getHyperLogLog(name) (M/RedissonBatch.java:57-64): RHyperLogLogAsync, every method queued.
+    addAsync / addAllAsync / countAsync of consecutive commands, over any keys, travel together (one
+    rbx_hll_stream call); countWithAsync with other names and mergeWithAsync run through RHyperLogLog's own call
+    at their position."""
+
+    def __init__(self, batch: "RBatch", name: str, codec: Codec):
+        self._batch, self._name, self._codec = batch, name, codec
+
+    def _single(self, method: str, *args) -> BatchFuture:
+        hll, name = self._batch._hyperloglog, self._name
+        return self._batch._add(_Queued(fn=lambda: getattr(hll(name, self._codec), method)(*args)))
+
+    def addAsync(self, obj) -> BatchFuture:
+        return self.addAllAsync([obj])
+
+    def addAllAsync(self, objects) -> BatchFuture:
+        elements = [self._codec.encode(o) for o in objects]
+        hll, name = self._batch._hyperloglog, self._name
+        return self._batch._add(_Queued(name, fn=lambda: hll(name, self._codec).addAll(Arena(elements)),
+                                        hll=(PFADD, elements)))
+
+    def countAsync(self) -> BatchFuture:
+        hll, name = self._batch._hyperloglog, self._name
+        return self._batch._add(_Queued(name, fn=lambda: hll(name, self._codec).count(), hll=(PFCOUNT, [])))
+
+    def countWithAsync(self, *otherLogNames: str) -> BatchFuture:
+        if not otherLogNames:
+            return self.countAsync()
+        return self._single("countWith", *otherLogNames)
+
+    def mergeWithAsync(self, *otherLogNames: str) -> BatchFuture:
+        return self._single("mergeWith", *otherLogNames)
+
+    add_async = addAsync
+    add_all_async = addAllAsync
+    count_async = countAsync
+    count_with_async = countWithAsync
+    merge_with_async = mergeWithAsync
+
+
 class RBatch:
     """RedissonClient.createBatch() (M/RedissonBatch.java): commands queue across any number of keys, execute()
     runs them in submission order (M/command/CommandBatchService.java:115-134,335) and returns their replies
-    in that order.  stream_call / bitset / field_stream_call replace the engine's calls (tests); without a
-    client and without a field_stream_call, field commands run singly through bitset(name)."""
+    in that order.  stream_call / bitset / field_stream_call / hll_stream_call / hyperloglog replace the engine's
+    calls (tests); without a client and without a field_stream_call (an hll_stream_call), field (HLL) commands
+    run singly through bitset(name) (hyperloglog(name, codec))."""
 
-    def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None, field_stream_call=None):
+    def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None, field_stream_call=None,
+                 hll_stream_call=None, hyperloglog=None):
         self._client = client
         self._stream_call = stream_call or (lambda *a: bitset_stream_call(client, *a))
         if field_stream_call is None and client is not None:
             field_stream_call = lambda *a: bitset_field_stream_call(client, *a)  # noqa: E731
         self._field_stream_call = field_stream_call
+        if hll_stream_call is None and client is not None:
+            hll_stream_call = lambda *a: _engine_hll_stream_call(client, *a)  # noqa: E731
+        self._hll_stream_call = hll_stream_call
+        self._hyperloglog = hyperloglog or (lambda name, codec: RHyperLogLog(client, name, codec))
         self._bitset = bitset or (lambda name: RBitSet(client, name))
         self._queue: list = []
         self._executed = False
@@ -1171,12 +1325,15 @@ class RBatch:
     def getBitSet(self, name: str) -> RBatchBitSet:
         return RBatchBitSet(self, name)
 
+    def getHyperLogLog(self, name: str, codec: Codec | None = None) -> RBatchHyperLogLog:
+        return RBatchHyperLogLog(self, name, codec or DEFAULT_CODEC)
+
     def execute(self) -> BatchResult:
         """Every command runs, the ones after a failed one too; then the first failure is raised."""
         if self._executed:
             raise IllegalStateException("Batch already executed!")
         self._executed = True
-        responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call)
+        responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call, self._hll_stream_call)
         if error is not None:
             raise error
         return BatchResult(responses)
@@ -1187,6 +1344,7 @@ class RBatch:
         self._queue.clear()
 
     get_bit_set = getBitSet
+    get_hyper_log_log = getHyperLogLog
 
 
 class BloomHandle:

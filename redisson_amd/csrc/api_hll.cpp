@@ -155,7 +155,7 @@ static int replay_merge(rbx_ctx *c, const std::vector<HllState *> &hl, hipStream
     for (HllState *h : hl)
         if (h && !h->dense && !seen.count(h)) {
             seen[h] = 1;
-            items.push_back(HllReplay{h->d_sp_ops, h->d_promoted, h->d_regs, 0, 0, h->d_regs});
+            items.push_back(HllReplay{h->d_sp_ops, h->d_promoted, h->d_regs, 0, 0, h->d_regs, nullptr, 0});
         }
     return replay_sparse(c, items, KeysDev{}, 0, st);
 }
@@ -171,9 +171,11 @@ static int resolve_dense(rbx_ctx *c, HllState *h) {
 }
 
 // PFADD batch: device elements, commands in order.  Commands naming the same HLL are
-// split into successive launches so each reply sees the previous commands' effect.
-static int pfadd_run(rbx_ctx *c, const std::vector<HllState *> &hl, const uint64_t *h_seg, const KeysDev &dk,
-                     uint32_t *d_changed, hipStream_t st, TinyArena *ta = nullptr) {
+// split into successive launches so each reply sees the previous commands' effect.  Command s adds the
+// elements [h_beg[s], h_end[s]) and reports under d_changed[seg_id ? seg_id[s] : s].
+static int pfadd_run(rbx_ctx *c, const std::vector<HllState *> &hl, const uint64_t *h_beg, const uint64_t *h_end,
+                     const uint32_t *seg_id, const KeysDev &dk, uint32_t *d_changed, hipStream_t st,
+                     TinyArena *ta = nullptr) {
     const uint32_t nseg = (uint32_t)hl.size();
     std::vector<HllSeg> tiles;
     uint32_t s0 = 0;
@@ -185,8 +187,8 @@ static int pfadd_run(rbx_ctx *c, const std::vector<HllState *> &hl, const uint64
         while (s1 < nseg && !seen.count(hl[s1])) seen[hl[s1++]] = 1;
         tiles.clear();
         for (uint32_t s = s0; s < s1; ++s) {
-            for (uint64_t b = h_seg[s]; b < h_seg[s + 1]; b += kTileElems)
-                tiles.push_back(HllSeg{hl[s]->d_regs, b, std::min(h_seg[s + 1], b + kTileElems), s, 0});
+            for (uint64_t b = h_beg[s]; b < h_end[s]; b += kTileElems)
+                tiles.push_back(HllSeg{hl[s]->d_regs, b, std::min(h_end[s], b + kTileElems), seg_id ? seg_id[s] : s, 0});
         }
         if (!tiles.empty()) {
             // a tiny call's tile list is read from the coherent block (each round its own copy)
@@ -202,9 +204,9 @@ static int pfadd_run(rbx_ctx *c, const std::vector<HllState *> &hl, const uint64
             HIP_TRY(hipGetLastError());
             std::vector<HllReplay> items;  // the round's HLLs are distinct
             for (uint32_t s = s0; s < s1; ++s)
-                if (!hl[s]->dense && h_seg[s + 1] > h_seg[s])
-                    items.push_back(HllReplay{hl[s]->d_sp_ops, hl[s]->d_promoted, nullptr, h_seg[s], h_seg[s + 1],
-                                              hl[s]->d_regs});
+                if (!hl[s]->dense && h_end[s] > h_beg[s])
+                    items.push_back(HllReplay{hl[s]->d_sp_ops, hl[s]->d_promoted, nullptr, h_beg[s], h_end[s],
+                                              hl[s]->d_regs, nullptr, 0});
             RBX_TRY(replay_sparse(c, items, dk, fl, st, ta));
         }
         s0 = s1;
@@ -255,8 +257,8 @@ int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint6
         memset(ch_h, 0, (size_t)nseg * 4);
         const KeysDev dk = tiny_stage(c, elements);
         TinyArena ta{sg.tiny() + kTinyArenaAt, sg.pin_tiny_dev + kTinyArenaAt, kTinyArenaBytes, 0};
-        RBX_TRY(tiny_done(c, pfadd_run(c, hl, seg_offsets, dk, (uint32_t *)(sg.pin_tiny_dev + kTinySegAt), c->stream,
-                                       &ta),
+        RBX_TRY(tiny_done(c, pfadd_run(c, hl, seg_offsets, seg_offsets + 1, nullptr, dk,
+                                       (uint32_t *)(sg.pin_tiny_dev + kTinySegAt), c->stream, &ta),
                           g_tune.tiny_spin));
         memcpy(ch.data(), ch_h, (size_t)nseg * 4);
         return reply();
@@ -265,7 +267,7 @@ int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint6
         // one transfer for the elements and the zeroed changed words, one readback (bloom_host_small)
         SmallStage sm;
         RBX_TRY(small_stage(c, elements, nseg * 4, &sm));
-        const int rc = pfadd_run(c, hl, seg_offsets, sm.dk, (uint32_t *)sm.dp, c->stream);
+        const int rc = pfadd_run(c, hl, seg_offsets, seg_offsets + 1, nullptr, sm.dk, (uint32_t *)sm.dp, c->stream);
         (void)hipEventRecord(sg.ev_done[0], c->stream);
         if (rc != RBX_OK) return small_fail(c, rc);
         HIP_TRY(hipMemcpyAsync(sm.hp, sm.dp, nseg * 4, hipMemcpyDeviceToHost, c->stream));
@@ -290,7 +292,7 @@ int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint6
         std::vector<uint64_t> reb(s1 - s0 + 1);
         for (uint32_t s = s0; s <= s1; ++s) reb[s - s0] = seg_offsets[s] - e0;
         std::vector<HllState *> grp(hl.begin() + s0, hl.begin() + s1);
-        RBX_TRY(pfadd_run(c, grp, reb.data(), dk, d_changed + s0, c->stream));
+        RBX_TRY(pfadd_run(c, grp, reb.data(), reb.data() + 1, nullptr, dk, d_changed + s0, c->stream));
         s0 = s1;
     }
     HIP_TRY(hipMemcpyAsync(ch.data(), d_changed, nseg * 4, hipMemcpyDeviceToHost, c->stream));
@@ -339,20 +341,20 @@ static uint64_t hll_count_from_histo(const int *reghisto) {
     return (uint64_t)E;
 }
 
-// Computes counts for raw register arrays (device pointers) -> host out.
-static int count_regs(rbx_ctx *c, const std::vector<uint8_t *> &regs, uint64_t *out) {
+// Computes counts for raw register arrays (device pointers) -> host out, on `st` (waited for).
+static int count_regs(rbx_ctx *c, const std::vector<uint8_t *> &regs, uint64_t *out, hipStream_t st) {
     uint32_t n = (uint32_t)regs.size();
     if (!n) return RBX_OK;
     SharedScratch &sh = c->dev->shared;
     RBX_TRY(sh.ptrs.reserve(n * sizeof(uint8_t *)));
     RBX_TRY(sh.histo.reserve((size_t)n * 64 * sizeof(int)));
     RBX_TRY(sh.misc.reserve(n * 8));
-    HIP_TRY(hipMemcpyAsync(sh.ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-    launch_hll_count(sh.ptrs.as<uint8_t *>(), n, sh.histo.as<int>(), sh.misc.as<unsigned long long>(), c->stream);
+    HIP_TRY(hipMemcpyAsync(sh.ptrs.p, regs.data(), n * sizeof(uint8_t *), hipMemcpyHostToDevice, st));
+    launch_hll_count(sh.ptrs.as<uint8_t *>(), n, sh.histo.as<int>(), sh.misc.as<unsigned long long>(), st);
     HIP_TRY(hipGetLastError());
     std::vector<unsigned long long> res(n);
-    HIP_TRY(hipMemcpyAsync(res.data(), sh.misc.p, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(res.data(), sh.misc.p, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     std::vector<int> h;
     for (uint32_t i = 0; i < n; ++i) {
         if (res[i] == ~0ULL) {  // tau branch: histogram to host, glibc pow
@@ -368,7 +370,7 @@ static int count_regs(rbx_ctx *c, const std::vector<uint8_t *> &regs, uint64_t *
 }
 
 // single-key PFCOUNT with the header cache (valid cache -> cached value; else compute+store)
-static int pfcount_each(rbx_ctx *c, const std::vector<HllState *> &hl, uint64_t *out) {
+static int pfcount_each(rbx_ctx *c, const std::vector<HllState *> &hl, uint64_t *out, hipStream_t st) {
     std::vector<uint8_t *> regs;
     std::vector<uint32_t> idx;
     for (uint32_t i = 0; i < hl.size(); ++i) {
@@ -384,7 +386,7 @@ static int pfcount_each(rbx_ctx *c, const std::vector<HllState *> &hl, uint64_t 
         idx.push_back(i);
     }
     std::vector<uint64_t> r(regs.size());
-    RBX_TRY(count_regs(c, regs, r.data()));
+    RBX_TRY(count_regs(c, regs, r.data(), st));
     for (size_t j = 0; j < idx.size(); ++j) {
         out[idx[j]] = r[j];
         hl[idx[j]]->card = r[j];  // store the (valid) cached cardinality
@@ -401,7 +403,358 @@ static int hll_count_each(rbx_ctx *c, const std::vector<std::string> &names, uin
         RBX_TRY(hll_get(c, names[i], false, c->stream, &keep[i], nullptr));
         hl[i] = keep[i].get();
     }
-    return pfcount_each(c, hl, out);
+    return pfcount_each(c, hl, out, c->stream);
+}
+
+// ---- the ordered PFADD / PFCOUNT stream over many keys (RBatch.getHyperLogLog, M/RedissonBatch.java:57-64) ----
+// DESIGN 11.7.  The commands are host arrays, so the host walks them: it finds the commands that fail alone,
+// creates the keys, splits the stream into phases and picks each add run's path.
+static std::atomic<uint32_t> g_hllstream_last[4];  // rbx_bench_hllstream_last shows them
+enum { kHsPhases = 0, kHsRoundsRuns = 1, kHsGroupedRuns = 2, kHsChunks = 3 };
+
+static int significant_bits32(uint32_t v) {
+    int b = 0;
+    while (b < 32 && (v >> b)) ++b;
+    return b;
+}
+
+// The keys of one stream call.  Equal names are one key, known by its first entry (its canonical id); a key
+// of another type fails its commands.
+struct HsKeys {
+    std::vector<uint32_t> canon;
+    std::vector<uint8_t> wrong;                  // per entry of names
+    std::vector<std::shared_ptr<HllState>> hll;  // per canonical id; null = missing
+    std::vector<uint64_t> stamp, round;          // per canonical id: the phase of its last PFADD, its last round
+    std::vector<uint32_t> slot;                  // per canonical id: its place among a chunk's sparse keys + 1
+    bool any_wrong = false;
+};
+
+static int hll_stream_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                            const uint8_t *cmd_op, const uint64_t *cmd_elem, uint64_t n, const rbx_keys *elements) {
+    if (!c || (nkeys && !names) || (n && (!cmd_key || !cmd_op || !cmd_elem || !elements)))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (uint32_t i = 0; i < nkeys; ++i)
+        if (!names[i].bytes && names[i].len) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
+    if (n == 0) return RBX_OK;
+    RBX_TRY(validate_keys(elements));
+    if (n >= (1ULL << 32)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes fewer than 2^32 commands");
+    if (cmd_elem[0] != 0 || cmd_elem[n] != elements->n)
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "element offsets must span [0, elements->n]");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (cmd_key[i] >= nkeys) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys");
+        if (cmd_op[i] > RBX_HLL_PFCOUNT) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's op is not RBX_HLL_PFADD or RBX_HLL_PFCOUNT");
+        if (cmd_elem[i + 1] < cmd_elem[i]) return fail(RBX_E_ILLEGAL_ARGUMENT, "element offsets must be ascending");
+        if (cmd_op[i] == RBX_HLL_PFCOUNT && cmd_elem[i + 1] != cmd_elem[i])
+            return fail(RBX_E_ILLEGAL_ARGUMENT, "a PFCOUNT carries no elements");
+    }
+    return RBX_OK;
+}
+
+// What one call carries through its phases.  Element g of the call is element g - elem_base of `dk`.
+struct HsCall {
+    rbx_ctx *c;
+    hipStream_t st;
+    HsKeys keys;
+    const uint32_t *cmd_key;
+    const uint8_t *cmd_op;
+    const uint64_t *cmd_elem;
+    const HllKey *d_tab;
+    const uint64_t *d_cmd_elem;
+    const uint32_t *d_cmd_key;
+    uint32_t *d_changed;
+    uint32_t nkeys;
+    uint64_t n;
+    std::vector<uint8_t> created;  // per command: this PFADD created its key
+    uint64_t *replies;
+    KeysDev dk;
+    uint64_t elem_base;
+    uint64_t phase = 0, rounds = 0;
+    uint32_t stats[4] = {0, 0, 0, 0};
+    HllState *hll_of(uint64_t i) const { return keys.hll[keys.canon[cmd_key[i]]].get(); }
+    bool failed(uint64_t i) const { return keys.wrong[cmd_key[i]] != 0; }
+    bool adds(uint64_t i) const { return cmd_op[i] == RBX_HLL_PFADD && !failed(i); }
+};
+
+// the commands [a, b) by rounds: the PFADDs that run and carry elements, through pfadd_run
+static int hs_rounds(HsCall &h, uint64_t a, uint64_t b) {
+    std::vector<HllState *> hl;
+    std::vector<uint64_t> beg, end;
+    std::vector<uint32_t> id;
+    for (uint64_t i = a; i < b; ++i)
+        if (h.adds(i) && h.cmd_elem[i + 1] > h.cmd_elem[i]) {
+            hl.push_back(h.hll_of(i));
+            beg.push_back(h.cmd_elem[i] - h.elem_base);
+            end.push_back(h.cmd_elem[i + 1] - h.elem_base);
+            id.push_back((uint32_t)i);
+        }
+    if (hl.empty()) return RBX_OK;
+    return pfadd_run(h.c, hl, beg.data(), end.data(), id.data(), h.dk, h.d_changed, h.st);
+}
+
+// One grouped chunk: the commands [a, b), m = cmd_elem[b] - cmd_elem[a] elements in 1 .. hllstream_chunk.
+// Registers first (pairs, sort, runs); then, the registers final, one replay launch for the chunk's sparse
+// keys, each over its own elements in command order across all of its commands.
+static int hs_grouped_chunk(HsCall &h, uint64_t a, uint64_t b, int key_bits) {
+    rbx_ctx *c = h.c;
+    HllStreamScratch &ss = c->dev->hll.strm;
+    const uint64_t e0 = h.cmd_elem[a], first = e0 - h.elem_base;
+    const uint32_t m = (uint32_t)(h.cmd_elem[b] - e0);
+    const int fl = fast_len_hll(h.dk);
+    size_t scratch = 0;
+    int e = hllstream_grouped_scratch_bytes(m, (kHsKeyShift - kHsRegShift) + key_bits + (h.keys.any_wrong ? 1 : 0), &scratch);
+    if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+    RBX_TRY(ss.sort.reserve(scratch));
+    e = launch_hllstream_grouped(h.dk, fl, first, e0, m, h.d_tab, h.d_cmd_elem, h.d_cmd_key, a, (uint32_t)(b - a),
+                                 h.d_changed, key_bits, h.keys.any_wrong, ss.sort.p, ss.sort.cap, h.st);
+    if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipGetLastError());
+    // the sparse keys' element lists: count, place, fill
+    std::vector<uint32_t> skeys;   // canonical ids of the chunk's sparse keys, in order of first appearance
+    std::vector<uint64_t> count;   // their elements
+    for (uint64_t i = a; i < b; ++i) {
+        if (!h.adds(i) || h.cmd_elem[i + 1] == h.cmd_elem[i] || h.hll_of(i)->dense) continue;
+        const uint32_t k = h.keys.canon[h.cmd_key[i]];
+        if (!h.keys.slot[k]) {
+            skeys.push_back(k);
+            count.push_back(0);
+            h.keys.slot[k] = (uint32_t)skeys.size();
+        }
+        count[h.keys.slot[k] - 1] += h.cmd_elem[i + 1] - h.cmd_elem[i];
+    }
+    if (skeys.empty()) return RBX_OK;
+    std::vector<uint64_t> at(skeys.size() + 1, 0);
+    for (size_t j = 0; j < skeys.size(); ++j) at[j + 1] = at[j] + count[j];
+    std::vector<uint32_t> list(at.back());
+    std::vector<uint64_t> fill(at.begin(), at.end() - 1);
+    for (uint64_t i = a; i < b; ++i) {
+        if (!h.adds(i) || h.cmd_elem[i + 1] == h.cmd_elem[i]) continue;
+        const uint32_t sl = h.keys.slot[h.keys.canon[h.cmd_key[i]]];
+        if (!sl) continue;
+        uint64_t &w = fill[sl - 1];
+        for (uint64_t g = h.cmd_elem[i]; g < h.cmd_elem[i + 1]; ++g) list[w++] = (uint32_t)(g - e0);
+    }
+    RBX_TRY(ss.lists.reserve(list.size() * 4));
+    HIP_TRY(hipMemcpyAsync(ss.lists.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, h.st));
+    std::vector<HllReplay> items;
+    for (size_t j = 0; j < skeys.size(); ++j) {
+        HllState *s = h.keys.hll[skeys[j]].get();
+        h.keys.slot[skeys[j]] = 0;
+        items.push_back(HllReplay{s->d_sp_ops, s->d_promoted, nullptr, at[j], at[j + 1], s->d_regs,
+                                  ss.lists.as<uint32_t>(), first});
+    }
+    return replay_sparse(c, items, h.dk, fl, h.st);
+}
+
+// One phase, the commands [p0, p1): its PFCOUNTs as one pass over the state before it, then its PFADDs as one
+// add run, then the run's one readback (the changed words and the sparse keys' promotion words).
+static int hs_phase(HsCall &h, uint64_t p0, uint64_t p1) {
+    rbx_ctx *c = h.c;
+    HllStreamScratch &ss = c->dev->hll.strm;
+    h.stats[kHsPhases]++;
+    std::vector<HllState *> hl;
+    std::vector<uint64_t> at;
+    uint64_t nadd = 0, elems = 0, runs = 1;
+    h.rounds++;
+    for (uint64_t i = p0; i < p1; ++i) {
+        if (h.failed(i)) continue;
+        if (h.cmd_op[i] == RBX_HLL_PFCOUNT) {
+            hl.push_back(h.hll_of(i));
+            at.push_back(i);
+        } else if (h.cmd_elem[i + 1] > h.cmd_elem[i]) {
+            // the greedy rule of pfadd_run: a command on a key of the current round opens the next one
+            uint64_t &r = h.keys.round[h.keys.canon[h.cmd_key[i]]];
+            if (r == h.rounds) {
+                h.rounds++;
+                runs++;
+            }
+            r = h.rounds;
+            nadd++;
+            elems += h.cmd_elem[i + 1] - h.cmd_elem[i];
+        }
+    }
+    if (!hl.empty()) {
+        std::vector<uint64_t> out(hl.size());
+        RBX_TRY(pfcount_each(c, hl, out.data(), h.st));
+        if (h.replies)
+            for (size_t j = 0; j < at.size(); ++j) h.replies[at[j]] = out[j];
+    }
+    std::vector<uint32_t> ch;
+    if (nadd) {
+        const int tuned = g_tune.hllstream_path;
+        const uint64_t per_round = g_tune.hllstream_elems_per_round, chunk = g_tune.hllstream_chunk;
+        const bool grouped = tuned == 2 || (tuned == 0 && runs > std::max<uint64_t>(1, elems / per_round));
+        if (!grouped) {
+            h.stats[kHsRoundsRuns]++;
+            RBX_TRY(hs_rounds(h, p0, p1));
+        } else {
+            h.stats[kHsGroupedRuns]++;
+            const int key_bits = significant_bits32(h.nkeys - 1);
+            for (uint64_t a = p0; a < p1;) {
+                // the commands [a, b) whose elements fit one chunk; a command that does not goes by rounds, alone
+                uint64_t b = a;
+                while (b < p1 && h.cmd_elem[b + 1] - h.cmd_elem[a] <= chunk) ++b;
+                if (b == a) {
+                    RBX_TRY(hs_rounds(h, a, a + 1));
+                    b = a + 1;
+                } else if (h.cmd_elem[b] > h.cmd_elem[a]) {
+                    h.stats[kHsChunks]++;
+                    RBX_TRY(hs_grouped_chunk(h, a, b, key_bits));
+                }
+                a = b;
+            }
+        }
+        // the sparse keys of the run: the host learns their promotions here, so that a key promoted by this run
+        // costs the next one no element list and no replay block
+        std::vector<uint32_t *> states;
+        std::vector<HllState *> sparse;
+        for (uint64_t i = p0; i < p1; ++i) {
+            if (!h.adds(i) || h.cmd_elem[i + 1] == h.cmd_elem[i]) continue;
+            const uint32_t k = h.keys.canon[h.cmd_key[i]];
+            HllState *s = h.keys.hll[k].get();
+            if (s->dense || h.keys.slot[k]) continue;
+            h.keys.slot[k] = 1;
+            states.push_back(s->d_promoted);
+            sparse.push_back(s);
+        }
+        for (uint64_t i = p0; i < p1; ++i) h.keys.slot[h.keys.canon[h.cmd_key[i]]] = 0;
+        std::vector<uint32_t> promoted(states.size());
+        uint32_t *d_promoted = h.d_changed + h.n;
+        if (!states.empty()) {
+            RBX_TRY(ss.ptrs.reserve(states.size() * sizeof(uint32_t *)));
+            HIP_TRY(hipMemcpyAsync(ss.ptrs.p, states.data(), states.size() * sizeof(uint32_t *), hipMemcpyHostToDevice, h.st));
+            launch_hllstream_promoted(ss.ptrs.as<uint32_t *>(), (uint32_t)states.size(), d_promoted, h.st);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(promoted.data(), d_promoted, states.size() * 4, hipMemcpyDeviceToHost, h.st));
+        }
+        ch.resize(p1 - p0);
+        HIP_TRY(hipMemcpyAsync(ch.data(), h.d_changed + p0, (p1 - p0) * 4, hipMemcpyDeviceToHost, h.st));
+        HIP_TRY(hipStreamSynchronize(h.st));
+        for (size_t j = 0; j < sparse.size(); ++j)
+            if (promoted[j]) sparse[j]->dense = true;
+    }
+    for (uint64_t i = p0; i < p1; ++i) {
+        if (!h.adds(i)) continue;
+        const bool changed = !ch.empty() && ch[i - p0];
+        if (changed) h.hll_of(i)->card |= 1ULL << 63;  // HLL_INVALIDATE_CACHE
+        if (h.replies) h.replies[i] = changed || h.created[i];
+    }
+    return RBX_OK;
+}
+
+// the commands [g0, g1) over the elements of h.dk: a phase is a maximal stretch in which no PFCOUNT names a key
+// that an earlier PFADD of the stretch names
+static int hs_phases(HsCall &h, uint64_t g0, uint64_t g1) {
+    for (uint64_t p0 = g0; p0 < g1;) {
+        h.phase++;
+        uint64_t p1 = p0;
+        for (; p1 < g1; ++p1) {
+            if (h.failed(p1)) continue;
+            uint64_t &s = h.keys.stamp[h.keys.canon[h.cmd_key[p1]]];
+            if (h.cmd_op[p1] == RBX_HLL_PFADD) s = h.phase;
+            else if (s == h.phase) break;
+        }
+        RBX_TRY(hs_phase(h, p0, p1));
+        p0 = p1;
+    }
+    return RBX_OK;
+}
+
+// rbx_hll_stream[_dev] behind the argument checks, n > 0.  dev: `elements` is device memory (else it is uploaded
+// in groups of whole commands, as hll_add_multi uploads its segments).
+static int hll_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key, const uint8_t *cmd_op,
+                      const uint64_t *cmd_elem, uint64_t n, const rbx_keys *elements, uint64_t *replies, uint8_t *status,
+                      bool dev, hipStream_t st) {
+    RBX_ENTER(c, st);
+    HsCall h{};
+    h.c = c;
+    h.st = st;
+    h.cmd_key = cmd_key;
+    h.cmd_op = cmd_op;
+    h.cmd_elem = cmd_elem;
+    h.nkeys = nkeys;
+    h.n = n;
+    h.replies = replies;
+    HsKeys &K = h.keys;
+    K.canon.resize(nkeys);
+    K.wrong.assign(nkeys, 0);
+    K.hll.resize(nkeys);
+    K.stamp.assign(nkeys, 0);
+    K.round.assign(nkeys, 0);
+    K.slot.assign(nkeys, 0);
+    std::vector<std::string> nm(nkeys);
+    {
+        std::unordered_map<std::string, uint32_t> first;
+        first.reserve(nkeys);
+        for (uint32_t i = 0; i < nkeys; ++i) {
+            nm[i] = name_of(names[i]);
+            K.canon[i] = first.emplace(nm[i], i).first->second;
+            if (K.canon[i] != i) {
+                K.wrong[i] = K.wrong[K.canon[i]];
+                continue;
+            }
+            const Entry *e = c->ks.find(nm[i]);
+            if (e && e->type != KType::Hll) K.wrong[i] = 1, K.any_wrong = true;
+            else if (e) K.hll[i] = e->hll;
+        }
+    }
+    // the commands that fail alone, and the keys the others create: the first PFADD that runs on a missing key
+    uint64_t first_failed = ~0ULL;
+    h.created.assign(n, 0);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (replies) replies[i] = 0;
+        if (status) status[i] = h.failed(i) ? 0xFF : 0;
+        if (h.failed(i)) {
+            first_failed = std::min(first_failed, i);
+            continue;
+        }
+        const uint32_t k = K.canon[cmd_key[i]];
+        if (cmd_op[i] == RBX_HLL_PFADD && !K.hll[k]) {
+            bool cr;
+            RBX_TRY(hll_get(c, nm[k], true, st, &K.hll[k], &cr));
+            h.created[i] = cr;
+        }
+    }
+    HllStreamScratch &ss = c->dev->hll.strm;
+    std::vector<HllKey> tab(nkeys);
+    for (uint32_t i = 0; i < nkeys; ++i) {
+        const uint32_t k = K.canon[i];
+        tab[i] = HllKey{K.hll[k] ? K.hll[k]->d_regs : nullptr, K.wrong[i] ? (kHllKeyWrong | kHllKeyFailed) : 0u, k};
+    }
+    h.d_tab = ss.keys.sync(tab, st);
+    if (!h.d_tab) return ss.keys.err;
+    // the call's element offsets and keys, and one zeroed changed word per command (+ the promotion words)
+    RBX_TRY(ss.cmds.reserve((n + 1) * 8 + n * 4));
+    RBX_TRY(ss.changed.reserve((n + nkeys) * 4));
+    h.d_cmd_elem = ss.cmds.as<uint64_t>();
+    h.d_cmd_key = (const uint32_t *)(h.d_cmd_elem + n + 1);
+    h.d_changed = ss.changed.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync((void *)h.d_cmd_elem, cmd_elem, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void *)h.d_cmd_key, cmd_key, n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h.d_changed, 0, n * 4, st));
+    if (dev) {
+        h.dk = keys_dev(elements);
+        h.elem_base = 0;
+        RBX_TRY(hs_phases(h, 0, n));
+    } else {
+        auto span_bytes = [&](uint64_t e0, uint64_t e1) {
+            return elements->offsets ? elements->offsets[e1] - elements->offsets[e0] : (e1 - e0) * elements->stride;
+        };
+        const uint64_t budget = 256ull << 20;
+        for (uint64_t g0 = 0; g0 < n;) {
+            // commands [g0, g1) whose elements fit one staging upload (at least one command)
+            uint64_t g1 = g0 + 1;
+            while (g1 < n && span_bytes(cmd_elem[g0], cmd_elem[g1 + 1]) <= budget) ++g1;
+            h.dk = KeysDev{};
+            h.elem_base = cmd_elem[g0];
+            if (cmd_elem[g1] > cmd_elem[g0]) RBX_TRY(upload_keys(c, elements, cmd_elem[g0], cmd_elem[g1], &h.dk));
+            RBX_TRY(hs_phases(h, g0, g1));
+            g0 = g1;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < 4; ++i) g_hllstream_last[i] = h.stats[i];
+    if (first_failed != ~0ULL) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+    return RBX_OK;
 }
 
 // PFCOUNT k1..kn: one key = the cached single-key count; several = count of the union
@@ -430,7 +783,7 @@ int hll_count(rbx_ctx *c, const std::vector<std::string> &names, uint64_t *out) 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<uint8_t *> u{merged.as<uint8_t>()};
-    return count_regs(c, u, out);
+    return count_regs(c, u, out, c->stream);
 }
 
 // PFMERGE dest src1..srcn (dest's own registers included)
@@ -845,7 +1198,7 @@ int rbx_hll_add_multi_dev(rbx_ctx *c, rbx_hll *const *hlls, uint32_t nseg, const
         hl[s] = hlls[s]->st.get();
         hl[s]->card |= 1ULL << 63;  // conservatively invalidate (the flags are device-side)
     }
-    return pfadd_run(c, hl, h_seg_offsets, keys_dev(d_elements), d_changed, st);
+    return pfadd_run(c, hl, h_seg_offsets, h_seg_offsets + 1, nullptr, keys_dev(d_elements), d_changed, st);
 }
 
 int rbx_hll_count_each_handles(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, uint64_t *out) {
@@ -856,7 +1209,7 @@ int rbx_hll_count_each_handles(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, uin
         if (hlls[i]) RBX_TRY(hll_bind(c, hlls[i], false, c->stream));
         hl[i] = hlls[i] ? hlls[i]->st.get() : nullptr;
     }
-    return pfcount_each(c, hl, out);
+    return pfcount_each(c, hl, out, c->stream);
 }
 
 int rbx_hll_pack_registers(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, void *d_buf, void *stream) {
@@ -865,6 +1218,28 @@ int rbx_hll_pack_registers(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, void *d
 
 int rbx_hll_unpack_max_registers(rbx_ctx *c, rbx_hll *const *hlls, uint32_t n, const void *d_buf, void *stream) {
     return hll_pack(c, hlls, n, (uint8_t *)d_buf, true, stream);
+}
+
+int rbx_hll_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key, const uint8_t *cmd_op,
+                   const uint64_t *cmd_elem, uint64_t n, const rbx_keys *elements, uint64_t *replies, uint8_t *status) {
+    RBX_TRY(hll_stream_check(c, names, nkeys, cmd_key, cmd_op, cmd_elem, n, elements));
+    if (n == 0) return RBX_OK;  // no command is sent
+    return hll_stream(c, names, nkeys, cmd_key, cmd_op, cmd_elem, n, elements, replies, status, false, c->stream);
+}
+
+int rbx_hll_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key, const uint8_t *cmd_op,
+                       const uint64_t *cmd_elem, uint64_t n, const rbx_keys *d_elements, uint64_t *replies,
+                       uint8_t *status, void *stream) {
+    RBX_TRY(hll_stream_check(c, names, nkeys, cmd_key, cmd_op, cmd_elem, n, d_elements));
+    if (n == 0) return RBX_OK;
+    return hll_stream(c, names, nkeys, cmd_key, cmd_op, cmd_elem, n, d_elements, replies, status, true,
+                      pick_stream(c, stream));
+}
+
+int rbx_bench_hllstream_last(uint32_t out[4]) {
+    if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (int i = 0; i < 4; ++i) out[i] = g_hllstream_last[i];
+    return RBX_OK;
 }
 
 // ---- RCCL -----------------------------------------------------------------------------------

@@ -29,24 +29,6 @@ __device__ __forceinline__ uint32_t bytemax4(uint32_t a, uint32_t b) {
 }
 
 template <int ELEN>
-__device__ __forceinline__ uint64_t elem_hash(const KeysDev &e, uint64_t i) {
-    if constexpr (ELEN > 0) {
-        return murmur_fixed<ELEN>(e.bytes + i * (uint64_t)ELEN);
-    } else {
-        uint64_t a, len;
-        if (e.offsets) {
-            a = e.offsets[i];
-            len = e.offsets[i + 1] - a;
-            a -= e.off_base;
-        } else {
-            a = i * e.stride;
-            len = e.stride;
-        }
-        return murmur_bytes(e.bytes + a, len);
-    }
-}
-
-template <int ELEN>
 __global__ __launch_bounds__(kPfaddThreads) void k_hll_pfadd(KeysDev elems, const HllSeg *__restrict__ tiles,
                                                              uint32_t *__restrict__ changed) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_regs[];  // 16384 u32
@@ -588,7 +570,7 @@ __device__ void replay_one(sp::Lds &L, const HllReplay &it, const KeysDev &elems
                 idx = (uint32_t)e;
                 cnt = it.regs[e];
             } else {
-                const uint64_t h = elem_hash<ELEN>(elems, e);
+                const uint64_t h = elem_hash<ELEN>(elems, it.list ? it.list_base + it.list[e] : e);
                 idx = (uint32_t)(h & (kHllRegs - 1));
                 cnt = hll_count_of(h);
             }

@@ -324,6 +324,9 @@ static const TuneRow kTuneRows[] = {
     {"fieldstream_path", RANGE(0, 3), false, FIELD(fieldstream_path)},
     {"fieldstream_serial_max", RANGE(0, kIntMax), false, FIELD(fieldstream_serial_max)},
     {"fieldstream_chunk", RANGE(1, 1 << 30), false, FIELD(fieldstream_chunk)},  // positions in a chunk are 32-bit
+    {"hllstream_path", RANGE(0, 2), false, FIELD(hllstream_path)},
+    {"hllstream_chunk", RANGE(1, 1 << 30), false, FIELD(hllstream_chunk)},  // positions in a chunk are 32-bit
+    {"hllstream_elems_per_round", RANGE(1, kIntMax), false, FIELD(hllstream_elems_per_round)},
 };
 #undef RANGE
 #undef ONE_OF

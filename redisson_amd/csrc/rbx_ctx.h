@@ -337,6 +337,16 @@ struct Staging {
     }
 };
 
+// The ordered PFADD / PFCOUNT stream (rbx_hll_stream): one call at a time holds these.
+struct HllStreamScratch {
+    DevBuf cmds;     // the call's element offsets (n + 1 u64), then its keys (n u32)
+    DevBuf changed;  // one word per command, then the promotion words read back after an add run
+    DevBuf sort;     // the grouped path's cells, positions and rocPRIM's temporary storage
+    DevBuf lists;    // the sparse keys' element lists of a chunk (HllReplay::list)
+    DevBuf ptrs;     // the sparse keys' state words of a run, for the promotion readback
+    CachedTable<rbx::HllKey> keys;  // the key table
+};
+
 // HLL register pool (chunks of kHllPerChunk x 16 KiB) and PFADD's uploaded tables.
 struct HllPool {
     struct Slot {
@@ -351,6 +361,7 @@ struct HllPool {
     CachedTable<rbx::HllSeg> tiles;      // k_hll_pfadd tile list (cached for single-round calls)
     CachedTable<rbx::HllReplay> replay;  // k_hll_sparse_replay items
     DevBuf pack;                         // contiguous registers for the RCCL merge
+    HllStreamScratch strm;
     void free_chunks() {
         for (auto *p : chunks) (void)hipFree(p);
         chunks.clear();

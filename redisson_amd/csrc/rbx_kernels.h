@@ -519,6 +519,25 @@ void launch_gather_probe(const uint32_t *tbl, uint64_t nwords, uint64_t nkeys, u
                          hipStream_t st);
 
 // ---- hll_kernels.hip
+// MurmurHash64A of element i (ELEN: the fixed 16-byte-aligned length of with_klen<true>, 0 = any)
+template <int ELEN>
+__device__ __forceinline__ uint64_t elem_hash(const KeysDev &e, uint64_t i) {
+    if constexpr (ELEN > 0) {
+        return murmur_fixed<ELEN>(e.bytes + i * (uint64_t)ELEN);
+    } else {
+        uint64_t a, len;
+        if (e.offsets) {
+            a = e.offsets[i];
+            len = e.offsets[i + 1] - a;
+            a -= e.off_base;
+        } else {
+            a = i * e.stride;
+            len = e.stride;
+        }
+        return murmur_bytes(e.bytes + a, len);
+    }
+}
+
 struct HllSeg {
     uint8_t *regs;      // 16384 u8 registers
     uint64_t begin;     // element range [begin, end)
@@ -546,6 +565,10 @@ struct HllReplay {
     const uint8_t *regs;  // merge mode (PFMERGE write-back): the max registers, ascending; else null
     uint64_t begin, end;  // PFADD mode: the command's elements, in order
     const uint8_t *final_regs;  // the registers after the update (PFADD: the key's, merged already)
+    // PFADD mode, second form (the HLL stream: one key's elements across many commands): non-null = the
+    // elements are list_base + list[begin .. end), in that order; null = the elements [begin, end) themselves
+    const uint32_t *list;
+    uint64_t list_base;
 };
 // one block per item; items whose HLL is already promoted return at once
 void launch_hll_sparse_replay(const KeysDev &elems, int elen_fast, const HllReplay *items, uint32_t n,
@@ -554,5 +577,32 @@ void launch_hll_sparse_replay(const KeysDev &elems, int elen_fast, const HllRepl
 void launch_hll_zero(uint8_t *const *d_regs, uint32_t *const *d_state, uint32_t n, hipStream_t st);
 // buf[i*16384..] = regs[i] (pack) or regs[i] = max(regs[i], buf[i*16384..]) (unpack_max)
 void launch_hll_pack(uint8_t *const *d_regs, uint32_t n, uint8_t *buf, bool unpack_max, hipStream_t st);
+
+// ---- hllstream_kernels.hip
+// The grouped add run of the ordered PFADD / PFCOUNT stream over many HLLs (rbx_hll_stream).
+// One HLL of the call as the kernels see it, one record per entry of `names`.
+struct alignas(16) HllKey {
+    uint8_t *regs;   // 16384 u8 registers (null: the key holds another type)
+    uint32_t flags;  // kHllKeyWrong | kHllKeyFailed
+    uint32_t canon;  // the first entry of `names` with this entry's bytes (its own index if none is earlier)
+};
+static_assert(sizeof(HllKey) == 16, "four to a line");
+constexpr uint32_t kHllKeyWrong = 1;   // the key holds another type
+constexpr uint32_t kHllKeyFailed = 2;  // its commands fail alone: their elements touch nothing
+constexpr int kHsRegShift = 6, kHsKeyShift = 20;  // cell = canon << 20 | register << 6 | count
+// One chunk of an add run: the commands [cmd0, cmd0 + ncmds) of the call, whose elements are the m <= 2^30
+// elements from elem0 on in the call's numbering (d_cmd_elem's) and from `first` on in `elems`.  d_cmd_elem
+// and d_cmd_key are the call's arrays (a PFCOUNT or an empty PFADD of the range owns no element); d_changed
+// has one word per command of the call and gets a 1 for each command that raises a register.  key_bits: the
+// significant bits of nkeys - 1; has_failed: some key of the table has kHllKeyFailed.  The scratch size comes
+// from hllstream_grouped_scratch_bytes with cell_bits = 14 + key_bits + has_failed.  Both return 0 or a
+// hipError_t.
+int hllstream_grouped_scratch_bytes(uint32_t m, int cell_bits, size_t *bytes);
+int launch_hllstream_grouped(const KeysDev &elems, int elen_fast, uint64_t first, uint64_t elem0, uint32_t m,
+                             const HllKey *d_tab, const uint64_t *d_cmd_elem, const uint32_t *d_cmd_key, uint64_t cmd0,
+                             uint32_t ncmds, uint32_t *d_changed, int key_bits, bool has_failed, void *d_scratch,
+                             size_t scratch_bytes, hipStream_t st);
+// d_out[i] = d_states[i][0], the sticky promotion word (HllReplay::state) of each sparse HLL of a run
+void launch_hllstream_promoted(uint32_t *const *d_states, uint32_t n, uint32_t *d_out, hipStream_t st);
 
 }  // namespace rbx

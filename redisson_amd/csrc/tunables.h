@@ -109,6 +109,22 @@ struct Tunables {
     // "fieldstream_chunk": commands per chunk of the grouped paths (24 bytes of sort scratch per command plus
     // rocPRIM's own; positions inside a chunk are 32-bit)
     std::atomic<uint64_t> fieldstream_chunk{1 << 25};
+
+    // ---- the ordered PFADD / PFCOUNT stream (api_hll.cpp) ----
+    // "hllstream_path": how an add run (the PFADDs of one phase) reaches the registers: 0 (default) = by rounds
+    // (pfadd_run: one k_hll_pfadd launch per maximal run of commands on distinct keys) when the run has few
+    // rounds for its elements, else grouped (one sort by (key, register) per chunk, hllstream_kernels.hip);
+    // 1 = always rounds, 2 = always grouped.  All exact.
+    std::atomic<int> hllstream_path{0};
+    // "hllstream_chunk": elements per chunk of the grouped path (36.125 bytes of sort scratch per element, what
+    // hllstream_grouped_scratch_bytes returns at 2^25: 24 of cells and positions, the rest rocPRIM's temporary
+    // storage; 2^25 elements are 1.129 GiB); a command with more elements than this runs by rounds, alone
+    std::atomic<uint64_t> hllstream_chunk{1 << 25};
+    // "hllstream_elems_per_round": the auto rule takes the grouped path iff the run's rounds R exceed
+    // max(1, elements / this): what one round costs, in elements of the grouped path.  Measured on 2^20
+    // one-element PFADDs over 4,096 keys (DESIGN 11.7 row d): 10.2 us per round by rounds against 8.97 ns per
+    // element grouped, call times with the host's share in both: 1137 elements per round.
+    std::atomic<uint64_t> hllstream_elems_per_round{1137};
 };
 
 extern Tunables g_tune;

@@ -23,8 +23,8 @@ import functools
 import numpy as np
 
 from . import _lib as L
-from .client import (GETBIT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued, bitset_field_stream_call,
-                     bitset_stream_call, run_queue)
+from .client import (GETBIT, PFADD, PFCOUNT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued,
+                     bitset_field_stream_call, bitset_stream_call, hll_stream_call, run_queue)
 from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
 
@@ -129,11 +129,26 @@ def _one_sub_command(key, subCommands):
     return key, _field_row(cmds[0], "WRAP"), lambda reply: [reply]
 
 
-def _pipelined(fn=None, *, bit=None, field=None):
+def _pf_add(key, *values):
+    """(key, (PFADD, elements), convert) of a pipelined pfAdd: the reply is the Long 1 / 0"""
+    return key, (PFADD, [bytes(v) for v in values]), int
+
+
+def _pf_count(*keys):
+    """(key, (PFCOUNT, []), None) of a pipelined single-key pfCount; None for any other (it runs singly, and
+    raises there what it has to raise)"""
+    if len(keys) != 1 or keys[0] is None:
+        return None
+    return keys[0], (PFCOUNT, []), None
+
+
+def _pipelined(fn=None, *, bit=None, field=None, hll=None):
     """A command method of RedissonConnection: while a pipeline is open it queues itself and returns None
     (the result comes back from closePipeline); bit = (key, op, index) of a GETBIT / SETBIT, which travels with
     its neighbours in one rbx_bitset_stream call; field = (key, row, convert) of a BITFIELD with one sub-command
-    (or None for any other), which travels with its bit and field neighbours in one rbx_bitset_field_stream call."""
+    (or None for any other), which travels with its bit and field neighbours in one rbx_bitset_field_stream call;
+    hll = (key, (op, elements), convert) of a PFADD / single-key PFCOUNT (or None for any other), which travels
+    with its HLL neighbours in one rbx_hll_stream call."""
 
     def wrap(f):
         @functools.wraps(f)
@@ -145,6 +160,17 @@ def _pipelined(fn=None, *, bit=None, field=None):
                 self._pipeline.append(_Queued(_key(key), op, _bit_index(index)))
                 return None
             single = lambda: f(self, *args, **kwargs)  # noqa: E731
+            if hll is not None:
+                try:
+                    row = hll(*args, **kwargs)
+                except (IllegalArgumentException, TypeError):
+                    row = None  # the single call raises it at its position
+                if row is not None and row[0] is not None:
+                    key, cmd, convert = row
+                    self._pipeline.append(_Queued(_key(key), fn=single, hll=cmd, convert=convert))
+                else:
+                    self._pipeline.append(_Queued(fn=single))
+                return None
             try:
                 row = field(*args, **kwargs) if field is not None else None
             except IllegalArgumentException:
@@ -177,13 +203,15 @@ class RedissonConnection:
     def closePipeline(self) -> list:
         """:146-163 -- runs the queued commands in order and returns their results; [] outside a pipeline.
         Consecutive getBit / setBit commands, over any keys, are one rbx_bitset_stream call; with a bitField of
-        exactly one sub-command among them they are one rbx_bitset_field_stream call.  Every command runs; then
-        the first failure is raised."""
+        exactly one sub-command among them they are one rbx_bitset_field_stream call.  Consecutive pfAdd and
+        single-key pfCount commands, over any keys, are one rbx_hll_stream call (a multi-key pfCount and pfMerge
+        run singly).  Every command runs; then the first failure is raised."""
         if self._pipeline is None:
             return []
         queue, self._pipeline = self._pipeline, None
         results, error = run_queue(queue, lambda *a: bitset_stream_call(self._client, *a),
-                                   lambda *a: bitset_field_stream_call(self._client, *a))
+                                   lambda *a: bitset_field_stream_call(self._client, *a),
+                                   lambda *a: hll_stream_call(self._client, *a))
         if error is not None:
             raise error
         return results
@@ -192,7 +220,7 @@ class RedissonConnection:
     open_pipeline = openPipeline
     close_pipeline = closePipeline
 
-    @_pipelined
+    @_pipelined(hll=_pf_add)
     def pfAdd(self, key: bytes, *values: bytes) -> int:
         """PFADD key v1..vn -> 1 if the HLL was created or a register changed, else 0."""
         a = Arena([bytes(v) for v in values])
@@ -203,7 +231,7 @@ class RedissonConnection:
                                            ch.ctypes.data_as(L.u8p)))
         return int(ch[0])
 
-    @_pipelined
+    @_pipelined(hll=_pf_count)
     def pfCount(self, *keys: bytes) -> int:
         """PFCOUNT k1..kn (union when n > 1)."""
         if not keys:
