@@ -856,25 +856,35 @@ HLL_FAILED = 0xFF  # status of an HLL-stream command that failed alone
 _HLL_WRONGTYPE_MSG = "WRONGTYPE Key is not a valid HyperLogLog string value."
 
 
+class _HllStreamArrays:
+    """the command arrays of one rbx_hll_stream[_dev] call, checked, and the arrays it answers into"""
+
+    def __init__(self, names, cmd_key, cmd_op, seg):
+        self.key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+        self.op = np.ascontiguousarray(cmd_op, dtype=np.uint8).reshape(-1)
+        self.offs = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1)
+        self.n = n = self.key.size
+        if self.op.size != n or self.offs.size != n + 1:
+            raise IllegalArgumentException("cmd_key and cmd_op have one entry per command, seg one more")
+        self.names_arr, self._keep = L.names_array(names)
+        self.out = np.zeros(max(n, 1), np.uint64)
+        self.status = np.zeros(max(n, 1), np.uint8)
+        self.commands = (self.names_arr, len(names), self.key.ctypes.data_as(L.u32p), self.op.ctypes.data_as(L.u8p),
+                         self.offs.ctypes.data_as(L.u64p), n)
+        self.answers = (self.out.ctypes.data_as(L.u64p), self.status.ctypes.data_as(L.u8p))
+
+    def result(self, rc):
+        return rc, (L.last_error() if rc != L.RBX_OK else ""), self.out[: self.n], self.status[: self.n]
+
+
 def hll_stream_call(client: RedissonClient, names, cmd_key, cmd_op, seg, arena):
     """rbx_hll_stream over host arrays without raising: (rc, message, replies, status).  names: str or bytes keys;
     command i is cmd_op[i] (PFADD / PFCOUNT) on names[cmd_key[i]] with the elements [seg[i], seg[i + 1]) of
     `arena` (an Arena, or a list of bytes).  replies: uint64 (1 / 0 for a PFADD, the cardinality for a PFCOUNT);
     status: uint8 with 0 = the command ran, 0xFF = it failed alone."""
-    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
-    op = np.ascontiguousarray(cmd_op, dtype=np.uint8).reshape(-1)
-    offs = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1)
-    n = key.size
-    if op.size != n or offs.size != n + 1:
-        raise IllegalArgumentException("cmd_key and cmd_op have one entry per command, seg one more")
+    s = _HllStreamArrays(names, cmd_key, cmd_op, seg)
     a = arena if isinstance(arena, (Arena, _OneKey)) else Arena([bytes(e) for e in arena])
-    names_arr, _keep = L.names_array(names)
-    out = np.zeros(max(n, 1), np.uint64)
-    status = np.zeros(max(n, 1), np.uint8)
-    rc = L.lib().rbx_hll_stream(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p), op.ctypes.data_as(L.u8p),
-                                offs.ctypes.data_as(L.u64p), n, a.ptr(), out.ctypes.data_as(L.u64p),
-                                status.ctypes.data_as(L.u8p))
-    return rc, (L.last_error() if rc != L.RBX_OK else ""), out[:n], status[:n]
+    return s.result(L.lib().rbx_hll_stream(client.ctx, *s.commands, a.ptr(), *s.answers))
 
 
 _engine_hll_stream_call = hll_stream_call  # (RBatch.__init__ has a parameter of that name)
@@ -893,19 +903,8 @@ def hll_stream_dev_call(client: RedissonClient, names, cmd_key, cmd_op, seg, d_e
                         stream: int | None = None):
     """rbx_hll_stream_dev without raising: (rc, message, replies, status) over device-resident elements
     (device_keys); the command arrays stay host arrays."""
-    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
-    op = np.ascontiguousarray(cmd_op, dtype=np.uint8).reshape(-1)
-    offs = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1)
-    n = key.size
-    if op.size != n or offs.size != n + 1:
-        raise IllegalArgumentException("cmd_key and cmd_op have one entry per command, seg one more")
-    names_arr, _keep = L.names_array(names)
-    out = np.zeros(max(n, 1), np.uint64)
-    status = np.zeros(max(n, 1), np.uint8)
-    rc = L.lib().rbx_hll_stream_dev(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p),
-                                    op.ctypes.data_as(L.u8p), offs.ctypes.data_as(L.u64p), n, C.byref(d_elements),
-                                    out.ctypes.data_as(L.u64p), status.ctypes.data_as(L.u8p), stream)
-    return rc, (L.last_error() if rc != L.RBX_OK else ""), out[:n], status[:n]
+    s = _HllStreamArrays(names, cmd_key, cmd_op, seg)
+    return s.result(L.lib().rbx_hll_stream_dev(client.ctx, *s.commands, C.byref(d_elements), *s.answers, stream))
 
 
 def hll_stream_dev(client: RedissonClient, names, cmd_key, cmd_op, seg, d_elements: L.RbxKeys,
@@ -987,12 +986,15 @@ def _field_error(q: _Queued) -> RedissonAmdError:
     return RedisException("WRONGTYPE Operation against a key holding the wrong kind of value")
 
 
-def _run_fields(run, field_stream_call):
-    """one field stream call for a run of bit and field commands; sets every future, returns the first error"""
+def _run_stream(run, call, accepted_rcs, settle):
+    """One stream call for a run of coalesced commands: call(run, names, cmd_key) -> (rc, message, replies, status)
+    over the run's distinct names and each command's place among them.  An rc outside accepted_rcs refuses the run as a
+    whole, and every future gets that error; otherwise settle(command, reply, status) sets each command's future.
+    Returns the first error."""
     ids: dict = {}
     keys = [ids.setdefault(c.name, len(ids)) for c in run]
-    rc, msg, replies, status = field_stream_call(list(ids), keys, [c.as_field() for c in run])
-    if rc not in (L.RBX_OK, L.RBX_E_REDIS, L.RBX_E_WRONGTYPE):  # the run as a whole was refused
+    rc, msg, replies, status = call(run, list(ids), keys)
+    if rc not in accepted_rcs:
         try:
             raise_for(rc, msg)
         except RedissonAmdError as e:
@@ -1001,42 +1003,36 @@ def _run_fields(run, field_stream_call):
             return e
     first_error = None
     for c, r, s in zip(run, replies, status):
-        if int(s) == FIELD_FAILED:
-            c.future._set(error=_bit_error(c) if c.field is None else _field_error(c))
-        elif c.field is None:
-            c.future._set(bool(r))
-        else:
-            value = None if int(s) == 1 else int(r)  # nil
-            c.future._set(c.convert(value) if c.convert else value)
+        settle(c, r, s)
         first_error = first_error or c.future._error
     return first_error
 
 
-def _run_hll(run, hll_stream_call):
-    """one HLL stream call for a run of PFADD / PFCOUNT commands; sets every future, returns the first error"""
-    ids: dict = {}
-    keys = [ids.setdefault(c.name, len(ids)) for c in run]
-    seg, elements = [0], []
-    for c in run:
-        elements.extend(c.hll[1])
-        seg.append(len(elements))
-    rc, msg, replies, status = hll_stream_call(list(ids), keys, [c.hll[0] for c in run], seg, elements)
-    if rc not in (L.RBX_OK, L.RBX_E_WRONGTYPE):  # the run as a whole was refused
-        try:
-            raise_for(rc, msg)
-        except RedissonAmdError as e:
-            for c in run:
-                c.future._set(error=e)
-            return e
-    first_error = None
-    for c, r, s in zip(run, replies, status):
-        if int(s) == HLL_FAILED:
-            c.future._set(error=RedisException(_HLL_WRONGTYPE_MSG))
-        else:
-            value = bool(r) if c.hll[0] == PFADD else int(r)
-            c.future._set(c.convert(value) if c.convert else value)
-        first_error = first_error or c.future._error
-    return first_error
+def _settle_bit(c: _Queued, reply, _status) -> None:
+    """a bit command of a bit run: the reply is its own status"""
+    if int(reply) == _FAILED_REPLY:
+        c.future._set(error=_bit_error(c))
+    else:
+        c.future._set(bool(reply))
+
+
+def _settle_field(c: _Queued, reply, status) -> None:
+    """a bit or field command of a field run"""
+    if int(status) == FIELD_FAILED:
+        c.future._set(error=_bit_error(c) if c.field is None else _field_error(c))
+    elif c.field is None:
+        c.future._set(bool(reply))
+    else:
+        value = None if int(status) == 1 else int(reply)  # nil
+        c.future._set(c.convert(value) if c.convert else value)
+
+
+def _settle_hll(c: _Queued, reply, status) -> None:
+    if int(status) == HLL_FAILED:
+        c.future._set(error=RedisException(_HLL_WRONGTYPE_MSG))
+    else:
+        value = bool(reply) if c.hll[0] == PFADD else int(reply)
+        c.future._set(c.convert(value) if c.convert else value)
 
 
 def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None):
@@ -1054,52 +1050,49 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None):
     def joins_hll(q):
         return q.hll is not None and hll_stream_call is not None
 
+    def run_from(i, belongs):
+        """the maximal run of commands from queue[i] on that belong together"""
+        j = i
+        while j < len(queue) and belongs(queue[j]):
+            j += 1
+        return queue[i:j]
+
+    def hll_call(run, names, keys):
+        seg, elements = [0], []
+        for c in run:
+            elements.extend(c.hll[1])
+            seg.append(len(elements))
+        return hll_stream_call(names, keys, [c.hll[0] for c in run], seg, elements)
+
+    def field_call(run, names, keys):
+        return field_stream_call(names, keys, [c.as_field() for c in run])
+
+    def bit_call(run, names, keys):
+        rc, msg, replies = stream_call(names, keys, [c.op for c in run], [c.index for c in run])
+        return rc, msg, replies, replies
+
+    alone = (L.RBX_OK, L.RBX_E_REDIS, L.RBX_E_WRONGTYPE)  # what a run returns whose commands ran or failed alone
     first_error = None
     i = 0
-    while i < len(queue):
-        q = queue[i]
-        if joins_hll(q):
-            j = i
-            while j < len(queue) and joins_hll(queue[j]):
-                j += 1
-            error = _run_hll(queue[i:j], hll_stream_call)  # (runs whether or not an earlier command failed)
-            first_error = first_error or error
-            i = j
-            continue
-        if not joins(q):
-            try:
-                q.future._set(q.fn())
-            except RedissonAmdError as e:
-                q.future._set(error=e)
-                first_error = first_error or e
-            i += 1
-            continue
-        j = i
-        while j < len(queue) and joins(queue[j]):
-            j += 1
-        run = queue[i:j]
-        if any(c.field is not None for c in run):
-            first_error = first_error or _run_fields(run, field_stream_call)
-            i = j
-            continue
-        ids: dict = {}
-        keys = [ids.setdefault(c.name, len(ids)) for c in run]
-        rc, msg, replies = stream_call(list(ids), keys, [c.op for c in run], [c.index for c in run])
-        whole = None  # the run as a whole was refused
-        if rc not in (L.RBX_OK, L.RBX_E_REDIS, L.RBX_E_WRONGTYPE):
-            try:
-                raise_for(rc, msg)
-            except RedissonAmdError as e:
-                whole = e
-        for c, r in zip(run, replies if whole is None else [0] * len(run)):
-            if whole is not None:
-                c.future._set(error=whole)
-            elif int(r) == _FAILED_REPLY:
-                c.future._set(error=_bit_error(c))
+    while i < len(queue):  # (every run executes, whether or not an earlier command failed)
+        if joins_hll(queue[i]):
+            run = run_from(i, joins_hll)
+            error = _run_stream(run, hll_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_hll)
+        elif joins(queue[i]):
+            run = run_from(i, joins)
+            if any(c.field is not None for c in run):
+                error = _run_stream(run, field_call, alone, _settle_field)
             else:
-                c.future._set(bool(r))
-            first_error = first_error or c.future._error
-        i = j
+                error = _run_stream(run, bit_call, alone, _settle_bit)
+        else:
+            run = queue[i:i + 1]
+            try:
+                run[0].future._set(run[0].fn())
+            except RedissonAmdError as e:
+                run[0].future._set(error=e)
+            error = run[0].future._error
+        first_error = first_error or error
+        i += len(run)
     return [None if c.future._error is not None else c.future._value for c in queue], first_error
 
 

@@ -13,8 +13,6 @@ namespace rbx {
 
 static constexpr uint64_t kMaxBitOffset = kEngineMaxSize;  // offsets end at 2^32 - 1
 
-static bool bad_name(const rbx_name &n) { return !n.bytes && n.len; }
-
 // the bitmap under `name`; null for a missing key (the empty string)
 static int bitset_find(rbx_ctx *c, const std::string &name, std::shared_ptr<Bitmap> *out) {
     out->reset();
@@ -187,19 +185,14 @@ static int fields_run(rbx_ctx *c, const std::string &name, int op, int is_signed
     } else {
         // consecutive chunks of at most 2^30 elements, in order (positions are 32-bit inside a chunk)
         const uint64_t kChunk = 1ULL << 30;
-        int slot_bits = 1;
-        while (slot_bits < 32 && ((mx / (uint64_t)size) >> slot_bits) != 0) ++slot_bits;
-        size_t scratch = 0;
-        int e = fields_grouped_scratch_bytes((uint32_t)std::min(n, kChunk), slot_bits, &scratch);
-        if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
-        RBX_TRY(c->dev->bits.fld_sort.reserve(scratch));
+        const int slot_bits = std::min(32, std::max(1, significant_bits(mx / (uint64_t)size)));
+        DevBuf &sort = c->dev->bits.fld_sort;
+        RBX_TRY(cell_sort_reserve<uint32_t>(sort, (uint32_t)std::min(n, kChunk), 0, slot_bits));
         for (uint64_t i0 = 0; i0 < n; i0 += kChunk) {
             const uint32_t m = (uint32_t)std::min(kChunk, n - i0);
-            e = launch_fields_grouped(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, mode, d_offs + i0,
-                                      d_values + i0, m, d_replies ? d_replies + i0 : nullptr,
-                                      d_nil ? d_nil + i0 : nullptr, need, slot_bits, c->dev->bits.fld_sort.p,
-                                      c->dev->bits.fld_sort.cap, st);
-            if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+            RBX_TRY(sort_failed(launch_fields_grouped(bm->d_words, bm->d_len, bm->cap_bytes, op, is_signed, size, mode,
+                                                      d_offs + i0, d_values + i0, m, d_replies ? d_replies + i0 : nullptr,
+                                                      d_nil ? d_nil + i0 : nullptr, need, slot_bits, sort.p, sort.cap, st)));
         }
     }
     HIP_TRY(hipGetLastError());
@@ -453,14 +446,7 @@ static int range_of(const uint8_t *bytes, uint64_t len, int missing, bool pos, i
 }
 
 // ---- the ordered GETBIT / SETBIT stream over many keys (RBatch.getBitSet, M/RedissonBatch.java:182-184) ----
-static int significant_bits(uint64_t v) {
-    int b = 0;
-    while (b < 64 && (v >> b)) ++b;  // (a shift by 64 is undefined: a value with bit 63 set ends at b = 64)
-    return b;
-}
-
-// The keys of one stream call.  Equal names are one key, known by its first entry (its canonical id); a key
-// of another type fails its commands.
+// The keys of one bit-stream call (stream_names_resolve has the rules)
 struct StreamKeys {
     uint32_t nkeys = 0;
     std::vector<std::string> nm;
@@ -472,18 +458,8 @@ struct StreamKeys {
 // resolves the names once (lookup only) and uploads canonical ids | wrong-type flags to bst_keys
 static int stream_keys_resolve(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, hipStream_t st, StreamKeys *sk) {
     sk->nkeys = nkeys;
-    sk->nm.resize(nkeys);
     sk->kinfo.assign((size_t)nkeys * 5, 0);
-    uint32_t *canon = sk->canon();
-    uint8_t *wrong = sk->wrong();
-    std::unordered_map<std::string, uint32_t> first;
-    first.reserve(nkeys);
-    for (uint32_t i = 0; i < nkeys; ++i) {
-        sk->nm[i] = name_of(names[i]);
-        canon[i] = first.emplace(sk->nm[i], i).first->second;
-        const Entry *e = canon[i] == i ? c->ks.find(sk->nm[i]) : nullptr;
-        wrong[i] = canon[i] == i ? (uint8_t)(e && e->type != KType::Bitmap) : wrong[canon[i]];
-    }
+    stream_names_resolve(c, names, nkeys, KType::Bitmap, &sk->nm, sk->canon(), sk->wrong(), [](uint32_t, const Entry &) {});
     DevBuf &d = c->dev->bits.bst_keys;
     RBX_TRY(d.reserve(sk->kinfo.size()));
     HIP_TRY(hipMemcpyAsync(d.p, sk->kinfo.data(), sk->kinfo.size(), hipMemcpyHostToDevice, st));
@@ -521,39 +497,56 @@ static int stream_keys_table(rbx_ctx *c, StreamKeys &sk, const unsigned long lon
     return *d_tab ? RBX_OK : c->dev->bits.bst_table.err;
 }
 
-static int stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const void *key, const void *op,
-                             const void *index, uint64_t n) {
-    if (!c || (nkeys && !names) || (n && (!key || !op || !index))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
-    for (uint32_t i = 0; i < nkeys; ++i)
-        if (bad_name(names[i])) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
+// what both bit streams check before anything runs; arrays: every per-command array is there
+static int stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, uint64_t n, bool arrays) {
+    if (n && !arrays) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(stream_names_check(c, names, nkeys));
     // a cell is (key id, index) in 64 bits, one of them the failed commands'
     if (nkeys > (1u << 31)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes at most 2^31 keys");
     return RBX_OK;
 }
 
+// The summary pass of both bit streams, before anything is written: the names resolved once (lookup only), the
+// `words` summary words set (the first `ones` of them, the "first position" minima, to ~0; the others and the
+// nkeys per-key maxima behind them to 0), the stream's summary kernel through launch(d_canon, d_wrong, d_sum,
+// d_keymax), and the one wait for what the batch needs.  *sum = the summary words | the per-key maxima; they
+// stay in bst_sum for launch_bitstream_lengths.
+template <class Launch>
+static int stream_summary(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, size_t words, size_t ones, hipStream_t st,
+                          Launch launch, StreamKeys *sk, std::vector<unsigned long long> *sum) {
+    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys");
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(stream_keys_resolve(c, names, nkeys, st, sk));
+    const size_t sum_bytes = (words + (size_t)nkeys) * 8;
+    RBX_TRY(b.bst_sum.reserve(sum_bytes));
+    auto *d_sum = b.bst_sum.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(d_sum, 0xFF, ones * 8, st));
+    HIP_TRY(hipMemsetAsync(d_sum + ones, 0, sum_bytes - ones * 8, st));
+    launch(b.bst_keys.as<uint32_t>(), b.bst_keys.as<uint8_t>() + (size_t)nkeys * 4, d_sum, d_sum + words);
+    HIP_TRY(hipGetLastError());
+    sum->resize(words + (size_t)nkeys);
+    HIP_TRY(hipMemcpyAsync(sum->data(), d_sum, sum_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the one wait
+    return RBX_OK;
+}
+
 // A batch of n > 0 commands over device arrays inside the caller's scope on `st`; d_replies nullable.
 // *failed = RBX_OK, or the code of the first command in array order that failed alone (the caller
-// reports it once the replies are where they belong).  Three steps: the summary pass (names resolved
-// once, lookup only; one wait for what the batch needs), the host's decisions (create or grow every
-// written key, build the key table, pick the path), the execution kernels and the lengths.
+// reports it once the replies are where they belong).  Three steps: the summary pass, the host's decisions
+// (create or grow every written key, build the key table, pick the path), the execution kernels and the lengths.
 static int stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_key, const uint8_t *d_op,
                       const uint64_t *d_idx, uint64_t n, uint8_t *d_replies, hipStream_t st, int *failed) {
     *failed = RBX_OK;
-    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys");
     BitsetScratch &b = c->dev->bits;
     StreamKeys sk;
-    RBX_TRY(stream_keys_resolve(c, names, nkeys, st, &sk));
-    const size_t sum_bytes = (kBsSummaryWords + (size_t)nkeys) * 8;
-    RBX_TRY(b.bst_sum.reserve(sum_bytes));
-    auto *d_sum = b.bst_sum.as<unsigned long long>(), *d_keymax = d_sum + kBsSummaryWords;
-    HIP_TRY(hipMemsetAsync(d_sum, 0xFF, 16, st));
-    HIP_TRY(hipMemsetAsync(d_sum + 2, 0, sum_bytes - 16, st));
-    launch_bitstream_summary(d_key, d_op, d_idx, n, nkeys, b.bst_keys.as<uint32_t>(),
-                             b.bst_keys.as<uint8_t>() + (size_t)nkeys * 4, d_sum, d_keymax, st);
-    HIP_TRY(hipGetLastError());
-    std::vector<unsigned long long> sum(kBsSummaryWords + (size_t)nkeys);
-    HIP_TRY(hipMemcpyAsync(sum.data(), d_sum, sum_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));  // the one wait
+    std::vector<unsigned long long> sum;
+    RBX_TRY(stream_summary(c, names, nkeys, kBsSummaryWords, kBsFlags, st,
+                           [&](const uint32_t *d_canon, const uint8_t *d_wrong, unsigned long long *d_sum,
+                               unsigned long long *d_keymax) {
+                               launch_bitstream_summary(d_key, d_op, d_idx, n, nkeys, d_canon, d_wrong, d_sum, d_keymax, st);
+                           },
+                           &sk, &sum));
+    const unsigned long long *d_keymax = b.bst_sum.as<unsigned long long>() + kBsSummaryWords;
     const uint64_t first_oob = sum[kBsFirstOob], first_wrong = sum[kBsFirstWrong];
     const uint32_t flags = (uint32_t)sum[kBsFlags];
     if (flags & kBsIllegal) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys, or its op not 0, 1 or 2");
@@ -578,16 +571,13 @@ static int stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const u
         const uint64_t chunk = g_tune.bitstream_chunk;
         const int index_bits = std::max(1, significant_bits(sum[kBsMaxIndex]));
         const int key_bits = significant_bits((uint64_t)nkeys - 1);
-        size_t scratch = 0;
-        int e = bitstream_grouped_scratch_bytes((uint32_t)std::min(n, chunk), index_bits + key_bits + (has_failed ? 1 : 0),
-                                                &scratch);
-        if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
-        RBX_TRY(b.bst_sort.reserve(scratch));
+        RBX_TRY(cell_sort_reserve<unsigned long long>(b.bst_sort, (uint32_t)std::min(n, chunk), 0,
+                                                      index_bits + key_bits + (has_failed ? 1 : 0)));
         for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
             const uint32_t m = (uint32_t)std::min(chunk, n - i0);
-            e = launch_bitstream_grouped(d_tab, d_key + i0, d_op + i0, d_idx + i0, m, d_replies ? d_replies + i0 : nullptr,
-                                         index_bits, key_bits, has_failed, b.bst_sort.p, b.bst_sort.cap, st);
-            if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+            RBX_TRY(sort_failed(launch_bitstream_grouped(d_tab, d_key + i0, d_op + i0, d_idx + i0, m,
+                                                         d_replies ? d_replies + i0 : nullptr, index_bits, key_bits,
+                                                         has_failed, b.bst_sort.p, b.bst_sort.cap, st)));
         }
     }
     if (writes) launch_bitstream_lengths(d_tab, d_keymax, nkeys, st);
@@ -605,38 +595,24 @@ static int stream_failed(int code) {
 enum { kFsPathNone = 0, kFsPathSerial = 1, kFsPathWords = 2, kFsPathKeys = 3, kFsPathGather = 4, kFsPathAtomic = 5 };
 static std::atomic<int> g_fieldstream_last_path{kFsPathNone};  // rbx_bench_fieldstream_last_path shows it
 
-static int field_stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const void *key,
-                                   const void *cmds, uint64_t n) {
-    if (!c || (nkeys && !names) || (n && (!key || !cmds))) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
-    for (uint32_t i = 0; i < nkeys; ++i)
-        if (bad_name(names[i])) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
-    if (nkeys > (1u << 31)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes at most 2^31 keys");
-    return RBX_OK;
-}
-
 // A batch of n > 0 commands over device arrays inside the caller's scope on `st`; d_replies and d_status
 // nullable.  *failed = 0, or the failure kind (kFs*) of the first command in array order that failed alone.
-// stream_run's steps: the summary pass (names resolved once; one wait), the host's decisions (the caller's
-// errors, every written key created or grown, the key table, the path), one execution path, the lengths.
+// stream_run's steps: the summary pass, the host's decisions (the caller's errors, every written key created
+// or grown, the key table, the path), one execution path, the lengths.
 static int field_stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_key,
                             const rbx_field_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
                             hipStream_t st, int *failed) {
     *failed = 0;
-    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "a command's key is not below nkeys");
     BitsetScratch &b = c->dev->bits;
     StreamKeys sk;
-    RBX_TRY(stream_keys_resolve(c, names, nkeys, st, &sk));
-    const size_t sum_bytes = (kFsSummaryWords + (size_t)nkeys) * 8;
-    RBX_TRY(b.bst_sum.reserve(sum_bytes));
-    auto *d_sum = b.bst_sum.as<unsigned long long>(), *d_keymax = d_sum + kFsSummaryWords;
-    HIP_TRY(hipMemsetAsync(d_sum, 0xFF, kFsFlags * 8, st));
-    HIP_TRY(hipMemsetAsync(d_sum + kFsFlags, 0, sum_bytes - kFsFlags * 8, st));
-    launch_fieldstream_summary(d_key, d_cmds, n, nkeys, b.bst_keys.as<uint32_t>(),
-                               b.bst_keys.as<uint8_t>() + (size_t)nkeys * 4, d_sum, d_keymax, st);
-    HIP_TRY(hipGetLastError());
-    std::vector<unsigned long long> sum(kFsSummaryWords + (size_t)nkeys);
-    HIP_TRY(hipMemcpyAsync(sum.data(), d_sum, sum_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));  // the one wait
+    std::vector<unsigned long long> sum;
+    RBX_TRY(stream_summary(c, names, nkeys, kFsSummaryWords, kFsFlags, st,
+                           [&](const uint32_t *d_canon, const uint8_t *d_wrong, unsigned long long *d_sum,
+                               unsigned long long *d_keymax) {
+                               launch_fieldstream_summary(d_key, d_cmds, n, nkeys, d_canon, d_wrong, d_sum, d_keymax, st);
+                           },
+                           &sk, &sum));
+    const unsigned long long *d_keymax = b.bst_sum.as<unsigned long long>() + kFsSummaryWords;
     const uint32_t flags = (uint32_t)sum[kFsFlags];
     if (flags & kFsIllegal)
         return fail(RBX_E_ILLEGAL_ARGUMENT,
@@ -679,17 +655,14 @@ static int field_stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, c
         const uint64_t chunk = g_tune.fieldstream_chunk;
         const int word_bits = path == kFsPathWords ? std::max(1, significant_bits(sum[kFsMaxWord])) : 0;
         const int key_bits = std::max(1, significant_bits((uint64_t)nkeys - 1));
-        size_t scratch = 0;
-        int e = fieldstream_grouped_scratch_bytes((uint32_t)std::min(n, chunk), word_bits + key_bits + (has_failed ? 1 : 0),
-                                                  &scratch);
-        if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
-        RBX_TRY(b.bst_sort.reserve(scratch));
+        RBX_TRY(cell_sort_reserve<unsigned long long>(b.bst_sort, (uint32_t)std::min(n, chunk), 0,
+                                                      word_bits + key_bits + (has_failed ? 1 : 0)));
         for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
             const uint32_t m = (uint32_t)std::min(chunk, n - i0);
-            e = launch_fieldstream_grouped(d_tab, d_key + i0, d_cmds + i0, m, d_replies ? d_replies + i0 : nullptr,
-                                           d_status ? d_status + i0 : nullptr, word_bits, key_bits, has_failed,
-                                           b.bst_sort.p, b.bst_sort.cap, st);
-            if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+            RBX_TRY(sort_failed(launch_fieldstream_grouped(d_tab, d_key + i0, d_cmds + i0, m,
+                                                           d_replies ? d_replies + i0 : nullptr,
+                                                           d_status ? d_status + i0 : nullptr, word_bits, key_bits,
+                                                           has_failed, b.bst_sort.p, b.bst_sort.cap, st)));
         }
     }
     if (writes) launch_bitstream_lengths(d_tab, d_keymax, nkeys, st);
@@ -800,7 +773,7 @@ int rbx_bitset_get_indexes_dev(rbx_ctx *c, rbx_name name, const uint64_t *d_inde
 int rbx_bitset_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
                           const uint8_t *d_cmd_op, const uint64_t *d_cmd_index, uint64_t n, uint8_t *d_replies,
                           void *stream) {
-    RBX_TRY(stream_args_check(c, names, nkeys, d_cmd_key, d_cmd_op, d_cmd_index, n));
+    RBX_TRY(stream_args_check(c, names, nkeys, n, d_cmd_key && d_cmd_op && d_cmd_index));
     if (n == 0) return RBX_OK;  // no command is sent
     hipStream_t st = pick_stream(c, stream);
     RBX_ENTER(c, st);
@@ -811,7 +784,7 @@ int rbx_bitset_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, con
 
 int rbx_bitset_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key, const uint8_t *cmd_op,
                       const uint64_t *cmd_index, uint64_t n, uint8_t *replies) {
-    RBX_TRY(stream_args_check(c, names, nkeys, cmd_key, cmd_op, cmd_index, n));
+    RBX_TRY(stream_args_check(c, names, nkeys, n, cmd_key && cmd_op && cmd_index));
     if (n == 0) return RBX_OK;
     hipStream_t st = c->stream;
     RBX_ENTER(c, st);
@@ -834,7 +807,7 @@ int rbx_bitset_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const u
 int rbx_bitset_field_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
                                 const rbx_field_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
                                 void *stream) {
-    RBX_TRY(field_stream_args_check(c, names, nkeys, d_cmd_key, d_cmds, n));
+    RBX_TRY(stream_args_check(c, names, nkeys, n, d_cmd_key && d_cmds));
     if (n == 0) return RBX_OK;  // no command is sent
     hipStream_t st = pick_stream(c, stream);
     RBX_ENTER(c, st);
@@ -845,7 +818,7 @@ int rbx_bitset_field_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkey
 
 int rbx_bitset_field_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
                             const rbx_field_cmd *cmds, uint64_t n, int64_t *replies, uint8_t *status) {
-    RBX_TRY(field_stream_args_check(c, names, nkeys, cmd_key, cmds, n));
+    RBX_TRY(stream_args_check(c, names, nkeys, n, cmd_key && cmds));
     if (n == 0) return RBX_OK;
     hipStream_t st = c->stream;
     RBX_ENTER(c, st);

@@ -412,14 +412,7 @@ static int hll_count_each(rbx_ctx *c, const std::vector<std::string> &names, uin
 static std::atomic<uint32_t> g_hllstream_last[4];  // rbx_bench_hllstream_last shows them
 enum { kHsPhases = 0, kHsRoundsRuns = 1, kHsGroupedRuns = 2, kHsChunks = 3 };
 
-static int significant_bits32(uint32_t v) {
-    int b = 0;
-    while (b < 32 && (v >> b)) ++b;
-    return b;
-}
-
-// The keys of one stream call.  Equal names are one key, known by its first entry (its canonical id); a key
-// of another type fails its commands.
+// The keys of one stream call (stream_names_resolve has the rules)
 struct HsKeys {
     std::vector<uint32_t> canon;
     std::vector<uint8_t> wrong;                  // per entry of names
@@ -431,10 +424,8 @@ struct HsKeys {
 
 static int hll_stream_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
                             const uint8_t *cmd_op, const uint64_t *cmd_elem, uint64_t n, const rbx_keys *elements) {
-    if (!c || (nkeys && !names) || (n && (!cmd_key || !cmd_op || !cmd_elem || !elements)))
-        return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
-    for (uint32_t i = 0; i < nkeys; ++i)
-        if (!names[i].bytes && names[i].len) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
+    if (n && (!cmd_key || !cmd_op || !cmd_elem || !elements)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(stream_names_check(c, names, nkeys));
     if (n == 0) return RBX_OK;
     RBX_TRY(validate_keys(elements));
     if (n >= (1ULL << 32)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes fewer than 2^32 commands");
@@ -500,13 +491,10 @@ static int hs_grouped_chunk(HsCall &h, uint64_t a, uint64_t b, int key_bits) {
     const uint64_t e0 = h.cmd_elem[a], first = e0 - h.elem_base;
     const uint32_t m = (uint32_t)(h.cmd_elem[b] - e0);
     const int fl = fast_len_hll(h.dk);
-    size_t scratch = 0;
-    int e = hllstream_grouped_scratch_bytes(m, (kHsKeyShift - kHsRegShift) + key_bits + (h.keys.any_wrong ? 1 : 0), &scratch);
-    if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
-    RBX_TRY(ss.sort.reserve(scratch));
-    e = launch_hllstream_grouped(h.dk, fl, first, e0, m, h.d_tab, h.d_cmd_elem, h.d_cmd_key, a, (uint32_t)(b - a),
-                                 h.d_changed, key_bits, h.keys.any_wrong, ss.sort.p, ss.sort.cap, h.st);
-    if (e) return fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e));
+    RBX_TRY(cell_sort_reserve<unsigned long long>(ss.sort, m, kHsRegShift, hllstream_end_bit(key_bits, h.keys.any_wrong)));
+    RBX_TRY(sort_failed(launch_hllstream_grouped(h.dk, fl, first, e0, m, h.d_tab, h.d_cmd_elem, h.d_cmd_key, a,
+                                                 (uint32_t)(b - a), h.d_changed, key_bits, h.keys.any_wrong, ss.sort.p,
+                                                 ss.sort.cap, h.st)));
     HIP_TRY(hipGetLastError());
     // the sparse keys' element lists: count, place, fill
     std::vector<uint32_t> skeys;   // canonical ids of the chunk's sparse keys, in order of first appearance
@@ -588,7 +576,7 @@ static int hs_phase(HsCall &h, uint64_t p0, uint64_t p1) {
             RBX_TRY(hs_rounds(h, p0, p1));
         } else {
             h.stats[kHsGroupedRuns]++;
-            const int key_bits = significant_bits32(h.nkeys - 1);
+            const int key_bits = significant_bits(h.nkeys - 1);
             for (uint64_t a = p0; a < p1;) {
                 // the commands [a, b) whose elements fit one chunk; a command that does not goes by rounds, alone
                 uint64_t b = a;
@@ -681,22 +669,9 @@ static int hll_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const u
     K.stamp.assign(nkeys, 0);
     K.round.assign(nkeys, 0);
     K.slot.assign(nkeys, 0);
-    std::vector<std::string> nm(nkeys);
-    {
-        std::unordered_map<std::string, uint32_t> first;
-        first.reserve(nkeys);
-        for (uint32_t i = 0; i < nkeys; ++i) {
-            nm[i] = name_of(names[i]);
-            K.canon[i] = first.emplace(nm[i], i).first->second;
-            if (K.canon[i] != i) {
-                K.wrong[i] = K.wrong[K.canon[i]];
-                continue;
-            }
-            const Entry *e = c->ks.find(nm[i]);
-            if (e && e->type != KType::Hll) K.wrong[i] = 1, K.any_wrong = true;
-            else if (e) K.hll[i] = e->hll;
-        }
-    }
+    std::vector<std::string> nm;
+    K.any_wrong = stream_names_resolve(c, names, nkeys, KType::Hll, &nm, K.canon.data(), K.wrong.data(),
+                                       [&](uint32_t i, const Entry &e) { K.hll[i] = e.hll; });
     // the commands that fail alone, and the keys the others create: the first PFADD that runs on a missing key
     uint64_t first_failed = ~0ULL;
     h.created.assign(n, 0);

@@ -8,9 +8,8 @@
 // The bitmap is addressed here as aligned 64-bit words (field_device.h has the layout and the loads and
 // stores); the kernels keep the bytes from the string's length to the allocation's end zero (they write
 // only inside fields the host sized the string for).
-// M/ = /root/reference/redisson/src/main/java/org/redisson/
+// M/ = redisson/src/main/java/org/redisson/ of the reference
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/rbx.h"
 #include "bloom_common.h"
@@ -329,39 +328,22 @@ void launch_fields_incr_sat(uint32_t *words, unsigned long long *len, uint64_t c
                        cap_bytes * 8, d_offs, d_incs, n, (uint32_t)size, is_signed ? 1u : 0u, new_len);
 }
 
-// the four u32 arrays of a chunk of n elements, then rocPRIM's temporary storage
-static size_t fields_arrays_bytes(uint32_t n) { return (((size_t)n * 4 + 255) & ~(size_t)255) * 4; }
-
-int fields_grouped_scratch_bytes(uint32_t n, int slot_bits, size_t *bytes) {
-    size_t temp = 0;
-    uint32_t *nil = nullptr;
-    const hipError_t e = rocprim::radix_sort_pairs(nullptr, temp, nil, nil, nil, nil, (size_t)n, 0u,
-                                                   (unsigned)slot_bits, (hipStream_t) nullptr);
-    if (e != hipSuccess) return (int)e;
-    *bytes = fields_arrays_bytes(n) + temp;
-    return 0;
-}
-
 int launch_fields_grouped(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed,
                           int size, int mode, const uint64_t *d_offs, const int64_t *d_values, uint32_t n,
                           int64_t *d_replies, uint8_t *d_nil, uint64_t new_len, int slot_bits, void *d_scratch,
                           size_t scratch_bytes, hipStream_t st) {
-    const size_t one = fields_arrays_bytes(n) / 4;
-    uint8_t *s = (uint8_t *)d_scratch;
-    uint32_t *slot_in = (uint32_t *)s, *slot_out = (uint32_t *)(s + one);
-    uint32_t *pos_in = (uint32_t *)(s + 2 * one), *pos_out = (uint32_t *)(s + 3 * one);
-    size_t temp = scratch_bytes - 4 * one;
+    CellSortBufs<uint32_t> b;  // the cells are the slots
+    int e = cell_sort_carve(d_scratch, scratch_bytes, n, &b);
+    if (e) return e;
     hipLaunchKernelGGL(k_fields_slots, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_offs, n, (uint32_t)size,
-                       slot_in, pos_in);
-    // stable, stream-ordered, over the slot's significant bits only
-    const hipError_t e = rocprim::radix_sort_pairs(s + 4 * one, temp, slot_in, slot_out, pos_in, pos_out, (size_t)n,
-                                                   0u, (unsigned)slot_bits, st);
-    if (e != hipSuccess) return (int)e;
+                       b.cell_in, b.pos_in);
+    e = cell_sort(b, n, 0, slot_bits, st);  // over the slot's significant bits only
+    if (e) return e;
     auto *runs = mode == RBX_OVERFLOW_SAT    ? k_fields_runs<RBX_OVERFLOW_SAT>
                  : mode == RBX_OVERFLOW_FAIL ? k_fields_runs<RBX_OVERFLOW_FAIL>
                                              : k_fields_runs<RBX_OVERFLOW_WRAP>;
     hipLaunchKernelGGL(runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, (u64 *)words, len, cap_bytes * 8, op,
-                       is_signed ? 1u : 0u, (uint32_t)size, slot_out, pos_out, n, d_values, d_replies, d_nil, new_len);
+                       is_signed ? 1u : 0u, (uint32_t)size, b.cell_out, b.pos_out, n, d_values, d_replies, d_nil, new_len);
     return 0;
 }
 

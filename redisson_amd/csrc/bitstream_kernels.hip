@@ -12,10 +12,10 @@
 // bit_in_word(i).
 // M/ = redisson/src/main/java/org/redisson/ of the reference
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/rbx.h"
 #include "bloom_common.h"
+#include "keymax_device.h"
 #include "rbx_kernels.h"
 
 namespace rbx {
@@ -32,19 +32,8 @@ __device__ __forceinline__ uint32_t key_bit(const BitKey &k, u64 idx) {
 // ---------------------------------------------------------------------------------
 // 1. The summary pass, before anything is written.  A lane folds its commands into registers, a
 // workgroup into one set of atomics on the summary words.  The per-key maximum (of index + 1: 0 = the
-// key has no SETBIT that runs) is an atomicMax, kept rare: a lane holds the maximum back while its
-// commands stay on one key, a load that already shows as much settles it without the atomic, and the
-// lanes of a wave that end on one key send one.  (One atomicMax per SETBIT measured 191 ms for 2^24
-// SETBITs on ONE key, every one of them on the same word, against 2.2 ms on 4,096 keys.)
+// key has no SETBIT that runs) goes through keymax_device.h, which keeps its atomicMax rare.
 // ---------------------------------------------------------------------------------
-// keymax[key] = max(keymax[key], m); m = 0: nothing.  The word only rises during the pass, so a load
-// that shows m or more settles it; the load goes past the L1, which other CUs' atomics do not refresh.
-__device__ __forceinline__ void keymax_raise(u64 *keymax, uint32_t key, u64 m) {
-    if (m == 0) return;
-    if (__hip_atomic_load(keymax + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= m) return;
-    atomicMax(keymax + key, m);
-}
-
 __global__ __launch_bounds__(256) void k_bs_summary(const uint32_t *__restrict__ ckey, const uint8_t *__restrict__ cop,
                                                     const uint64_t *__restrict__ cidx, uint64_t n, uint32_t nkeys,
                                                     const uint32_t *__restrict__ canon,
@@ -53,8 +42,7 @@ __global__ __launch_bounds__(256) void k_bs_summary(const uint32_t *__restrict__
     __shared__ uint32_t s_flags[4];
     u64 oob = ~0ULL, wr = ~0ULL, mx = 0;
     uint32_t flags = 0;
-    uint32_t held = ~0u;  // the key whose maximum this lane holds back, and that maximum (0 = nothing held)
-    u64 held_max = 0;
+    KeymaxHeld held;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint32_t k = ckey[i];
@@ -71,32 +59,10 @@ __global__ __launch_bounds__(256) void k_bs_summary(const uint32_t *__restrict__
             wr = min(wr, (u64)i);
         } else {
             mx = max(mx, idx);
-            if (op) {
-                const uint32_t c = canon[k];
-                if (c != held) {
-                    keymax_raise(keymax, held, held_max);
-                    held = c;
-                    held_max = 0;
-                }
-                held_max = max(held_max, idx + 1);
-            }
+            if (op) held.take(keymax, canon[k], idx + 1);
         }
     }
-    // what the lanes still hold: one atomic per wave when they all hold the same key (a batch on few keys)
-    {
-        uint32_t lo = held_max ? held : ~0u;
-        u64 m = held_max;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
-            m = max(m, (u64)__shfl_xor(m, d, 64));
-        }
-        if (__all(!held_max || held == lo)) {
-            if ((threadIdx.x & 63) == 0) keymax_raise(keymax, lo, m);
-        } else {
-            keymax_raise(keymax, held, held_max);
-        }
-    }
+    held.flush(keymax);
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
         oob = min(oob, (u64)__shfl_down(oob, d, 64));
@@ -272,39 +238,20 @@ void launch_bitstream_lengths(const BitKey *d_tab, const unsigned long long *d_k
     hipLaunchKernelGGL(k_bs_lengths, dim3(grid_for(nkeys, kMaxGrid)), dim3(256), 0, st, d_tab, d_keymax, nkeys);
 }
 
-// the two u64 and the two u32 arrays of a chunk of n commands, then rocPRIM's temporary storage
-static size_t bitstream_cells_bytes(uint32_t n) { return ((size_t)n * 8 + 255) & ~(size_t)255; }
-static size_t bitstream_pos_bytes(uint32_t n) { return ((size_t)n * 4 + 255) & ~(size_t)255; }
-
-int bitstream_grouped_scratch_bytes(uint32_t n, int cell_bits, size_t *bytes) {
-    size_t temp = 0;
-    u64 *nil8 = nullptr;
-    uint32_t *nil4 = nullptr;
-    const hipError_t e = rocprim::radix_sort_pairs(nullptr, temp, nil8, nil8, nil4, nil4, (size_t)n, 0u,
-                                                   (unsigned)cell_bits, (hipStream_t) nullptr);
-    if (e != hipSuccess) return (int)e;
-    *bytes = 2 * bitstream_cells_bytes(n) + 2 * bitstream_pos_bytes(n) + temp;
-    return 0;
-}
-
 int launch_bitstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const uint8_t *d_op, const uint64_t *d_idx,
                              uint32_t n, uint8_t *d_replies, int index_bits, int key_bits, bool has_failed,
                              void *d_scratch, size_t scratch_bytes, hipStream_t st) {
-    const size_t cb = bitstream_cells_bytes(n), pb = bitstream_pos_bytes(n);
-    uint8_t *s = (uint8_t *)d_scratch;
-    u64 *cell_in = (u64 *)s, *cell_out = (u64 *)(s + cb);
-    uint32_t *pos_in = (uint32_t *)(s + 2 * cb), *pos_out = (uint32_t *)(s + 2 * cb + pb);
-    size_t temp = scratch_bytes - 2 * cb - 2 * pb;
+    CellSortBufs<u64> b;
+    int e = cell_sort_carve(d_scratch, scratch_bytes, n, &b);
+    if (e) return e;
     // the bit above every cell (index_bits + key_bits <= 63); the sort looks at it only when a command failed
     const u64 failed_cell = 1ULL << (index_bits + key_bits);
     const int cell_bits = index_bits + key_bits + (has_failed ? 1 : 0);
     hipLaunchKernelGGL(k_bs_pairs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_key, d_idx, n,
-                       (uint32_t)index_bits, failed_cell, cell_in, pos_in, d_replies);
-    // stable, stream-ordered, over the cells' significant bits only
-    const hipError_t e = rocprim::radix_sort_pairs(s + 2 * cb + 2 * pb, temp, cell_in, cell_out, pos_in, pos_out,
-                                                   (size_t)n, 0u, (unsigned)cell_bits, st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_bs_runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_op, cell_out, pos_out, n,
+                       (uint32_t)index_bits, failed_cell, b.cell_in, b.pos_in, d_replies);
+    e = cell_sort(b, n, 0, cell_bits, st);  // over the cells' significant bits only
+    if (e) return e;
+    hipLaunchKernelGGL(k_bs_runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_op, b.cell_out, b.pos_out, n,
                        (uint32_t)index_bits, failed_cell, d_replies);
     return 0;
 }

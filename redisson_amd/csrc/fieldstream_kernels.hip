@@ -11,11 +11,11 @@
 // a SET / INCRBY always lies inside its allocation; a GET reads zero at or past it (field_device.h).
 // M/ = redisson/src/main/java/org/redisson/ of the reference
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/rbx.h"
 #include "bloom_common.h"
 #include "field_device.h"
+#include "keymax_device.h"
 #include "rbx_kernels.h"
 
 namespace rbx {
@@ -55,16 +55,8 @@ __device__ __forceinline__ void fs_exec(const BitKey &k, const rbx_field_cmd &c,
 // ---------------------------------------------------------------------------------
 // 1. The summary pass, before anything is written (k_bs_summary's form).  A lane folds its commands into
 // registers, a workgroup into one set of atomics on the summary words.  The per-key maximum (of offset +
-// size over the SET / INCRBY that run: 0 = none) is an atomicMax kept rare as there: a lane holds its
-// maximum back while its commands stay on one key, a load that already shows as much settles it without
-// the atomic, and the lanes of a wave that end on one key send one.
+// size over the SET / INCRBY that run: 0 = none) goes through keymax_device.h, as there.
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ void fs_keymax_raise(u64 *keymax, uint32_t key, u64 m) {
-    if (m == 0) return;
-    if (__hip_atomic_load(keymax + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= m) return;
-    atomicMax(keymax + key, m);
-}
-
 __global__ __launch_bounds__(256) void k_fs_summary(const uint32_t *__restrict__ ckey,
                                                     const rbx_field_cmd *__restrict__ cmds, uint64_t n, uint32_t nkeys,
                                                     const uint32_t *__restrict__ canon,
@@ -73,8 +65,7 @@ __global__ __launch_bounds__(256) void k_fs_summary(const uint32_t *__restrict__
     __shared__ uint32_t s_flags[4];
     u64 bad_type = ~0ULL, bad_off = ~0ULL, wr = ~0ULL, mx = 0, sizes = 0;
     uint32_t flags = 0;
-    uint32_t held = ~0u;  // the key whose maximum this lane holds back, and that maximum (0 = nothing held)
-    u64 held_max = 0;
+    KeymaxHeld held;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint32_t k = ckey[i];
@@ -99,31 +90,11 @@ __global__ __launch_bounds__(256) void k_fs_summary(const uint32_t *__restrict__
             if ((uint32_t)c.offset % c.size != 0) flags |= kFsUnaligned;
             if (c.op != RBX_FIELD_GET) {
                 flags |= kFsWrap << c.overflow;
-                const uint32_t cn = canon[k];
-                if (cn != held) {
-                    fs_keymax_raise(keymax, held, held_max);
-                    held = cn;
-                    held_max = 0;
-                }
-                held_max = max(held_max, end);
+                held.take(keymax, canon[k], end);
             }
         }
     }
-    // what the lanes still hold: one atomic per wave when they all hold the same key (a batch on few keys)
-    {
-        uint32_t lo = held_max ? held : ~0u;
-        u64 m = held_max;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
-            m = max(m, (u64)__shfl_xor(m, d, 64));
-        }
-        if (__all(!held_max || held == lo)) {
-            if ((threadIdx.x & 63) == 0 && lo != ~0u) fs_keymax_raise(keymax, lo, m);
-        } else {
-            fs_keymax_raise(keymax, held, held_max);
-        }
-    }
+    held.flush(keymax);
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
         bad_type = min(bad_type, (u64)__shfl_down(bad_type, d, 64));
@@ -330,44 +301,25 @@ void launch_fieldstream_serial(const BitKey *d_tab, const uint32_t *d_key, const
     hipLaunchKernelGGL(k_fs_serial, dim3(1), dim3(1), 0, st, d_tab, d_key, d_cmds, n, d_replies, d_status);
 }
 
-// the two u64 and the two u32 arrays of a chunk of n commands, then rocPRIM's temporary storage
-static size_t fs_cells_bytes(uint32_t n) { return ((size_t)n * 8 + 255) & ~(size_t)255; }
-static size_t fs_pos_bytes(uint32_t n) { return ((size_t)n * 4 + 255) & ~(size_t)255; }
-
-int fieldstream_grouped_scratch_bytes(uint32_t n, int cell_bits, size_t *bytes) {
-    size_t temp = 0;
-    u64 *nil8 = nullptr;
-    uint32_t *nil4 = nullptr;
-    const hipError_t e = rocprim::radix_sort_pairs(nullptr, temp, nil8, nil8, nil4, nil4, (size_t)n, 0u,
-                                                   (unsigned)cell_bits, (hipStream_t) nullptr);
-    if (e != hipSuccess) return (int)e;
-    *bytes = 2 * fs_cells_bytes(n) + 2 * fs_pos_bytes(n) + temp;
-    return 0;
-}
-
 int launch_fieldstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const rbx_field_cmd *d_cmds, uint32_t n,
                                int64_t *d_replies, uint8_t *d_status, int word_bits, int key_bits, bool has_failed,
                                void *d_scratch, size_t scratch_bytes, hipStream_t st) {
-    const size_t cb = fs_cells_bytes(n), pb = fs_pos_bytes(n);
-    uint8_t *s = (uint8_t *)d_scratch;
-    u64 *cell_in = (u64 *)s, *cell_out = (u64 *)(s + cb);
-    uint32_t *pos_in = (uint32_t *)(s + 2 * cb), *pos_out = (uint32_t *)(s + 2 * cb + pb);
-    size_t temp = scratch_bytes - 2 * cb - 2 * pb;
+    CellSortBufs<u64> b;
+    int e = cell_sort_carve(d_scratch, scratch_bytes, n, &b);
+    if (e) return e;
     // the bit above every cell (word_bits + key_bits <= 57); the sort looks at it only when a command failed
     const u64 failed_cell = 1ULL << (word_bits + key_bits);
     const int cell_bits = word_bits + key_bits + (has_failed ? 1 : 0);
     hipLaunchKernelGGL(k_fs_cells, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_key, d_cmds, n,
-                       (uint32_t)word_bits, failed_cell, cell_in, pos_in, d_replies, d_status);
-    // stable, stream-ordered, over the cells' significant bits only
-    const hipError_t e = rocprim::radix_sort_pairs(s + 2 * cb + 2 * pb, temp, cell_in, cell_out, pos_in, pos_out,
-                                                   (size_t)n, 0u, (unsigned)cell_bits, st);
-    if (e != hipSuccess) return (int)e;
+                       (uint32_t)word_bits, failed_cell, b.cell_in, b.pos_in, d_replies, d_status);
+    e = cell_sort(b, n, 0, cell_bits, st);  // over the cells' significant bits only
+    if (e) return e;
     if (word_bits)
-        hipLaunchKernelGGL(k_fs_word_runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_cmds, cell_out, pos_out,
-                           n, (uint32_t)word_bits, failed_cell, d_replies, d_status);
+        hipLaunchKernelGGL(k_fs_word_runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_cmds, b.cell_out,
+                           b.pos_out, n, (uint32_t)word_bits, failed_cell, d_replies, d_status);
     else
-        hipLaunchKernelGGL(k_fs_key_runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_cmds, cell_out, pos_out,
-                           n, failed_cell, d_replies, d_status);
+        hipLaunchKernelGGL(k_fs_key_runs, dim3(grid_for(n, kMaxGrid)), dim3(256), 0, st, d_tab, d_cmds, b.cell_out,
+                           b.pos_out, n, failed_cell, d_replies, d_status);
     return 0;
 }
 

@@ -10,7 +10,7 @@
 //                   record, its hash; emits cell = canon << 20 | register << 6 | count and the command's
 //                   position in the chunk.  An element of a command that fails alone gets the one bit above
 //                   every cell.
-//   2. rocPRIM      a stable radix sort of the pairs over bits [6, 20 + key bits [+ 1]): equal (key, register)
+//   2. cell_sort    a stable radix sort of the pairs over bits [6, 20 + key bits [+ 1]): equal (key, register)
 //                   stay in element order, which is command order, and the count rides in the unsorted low bits.
 //   3. k_hs_runs    the lane at the head of a run of equal (key, register) reads the register byte once, walks
 //                   the run, stores 1 into the changed word of every command whose count rises above what
@@ -20,7 +20,6 @@
 // around).
 // M/ = redisson/src/main/java/org/redisson/ of the reference
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/rbx.h"
 #include "bloom_common.h"
@@ -92,45 +91,24 @@ __global__ __launch_bounds__(256) void k_hs_promoted(uint32_t *const *__restrict
     if (i < n) out[i] = states[i][0];
 }
 
-// the two u64 and the two u32 arrays of a chunk of m elements, then rocPRIM's temporary storage
-static size_t hs_cells_bytes(uint32_t m) { return ((size_t)m * 8 + 255) & ~(size_t)255; }
-static size_t hs_pos_bytes(uint32_t m) { return ((size_t)m * 4 + 255) & ~(size_t)255; }
-
-int hllstream_grouped_scratch_bytes(uint32_t m, int cell_bits, size_t *bytes) {
-    size_t temp = 0;
-    u64 *nil8 = nullptr;
-    uint32_t *nil4 = nullptr;
-    const hipError_t e = rocprim::radix_sort_pairs(nullptr, temp, nil8, nil8, nil4, nil4, (size_t)m, (unsigned)kHsRegShift,
-                                                   (unsigned)(kHsRegShift + cell_bits), (hipStream_t) nullptr);
-    if (e != hipSuccess) return (int)e;
-    *bytes = 2 * hs_cells_bytes(m) + 2 * hs_pos_bytes(m) + temp;
-    return 0;
-}
-
 int launch_hllstream_grouped(const KeysDev &elems, int elen_fast, uint64_t first, uint64_t elem0, uint32_t m,
                              const HllKey *d_tab, const uint64_t *d_cmd_elem, const uint32_t *d_cmd_key, uint64_t cmd0,
                              uint32_t ncmds, uint32_t *d_changed, int key_bits, bool has_failed, void *d_scratch,
                              size_t scratch_bytes, hipStream_t st) {
     if (!m || !ncmds) return 0;
-    const size_t cb = hs_cells_bytes(m), pb = hs_pos_bytes(m);
-    if (scratch_bytes < 2 * cb + 2 * pb) return (int)hipErrorInvalidValue;
-    uint8_t *s = (uint8_t *)d_scratch;
-    u64 *cell_in = (u64 *)s, *cell_out = (u64 *)(s + cb);
-    uint32_t *pos_in = (uint32_t *)(s + 2 * cb), *pos_out = (uint32_t *)(s + 2 * cb + pb);
-    size_t temp = scratch_bytes - 2 * cb - 2 * pb;
+    CellSortBufs<u64> b;
+    int e = cell_sort_carve(d_scratch, scratch_bytes, m, &b);
+    if (e) return e;
     // the bit above every cell (20 + key_bits <= 52); the sort looks at it only when a command fails
     const u64 failed_cell = 1ULL << (kHsKeyShift + key_bits);
-    const int cell_bits = (kHsKeyShift - kHsRegShift) + key_bits + (has_failed ? 1 : 0);
     with_klen<true>(elen_fast, [&](auto elen) {
         hipLaunchKernelGGL(k_hs_pairs<decltype(elen)::value>, dim3(grid_for(m, kMaxGrid)), dim3(256), 0, st, elems, first,
-                           elem0, m, d_tab, d_cmd_elem, d_cmd_key, cmd0, ncmds, failed_cell, cell_in, pos_in);
+                           elem0, m, d_tab, d_cmd_elem, d_cmd_key, cmd0, ncmds, failed_cell, b.cell_in, b.pos_in);
     });
-    // stable, stream-ordered, over the (key, register) bits only
-    const hipError_t e = rocprim::radix_sort_pairs(s + 2 * cb + 2 * pb, temp, cell_in, cell_out, pos_in, pos_out, (size_t)m,
-                                                   (unsigned)kHsRegShift, (unsigned)(kHsRegShift + cell_bits), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_hs_runs, dim3(grid_for(m, kMaxGrid)), dim3(256), 0, st, d_tab, cell_out, pos_out, m, failed_cell,
-                       d_changed + cmd0);
+    e = cell_sort(b, m, kHsRegShift, hllstream_end_bit(key_bits, has_failed), st);  // the (key, register) bits only
+    if (e) return e;
+    hipLaunchKernelGGL(k_hs_runs, dim3(grid_for(m, kMaxGrid)), dim3(256), 0, st, d_tab, b.cell_out, b.pos_out, m,
+                       failed_cell, d_changed + cmd0);
     return 0;
 }
 

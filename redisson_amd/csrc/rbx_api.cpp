@@ -132,9 +132,16 @@ int names_of(const rbx_name *names, uint32_t n, std::vector<std::string> *out) {
     if (n && !names) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL names");
     out->clear();
     for (uint32_t i = 0; i < n; ++i) {
-        if (!names[i].bytes && names[i].len) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
+        if (bad_name(names[i])) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
         out->push_back(name_of(names[i]));
     }
+    return RBX_OK;
+}
+
+int stream_names_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys) {
+    if (!c || (nkeys && !names)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (uint32_t i = 0; i < nkeys; ++i)
+        if (bad_name(names[i])) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL key name");
     return RBX_OK;
 }
 

@@ -514,12 +514,61 @@ static constexpr uint64_t kTinyDoneAt = kTinyArenaAt + kTinyArenaBytes;  // one-
 static constexpr size_t kTinyBlock = kTinyDoneAt + 64;
 
 // ---- helpers that cross a file boundary (api_staging.h has the staging tiers') ----------------------
+inline bool bad_name(const rbx_name &n) { return !n.bytes && n.len; }
+
+// the significant bits of v: 0 for 0, 64 for a value with bit 63 set (a shift by 64 is undefined)
+inline int significant_bits(uint64_t v) {
+    int b = 0;
+    while (b < 64 && (v >> b)) ++b;
+    return b;
+}
+
+// The grouped paths' sort (rbx_kernels.h, cell_sort.hip): sort_failed turns what it or a launch_*_grouped
+// returns into the call's error; cell_sort_reserve sizes `buf` for n pairs sorted over [begin_bit, end_bit).
+inline int sort_failed(int e) {
+    return e ? fail(RBX_E_DEVICE, std::string("radix sort: ") + hipGetErrorString((hipError_t)e)) : RBX_OK;
+}
+template <class Cell> int cell_sort_reserve(DevBuf &buf, uint32_t n, int begin_bit, int end_bit) {
+    size_t bytes = 0;
+    RBX_TRY(sort_failed(cell_sort_scratch_bytes<Cell>(n, begin_bit, end_bit, &bytes)));
+    return buf.reserve(bytes);
+}
+
+std::string name_of(const rbx_name &n);
+// The names of one multi-key stream call (rbx_bitset_stream, rbx_bitset_field_stream, rbx_hll_stream), resolved
+// once, lookup only, under the context lock.  Equal names are one key, known by its first entry: canon[i] = the
+// first entry with entry i's bytes (its canonical id).  wrong[i] = the key holds another type than `expect`, which
+// fails its commands.  canon and wrong are the caller's arrays of nkeys entries, in whatever form it keeps them;
+// found(i, entry) is called for each canonical key that exists with the expected type, while the entry is at
+// hand.  Returns "some key is wrong".
+template <class Found>
+bool stream_names_resolve(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, KType expect, std::vector<std::string> *nm,
+                          uint32_t *canon, uint8_t *wrong, Found found) {
+    bool any_wrong = false;
+    nm->resize(nkeys);
+    std::unordered_map<std::string, uint32_t> first;
+    first.reserve(nkeys);
+    for (uint32_t i = 0; i < nkeys; ++i) {
+        (*nm)[i] = name_of(names[i]);
+        canon[i] = first.emplace((*nm)[i], i).first->second;
+        if (canon[i] != i) {
+            wrong[i] = wrong[canon[i]];
+            continue;
+        }
+        const Entry *e = c->ks.find((*nm)[i]);
+        wrong[i] = e && e->type != expect;
+        if (wrong[i]) any_wrong = true;
+        else if (e) found(i, *e);
+    }
+    return any_wrong;
+}
 // rbx_api.cpp
+// NULL context, NULL names, a name of NULL bytes with a length
+int stream_names_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys);
 int new_bitmap(rbx_ctx *c, uint64_t size_bits, hipStream_t st, std::shared_ptr<Bitmap> *out);
 int grow_bitmap(rbx_ctx *c, Bitmap &b, uint64_t size_bits, hipStream_t st);
 uint64_t read_dev_u64(rbx_ctx *c, const unsigned long long *p, int *rc);
 int check_offsets(int64_t size);
-std::string name_of(const rbx_name &n);
 int names_of(const rbx_name *names, uint32_t n, std::vector<std::string> *out);
 int cstr_names(const char *const *names, uint32_t n, std::vector<std::string> *out);
 int bitmap_for(rbx_ctx *c, const std::string &name, uint64_t nbits, bool create, hipStream_t st,

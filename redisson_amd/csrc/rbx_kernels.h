@@ -312,6 +312,36 @@ void launch_bits_max(const uint64_t *d_idx, uint64_t n, unsigned long long *d_ou
 // SETBIT bit value; *d_old = the bit before
 void launch_bits_set_one(uint32_t *words, unsigned long long *len, uint64_t bit, bool value, unsigned long long *d_old,
                          hipStream_t st);
+// ---- cell_sort.hip
+// What every grouped path below shares.  Commands on different cells are independent, those on one cell totally
+// ordered: a pairs kernel emits (cell, position), a stable radix sort by cell lists each cell's commands in array
+// order, and a runs kernel gives each run of equal cells to the lane at its head.  The cell encodings and the
+// runs kernels are each path's own; the sort and its scratch are here.  Cell: uint32_t (the single-key BITFIELD
+// batch's slots) or unsigned long long (the streams' cells); positions are 32-bit, n <= 2^30.
+// A caller's scratch: cell_in | cell_out | pos_in | pos_out, each rounded up to 256 bytes, then rocPRIM's
+// temporary storage.
+inline size_t cell_sort_array_bytes(uint32_t n, size_t elem) { return ((size_t)n * elem + 255) & ~(size_t)255; }
+template <class Cell> struct CellSortBufs {
+    Cell *cell_in, *cell_out;
+    uint32_t *pos_in, *pos_out;
+    void *temp;
+    size_t temp_bytes;
+};
+// the scratch for n pairs sorted over the cells' bits [begin_bit, end_bit); 0 or a hipError_t
+template <class Cell> int cell_sort_scratch_bytes(uint32_t n, int begin_bit, int end_bit, size_t *bytes);
+// carves a scratch of at least that size; hipErrorInvalidValue when it cannot hold the four arrays
+template <class Cell> int cell_sort_carve(void *d_scratch, size_t scratch_bytes, uint32_t n, CellSortBufs<Cell> *b) {
+    const size_t cb = cell_sort_array_bytes(n, sizeof(Cell)), pb = cell_sort_array_bytes(n, 4);
+    if (scratch_bytes < 2 * cb + 2 * pb) return (int)hipErrorInvalidValue;
+    uint8_t *s = (uint8_t *)d_scratch;
+    *b = CellSortBufs<Cell>{(Cell *)s, (Cell *)(s + cb), (uint32_t *)(s + 2 * cb), (uint32_t *)(s + 2 * cb + pb),
+                            s + 2 * cb + 2 * pb, scratch_bytes - 2 * cb - 2 * pb};
+    return 0;
+}
+// (cell_in, pos_in) -> (cell_out, pos_out), stable and stream-ordered, looking at bits [begin_bit, end_bit) only;
+// 0 or a hipError_t
+template <class Cell> int cell_sort(const CellSortBufs<Cell> &b, uint32_t n, int begin_bit, int end_bit, hipStream_t st);
+
 // bitfield_kernels.hip -- BITFIELD GET / SET / INCRBY (RBX_FIELD_* of rbx.h) on fields of one type;
 // `words` / cap_bytes: a bitmap's allocation, which already holds every field written
 // d_out2[0] = max(d_out2[0], max offset), d_out2[1] |= 1 when an offset is no multiple of size; with
@@ -331,9 +361,7 @@ void launch_fields_incr_sat(uint32_t *words, unsigned long long *len, uint64_t c
 // SET / INCRBY in array order on offsets that are multiples of size, n <= 2^30: a stable sort by
 // slot (slot_bits = the significant bits of the largest offset / size), then one lane per slot.
 // d_replies nullable.  mode = RBX_OVERFLOW_*; under FAIL d_nil[i] (nullable) = reply i is nil.  The
-// scratch size for n elements comes from fields_grouped_scratch_bytes.
-// Both return 0 or a hipError_t.
-int fields_grouped_scratch_bytes(uint32_t n, int slot_bits, size_t *bytes);
+// scratch: cell_sort_scratch_bytes<uint32_t>(n, 0, slot_bits).  Returns 0 or a hipError_t.
 int launch_fields_grouped(uint32_t *words, unsigned long long *len, uint64_t cap_bytes, int op, int is_signed,
                           int size, int mode, const uint64_t *d_offs, const int64_t *d_values, uint32_t n,
                           int64_t *d_replies, uint8_t *d_nil, uint64_t new_len, int slot_bits, void *d_scratch,
@@ -445,9 +473,8 @@ void launch_bitstream_serial(const BitKey *d_tab, const uint32_t *d_key, const u
                              uint64_t n, uint8_t *d_replies, hipStream_t st);
 // any batch of n <= 2^30 commands: a stable sort by cell = canon << index_bits | index, then one lane per
 // cell.  index_bits: the significant bits of the largest index (1..32); key_bits: those of nkeys - 1 (<= 31);
-// has_failed: some command of the batch fails.  The scratch size comes from bitstream_grouped_scratch_bytes
-// with cell_bits = index_bits + key_bits + has_failed.  Both return 0 or a hipError_t.
-int bitstream_grouped_scratch_bytes(uint32_t n, int cell_bits, size_t *bytes);
+// has_failed: some command of the batch fails.  The scratch: cell_sort_scratch_bytes<unsigned long long>(n, 0,
+// index_bits + key_bits + has_failed).  Returns 0 or a hipError_t.
 int launch_bitstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const uint8_t *d_op, const uint64_t *d_idx,
                              uint32_t n, uint8_t *d_replies, int index_bits, int key_bits, bool has_failed,
                              void *d_scratch, size_t scratch_bytes, hipStream_t st);
@@ -492,9 +519,8 @@ void launch_fieldstream_serial(const BitKey *d_tab, const uint32_t *d_key, const
 // any batch of n <= 2^30 commands: a stable sort by cell, then one lane per cell.  word_bits > 0: cell = canon
 // << word_bits | offset >> 6 (word_bits = the significant bits of [kFsMaxWord], at least 1; the batch must not
 // have kFsStraddles); word_bits = 0: cell = canon.  key_bits: the significant bits of nkeys - 1, at least 1;
-// has_failed: some command of the batch fails.  The scratch size comes from fieldstream_grouped_scratch_bytes
-// with cell_bits = word_bits + key_bits + has_failed.  Both return 0 or a hipError_t.
-int fieldstream_grouped_scratch_bytes(uint32_t n, int cell_bits, size_t *bytes);
+// has_failed: some command of the batch fails.  The scratch: cell_sort_scratch_bytes<unsigned long long>(n, 0,
+// word_bits + key_bits + has_failed).  Returns 0 or a hipError_t.
 int launch_fieldstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const rbx_field_cmd *d_cmds, uint32_t n,
                                int64_t *d_replies, uint8_t *d_status, int word_bits, int key_bits, bool has_failed,
                                void *d_scratch, size_t scratch_bytes, hipStream_t st);
@@ -594,10 +620,10 @@ constexpr int kHsRegShift = 6, kHsKeyShift = 20;  // cell = canon << 20 | regist
 // elements from elem0 on in the call's numbering (d_cmd_elem's) and from `first` on in `elems`.  d_cmd_elem
 // and d_cmd_key are the call's arrays (a PFCOUNT or an empty PFADD of the range owns no element); d_changed
 // has one word per command of the call and gets a 1 for each command that raises a register.  key_bits: the
-// significant bits of nkeys - 1; has_failed: some key of the table has kHllKeyFailed.  The scratch size comes
-// from hllstream_grouped_scratch_bytes with cell_bits = 14 + key_bits + has_failed.  Both return 0 or a
-// hipError_t.
-int hllstream_grouped_scratch_bytes(uint32_t m, int cell_bits, size_t *bytes);
+// significant bits of nkeys - 1; has_failed: some key of the table has kHllKeyFailed.  The sort looks at the
+// (key, register) bits only, so the scratch is cell_sort_scratch_bytes<unsigned long long>(m, kHsRegShift,
+// hllstream_end_bit(key_bits, has_failed)).  Returns 0 or a hipError_t.
+constexpr int hllstream_end_bit(int key_bits, bool has_failed) { return kHsKeyShift + key_bits + (has_failed ? 1 : 0); }
 int launch_hllstream_grouped(const KeysDev &elems, int elen_fast, uint64_t first, uint64_t elem0, uint32_t m,
                              const HllKey *d_tab, const uint64_t *d_cmd_elem, const uint32_t *d_cmd_key, uint64_t cmd0,
                              uint32_t ncmds, uint32_t *d_changed, int key_bits, bool has_failed, void *d_scratch,

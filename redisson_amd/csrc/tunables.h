@@ -117,7 +117,7 @@ struct Tunables {
     // 1 = always rounds, 2 = always grouped.  All exact.
     std::atomic<int> hllstream_path{0};
     // "hllstream_chunk": elements per chunk of the grouped path (36.125 bytes of sort scratch per element, what
-    // hllstream_grouped_scratch_bytes returns at 2^25: 24 of cells and positions, the rest rocPRIM's temporary
+    // cell_sort_scratch_bytes returns at 2^25: 24 of cells and positions, the rest rocPRIM's temporary
     // storage; 2^25 elements are 1.129 GiB); a command with more elements than this runs by rounds, alone
     std::atomic<uint64_t> hllstream_chunk{1 << 25};
     // "hllstream_elems_per_round": the auto rule takes the grouped path iff the run's rounds R exceed
