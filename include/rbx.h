@@ -609,7 +609,8 @@ int rbx_hll_import_n(rbx_ctx *ctx, rbx_name name, const uint8_t *bytes, uint64_t
  *             the state before it, then its PFADDs as one add run, whose launch count does not depend on how
  *             often keys repeat.  Adds followed by counts are two phases; add, count, add, count
  *             on one key is one phase per pair -- a PFCOUNT is a 16,384-register scan either way.
- *   Scope     multi-key PFCOUNT and PFMERGE stay single calls.  The node router and the Java shim do not
+ *   Scope     multi-key PFCOUNT and PFMERGE are not part of a stream: many of them travel through
+ *             rbx_hll_count_groups / rbx_hll_merge_groups below.  The node router and the Java shim do not
  *             carry this call.  There is no point-in-time PFCOUNT from inside one launch: a count that must
  *             see an earlier add of its key closes the phase.
  * The command arrays, `names`, `replies` and `status` are host memory in both forms: the host must know the
@@ -622,6 +623,52 @@ int rbx_hll_stream(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const ui
 int rbx_hll_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
                        const uint8_t *cmd_op, const uint64_t *cmd_elem, uint64_t n, const rbx_keys *d_elements,
                        uint64_t *replies, uint8_t *status, void *stream);
+/* Many multi-key PFCOUNTs, and many PFMERGEs, in one call each: what RHyperLogLog.countWith / mergeWith send one
+ * command at a time (M/RedissonHyperLogLog.java:89-102), what a batch queues through
+ * RBatch.getHyperLogLog(name).countWithAsync / mergeWithAsync (M/RedissonBatch.java:57-64), and Spring Data's
+ * pfCount(k1, k2, ..) / pfMerge between openPipeline() and closePipeline(): the roll-ups that sketches exist for
+ * (daily uniques from 24 hourly HLLs, one window per group).
+ *   Commands  group g names the keys names[grp_key[grp_off[g] .. grp_off[g + 1])] (grp_off has ngroups + 1 entries
+ *             and ascends from 0).  rbx_hll_count_groups: PFCOUNT of those keys, at least one.
+ *             rbx_hll_merge_groups: PFMERGE names[grp_dest[g]] <those keys>; no source is legal.  Two entries of
+ *             `names` with equal bytes are one key.
+ *   Result    exactly that of ngroups single calls in array order -- rbx_hll_count_n into out[g], rbx_hll_merge_n.
+ *             A count of one entry is the single-key PFCOUNT with the header cache: a valid cache is returned as
+ *             it stands, otherwise the recount is stored.  A count of two or more entries -- counted as Redis
+ *             counts argc, so [a, a] is one -- is the count of the register maxima and touches no header.  A
+ *             missing key is empty; counts do not affect each other.  A merge includes the destination's own
+ *             registers, creates a missing destination (sparse, one XZERO) first, leaves it dense iff it or any
+ *             existing source is dense, else writes the maxima back through hllSparseSet in ascending register
+ *             order (which may promote: a value above 32, growth past hll-sparse-max-bytes), and sets the cached
+ *             cardinality's invalid bit always, also without sources; the low 63 bits and the timeout stay.
+ *             Later merges see earlier ones: a destination may be a later group's source, a source a later
+ *             group's destination, one key the destination twice; a source equal to its destination changes
+ *             nothing.
+ *   Failures  the pipelined-batch rule of RBX_E_REDIS above: a group that names a key of another type (a bit
+ *             string, a {name}:config hash) anywhere fails alone.  status[g] (nullable array) is 0xFF, out[g] is 0,
+ *             and it changes, stores and creates nothing.  Every other group runs (status 0) with its exact
+ *             result.  The call returns RBX_E_WRONGTYPE, the code of the first failing group in array order, with
+ *             the HLL wrong-type message in rbx_last_error().
+ *   Caller    a count group without entries, an entry or destination >= nkeys, offsets that do not ascend from 0,
+ *             or a NULL array with ngroups > 0 is RBX_E_ILLEGAL_ARGUMENT with nothing changed and nothing created.
+ *             ngroups = 0 sends nothing.  A call takes fewer than 2^31 groups and 2^32 entries.
+ *   Cost      each distinct name is looked up once.  Counts: one table upload, one launch that reads every
+ *             member's 16 KiB once and ends in the estimator (plus a fill and a one-lane-per-group finish launch
+ *             when few groups are spread over several workgroups each, rbx_tune "hllgroups_split"), one copy
+ *             back, one wait; one-key counts with a valid cache never reach the device; a union that holds a
+ *             register of 51 is finished on the host.  Merges: the host splits the groups into phases -- a group
+ *             closes the phase before it when its destination is a destination or a source of an earlier group of
+ *             the phase, or one of its sources is such a destination -- and runs each phase as one merge launch,
+ *             one write-back launch for the destinations that stay sparse, and at most one wait (for the sparse
+ *             keys' promotion words).  Independent merges are one phase; a chain of dependent ones is a phase
+ *             each.
+ *   Scope     the node router and the Java shim do not carry these calls.  No handle or device-pointer forms.
+ *             PFADD and single-key PFCOUNT streams stay rbx_hll_stream's.
+ * All arrays are host memory: the host must know the keys to create the destinations. */
+int rbx_hll_count_groups(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint64_t *grp_off,
+                         const uint32_t *grp_key, uint32_t ngroups, uint64_t *out, uint8_t *status);
+int rbx_hll_merge_groups(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *grp_dest,
+                         const uint64_t *grp_off, const uint32_t *grp_key, uint32_t ngroups, uint8_t *status);
 
 /* ---- HLL handles and the device-resident path ------------------------------------- */
 /* Opens (creating an empty HLL if absent and create != 0). */

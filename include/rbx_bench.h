@@ -53,6 +53,10 @@ int rbx_bench_fieldstream_last_path(void);
 /* What the last rbx_hll_stream[_dev] call of this process did: out[0] = phases, out[1] = add runs taken by rounds,
  * out[2] = add runs taken grouped, out[3] = grouped chunks. */
 int rbx_bench_hllstream_last(uint32_t out[4]);
+/* What the last rbx_hll_count_groups / rbx_hll_merge_groups call of this process did: out[0] = phases (a merge
+ * call's; 0 for a count call), out[1] = union-count or merge launches, out[2] = the split P of the last of them
+ * (0: none), out[3] = groups that reached the device. */
+int rbx_bench_hllgroups_last(uint32_t out[4]);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -149,6 +153,9 @@ int rbx_bench_hllstream_last(uint32_t out[4]);
  *                           scratch per element, 1.129 GiB); a command with more elements runs by rounds, alone
  *   "hllstream_elems_per_round"  the auto rule's cost of one round in grouped elements (default 1137, from
  *                           10.2 us per round and 8.97 ns per grouped element, DESIGN 11.7 row d)
+ *   "hllgroups_split"       rbx_hll_count_groups / rbx_hll_merge_groups: the workgroups P one group's registers are
+ *                           spread over, 0 auto (default: the smallest power of two with groups * P >= 256, at most
+ *                           16), else P in {1, 2, 4, 8, 16}; every setting gives the same answers
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

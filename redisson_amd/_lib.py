@@ -211,6 +211,8 @@ SIGNATURES = {
                                  u64p, u8p]),
     "rbx_hll_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, u8p, u64p, C.c_uint64,
                                      C.POINTER(RbxKeys), u64p, u8p, vp]),
+    "rbx_hll_count_groups": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u64p, u32p, C.c_uint32, u64p, u8p]),
+    "rbx_hll_merge_groups": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, u64p, u32p, C.c_uint32, u8p]),
     "rbx_hll_merge_n": (C.c_int, [vp, RbxName, C.POINTER(RbxName), C.c_uint32]),
     "rbx_hll_export_enc_n": (C.c_int, [vp, RbxName, C.c_int, u8p, C.c_uint64, u64p]),
     "rbx_hll_import_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64]),
@@ -263,6 +265,7 @@ SIGNATURES = {
     "rbx_bench_bitrange_path": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "rbx_bench_fieldstream_last_path": (C.c_int, []),
     "rbx_bench_hllstream_last": (C.c_int, [u32p]),
+    "rbx_bench_hllgroups_last": (C.c_int, [u32p]),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

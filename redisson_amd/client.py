@@ -915,6 +915,65 @@ def hll_stream_dev(client: RedissonClient, names, cmd_key, cmd_op, seg, d_elemen
     return out, status
 
 
+class _HllGroupArrays:
+    """the CSR arrays of one rbx_hll_count_groups / rbx_hll_merge_groups call: groups = one list of indexes into
+    `names` per group"""
+
+    def __init__(self, names, groups):
+        groups = [list(g) for g in groups]
+        self.n = n = len(groups)
+        self.off = np.zeros(n + 1, np.uint64)
+        self.off[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64)
+        self.key = np.ascontiguousarray([k for g in groups for k in g] or [0], dtype=np.uint32)
+        self.names_arr, self._keep = L.names_array(names)
+        self.nkeys = len(names)
+        self.status = np.zeros(max(n, 1), np.uint8)
+
+
+def hll_count_groups_call(client: RedissonClient, names, groups):
+    """rbx_hll_count_groups without raising: (rc, message, counts, status).  names: str or bytes keys; group g is
+    PFCOUNT of names[k] for k in groups[g] (one entry: the single-key count with the header cache; more: the
+    union).  counts: uint64; status: uint8 with 0 = the group ran, 0xFF = it failed alone."""
+    a = _HllGroupArrays(names, groups)
+    out = np.zeros(max(a.n, 1), np.uint64)
+    rc = L.lib().rbx_hll_count_groups(client.ctx, a.names_arr, a.nkeys, a.off.ctypes.data_as(L.u64p),
+                                      a.key.ctypes.data_as(L.u32p), a.n, out.ctypes.data_as(L.u64p),
+                                      a.status.ctypes.data_as(L.u8p))
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), out[: a.n], a.status[: a.n]
+
+
+def hll_merge_groups_call(client: RedissonClient, names, dests, groups):
+    """rbx_hll_merge_groups without raising: (rc, message, status).  Group g is PFMERGE names[dests[g]] <names[k]
+    for k in groups[g]>, in order: a later group sees what an earlier one wrote."""
+    a = _HllGroupArrays(names, groups)
+    dest = np.ascontiguousarray(list(dests) or [0], dtype=np.uint32).reshape(-1)
+    if len(dests) != a.n:
+        raise IllegalArgumentException("dests and groups have one entry per group")
+    rc = L.lib().rbx_hll_merge_groups(client.ctx, a.names_arr, a.nkeys, dest.ctypes.data_as(L.u32p),
+                                      a.off.ctypes.data_as(L.u64p), a.key.ctypes.data_as(L.u32p), a.n,
+                                      a.status.ctypes.data_as(L.u8p))
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), a.status[: a.n]
+
+
+_engine_hll_count_groups_call, _engine_hll_merge_groups_call = hll_count_groups_call, hll_merge_groups_call
+
+
+def hll_count_groups(client: RedissonClient, names, groups):
+    """Many PFCOUNTs, unions among them, in one call (rbx_hll_count_groups): (counts, status) in order.  Raises the
+    first failing group's exception after every other group has run."""
+    rc, msg, out, status = hll_count_groups_call(client, names, groups)
+    raise_for(rc, msg)
+    return out, status
+
+
+def hll_merge_groups(client: RedissonClient, names, dests, groups):
+    """Many PFMERGEs in one call, in order (rbx_hll_merge_groups): the status bytes.  Raises the first failing
+    group's exception after every other group has run."""
+    rc, msg, status = hll_merge_groups_call(client, names, dests, groups)
+    raise_for(rc, msg)
+    return status
+
+
 class BatchFuture:
     """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
     methods), or raises what the command failed with."""
@@ -942,14 +1001,16 @@ class _Queued:
     """One queued command: a bit command (name, op, index) that coalesces, a field command (name, field =
     (op, signed, size, overflow, offset, value), fn) that coalesces where a field stream call is at hand and
     runs through fn otherwise, an HLL command (name, hll = (PFADD, [element bytes]) or (PFCOUNT, []), fn) that
-    coalesces where an HLL stream call is at hand and runs through fn otherwise, or a callable that runs singly.
+    coalesces where an HLL stream call is at hand and runs through fn otherwise, a grouped HLL command (group =
+    ("count", [names]) for a multi-key PFCOUNT or ("merge", dest, [sources]) for a PFMERGE, fn) that coalesces with
+    its like where the grouped call is at hand and runs through fn otherwise, or a callable that runs singly.
     convert: applied to a field or HLL command's reply."""
 
-    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll")
+    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group")
 
-    def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None):
+    def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None, group=None):
         self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
-        self.field, self.convert, self.hll = field, convert, hll
+        self.field, self.convert, self.hll, self.group = field, convert, hll, group
 
     def as_field(self):
         """the command as a BITFIELD sub-command: GETBIT / SETBIT are GET / SET of a u1, which leave the same
@@ -1035,20 +1096,40 @@ def _settle_hll(c: _Queued, reply, status) -> None:
         c.future._set(c.convert(value) if c.convert else value)
 
 
-def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None):
+def _settle_group(c: _Queued, reply, status) -> None:
+    """a multi-key PFCOUNT (the cardinality) or a PFMERGE (None) of a grouped run"""
+    if int(status) == HLL_FAILED:
+        c.future._set(error=RedisException(_HLL_WRONGTYPE_MSG))
+    else:
+        value = int(reply) if c.group[0] == "count" else None
+        c.future._set(c.convert(value) if c.convert else value)
+
+
+def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, hll_count_groups_call=None,
+              hll_merge_groups_call=None):
     """Executes queued commands in submission order.  Every maximal run of consecutive bit commands, over any
     keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies).  With a
     field_stream_call, field commands join the runs, and a run that holds at least one of them is ONE
     field_stream_call(names, cmd_key, cmds) -> (rc, message, replies, status) in which the bit commands travel as
     u1 GET / SET.  With an hll_stream_call, every maximal run of consecutive PFADD / single-key PFCOUNT commands,
     over any keys, is ONE hll_stream_call(names, cmd_key, cmd_op, seg, elements) -> (rc, message, replies,
-    status); bit and field runs and HLL runs never mix, and each closes the other.  Every other command runs
-    through its own call at its position.  Each command's future is set; returns (responses, first error)."""
+    status); bit and field runs and HLL runs never mix, and each closes the other.  With an hll_count_groups_call,
+    every maximal run of consecutive multi-key PFCOUNTs, over any keys, is ONE hll_count_groups_call(names, groups)
+    -> (rc, message, counts, status); with an hll_merge_groups_call, every maximal run of consecutive PFMERGEs is
+    ONE hll_merge_groups_call(names, dests, groups) -> (rc, message, status).  A count run, a merge run, an HLL
+    stream run and a bit / field run each close the others.  Every other command runs through its own call at
+    its position.  Each command's future is set; returns (responses, first error)."""
     def joins(q):
         return q.op is not None or (q.field is not None and field_stream_call is not None)
 
     def joins_hll(q):
         return q.hll is not None and hll_stream_call is not None
+
+    def joins_counts(q):
+        return q.group is not None and q.group[0] == "count" and hll_count_groups_call is not None
+
+    def joins_merges(q):
+        return q.group is not None and q.group[0] == "merge" and hll_merge_groups_call is not None
 
     def run_from(i, belongs):
         """the maximal run of commands from queue[i] on that belong together"""
@@ -1064,6 +1145,18 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None):
             seg.append(len(elements))
         return hll_stream_call(names, keys, [c.hll[0] for c in run], seg, elements)
 
+    def counts_call(run, _names, _keys):
+        ids: dict = {}
+        groups = [[ids.setdefault(n, len(ids)) for n in c.group[1]] for c in run]
+        return hll_count_groups_call(list(ids), groups)
+
+    def merges_call(run, _names, _keys):
+        ids: dict = {}
+        dests = [ids.setdefault(c.group[1], len(ids)) for c in run]
+        groups = [[ids.setdefault(n, len(ids)) for n in c.group[2]] for c in run]
+        rc, msg, status = hll_merge_groups_call(list(ids), dests, groups)
+        return rc, msg, [None] * len(status), status
+
     def field_call(run, names, keys):
         return field_stream_call(names, keys, [c.as_field() for c in run])
 
@@ -1078,6 +1171,12 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None):
         if joins_hll(queue[i]):
             run = run_from(i, joins_hll)
             error = _run_stream(run, hll_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_hll)
+        elif joins_counts(queue[i]):
+            run = run_from(i, joins_counts)
+            error = _run_stream(run, counts_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_group)
+        elif joins_merges(queue[i]):
+            run = run_from(i, joins_merges)
+            error = _run_stream(run, merges_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_group)
         elif joins(queue[i]):
             run = run_from(i, joins)
             if any(c.field is not None for c in run):
@@ -1249,8 +1348,8 @@ class RBatchBitSet:
 class RBatchHyperLogLog:
     """RBatch.getHyperLogLog(name) (M/RedissonBatch.java:57-64): RHyperLogLogAsync, every method queued.
     addAsync / addAllAsync / countAsync of consecutive commands, over any keys, travel together (one
-    rbx_hll_stream call); countWithAsync with other names and mergeWithAsync run through RHyperLogLog's own call
-    at their position."""
+    rbx_hll_stream call); so do consecutive countWithAsync commands with other names (one rbx_hll_count_groups
+    call) and consecutive mergeWithAsync commands (one rbx_hll_merge_groups call, in order)."""
 
     def __init__(self, batch: "RBatch", name: str, codec: Codec):
         self._batch, self._name, self._codec = batch, name, codec
@@ -1275,10 +1374,14 @@ class RBatchHyperLogLog:
     def countWithAsync(self, *otherLogNames: str) -> BatchFuture:
         if not otherLogNames:
             return self.countAsync()
-        return self._single("countWith", *otherLogNames)
+        hll, name = self._batch._hyperloglog, self._name
+        return self._batch._add(_Queued(name, fn=lambda: hll(name, self._codec).countWith(*otherLogNames),
+                                        group=("count", [name, *otherLogNames])))
 
     def mergeWithAsync(self, *otherLogNames: str) -> BatchFuture:
-        return self._single("mergeWith", *otherLogNames)
+        hll, name = self._batch._hyperloglog, self._name
+        return self._batch._add(_Queued(name, fn=lambda: hll(name, self._codec).mergeWith(*otherLogNames),
+                                        group=("merge", name, list(otherLogNames))))
 
     add_async = addAsync
     add_all_async = addAllAsync
@@ -1290,12 +1393,13 @@ class RBatchHyperLogLog:
 class RBatch:
     """RedissonClient.createBatch() (M/RedissonBatch.java): commands queue across any number of keys, execute()
     runs them in submission order (M/command/CommandBatchService.java:115-134,335) and returns their replies
-    in that order.  stream_call / bitset / field_stream_call / hll_stream_call / hyperloglog replace the engine's
-    calls (tests); without a client and without a field_stream_call (an hll_stream_call), field (HLL) commands
-    run singly through bitset(name) (hyperloglog(name, codec))."""
+    in that order.  stream_call / bitset / field_stream_call / hll_stream_call / hyperloglog /
+    hll_count_groups_call / hll_merge_groups_call replace the engine's calls (tests); without a client and without
+    a field_stream_call (an hll_stream_call, a grouped call), field (HLL, multi-key PFCOUNT / PFMERGE) commands run
+    singly through bitset(name) (hyperloglog(name, codec))."""
 
     def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None, field_stream_call=None,
-                 hll_stream_call=None, hyperloglog=None):
+                 hll_stream_call=None, hyperloglog=None, hll_count_groups_call=None, hll_merge_groups_call=None):
         self._client = client
         self._stream_call = stream_call or (lambda *a: bitset_stream_call(client, *a))
         if field_stream_call is None and client is not None:
@@ -1304,6 +1408,11 @@ class RBatch:
         if hll_stream_call is None and client is not None:
             hll_stream_call = lambda *a: _engine_hll_stream_call(client, *a)  # noqa: E731
         self._hll_stream_call = hll_stream_call
+        if hll_count_groups_call is None and client is not None:
+            hll_count_groups_call = lambda *a: _engine_hll_count_groups_call(client, *a)  # noqa: E731
+        if hll_merge_groups_call is None and client is not None:
+            hll_merge_groups_call = lambda *a: _engine_hll_merge_groups_call(client, *a)  # noqa: E731
+        self._hll_groups_calls = (hll_count_groups_call, hll_merge_groups_call)
         self._hyperloglog = hyperloglog or (lambda name, codec: RHyperLogLog(client, name, codec))
         self._bitset = bitset or (lambda name: RBitSet(client, name))
         self._queue: list = []
@@ -1326,7 +1435,8 @@ class RBatch:
         if self._executed:
             raise IllegalStateException("Batch already executed!")
         self._executed = True
-        responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call, self._hll_stream_call)
+        responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call, self._hll_stream_call,
+                                     *self._hll_groups_calls)
         if error is not None:
             raise error
         return BatchResult(responses)

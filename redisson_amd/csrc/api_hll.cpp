@@ -5,6 +5,7 @@
 #include <unordered_map>
 
 #include "api_staging.h"
+#include "hll_groups_plan.h"
 #include "tunables.h"
 
 namespace rbx {
@@ -794,6 +795,254 @@ int hll_merge(rbx_ctx *c, const std::string &dest, const std::vector<std::string
     return RBX_OK;
 }
 
+// ---- many PFCOUNT unions / PFMERGEs in one call (rbx_hll_count_groups, rbx_hll_merge_groups) ----
+static std::atomic<uint32_t> g_hllgroups_last[4];  // rbx_bench_hllgroups_last shows them
+enum { kHgPhases = 0, kHgLaunches = 1, kHgSplit = 2, kHgDeviceGroups = 3 };
+
+// The keys of one grouped call, each distinct name resolved once (stream_names_resolve has the rules), and the
+// groups that fail alone: those that name a key of another type.
+struct HgKeys {
+    std::vector<std::string> nm;
+    std::vector<uint32_t> canon;
+    std::vector<uint8_t> wrong;                  // per entry of names
+    std::vector<std::shared_ptr<HllState>> hll;  // per canonical id; null = missing
+    HllState *of(uint32_t key) const { return hll[canon[key]].get(); }
+};
+
+static void hg_resolve(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, HgKeys *K) {
+    K->canon.resize(nkeys);
+    K->wrong.assign(nkeys, 0);
+    K->hll.resize(nkeys);
+    stream_names_resolve(c, names, nkeys, KType::Hll, &K->nm, K->canon.data(), K->wrong.data(),
+                         [&](uint32_t i, const Entry &e) { K->hll[i] = e.hll; });
+}
+
+static int hg_split(uint64_t groups) {
+    const int tuned = g_tune.hllgroups_split;
+    int p = tuned ? tuned : hllgroups_auto_split(groups);
+    while (p > 1 && groups * (uint64_t)p >= (1ULL << 31)) p >>= 1;  // the grid
+    return p;
+}
+
+// One launch's table -- offsets (n + 1 u32, padded to 8 bytes) | destinations (a merge's) | member pointers --
+// in one upload.  off.size() == n + 1; dst is empty for a count.
+struct HgTable {
+    const uint32_t *d_off;
+    uint8_t *const *d_dst;
+    const uint8_t *const *d_members;
+};
+static int hg_upload(rbx_ctx *c, const std::vector<uint32_t> &off, const std::vector<uint8_t *> &dst,
+                     const std::vector<const uint8_t *> &members, hipStream_t st, HgTable *t) {
+    const size_t off_bytes = (off.size() * 4 + 7) & ~(size_t)7;
+    const size_t bytes = off_bytes + (dst.size() + members.size()) * sizeof(void *);
+    std::vector<uint8_t> blob(bytes);
+    memcpy(blob.data(), off.data(), off.size() * 4);
+    if (!dst.empty()) memcpy(blob.data() + off_bytes, dst.data(), dst.size() * sizeof(void *));
+    if (!members.empty())
+        memcpy(blob.data() + off_bytes + dst.size() * sizeof(void *), members.data(), members.size() * sizeof(void *));
+    DevBuf &tab = c->dev->hll.grp.table;
+    RBX_TRY(tab.reserve(bytes));
+    HIP_TRY(hipMemcpyAsync(tab.p, blob.data(), bytes, hipMemcpyHostToDevice, st));
+    uint8_t *p = tab.as<uint8_t>();
+    t->d_off = (const uint32_t *)p;
+    t->d_dst = (uint8_t *const *)(p + off_bytes);
+    t->d_members = (const uint8_t *const *)(p + off_bytes + dst.size() * sizeof(void *));
+    return RBX_OK;
+}
+
+static int hll_count_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint64_t *grp_off,
+                            const uint32_t *grp_key, uint32_t ngroups, uint64_t *out, uint8_t *status) {
+    RBX_ENTER(c, c->stream);
+    hipStream_t st = c->stream;
+    HgKeys K;
+    hg_resolve(c, names, nkeys, &K);
+    uint32_t stats[4] = {0, 0, 0, 0};
+    // the groups that reach the device: unions of existing keys, and one-key counts whose cache is invalid
+    std::vector<uint32_t> off{0}, at;
+    std::vector<const uint8_t *> members;
+    std::vector<HllState *> store;  // per device group: the key whose header takes the recount, or null
+    bool any_failed = false;
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        const uint64_t a = grp_off[g], b = grp_off[g + 1];
+        bool failed = false;
+        for (uint64_t i = a; i < b && !failed; ++i) failed = K.wrong[grp_key[i]] != 0;
+        out[g] = 0;
+        if (status) status[g] = failed ? 0xFF : 0;
+        if (failed) {
+            any_failed = true;
+            continue;
+        }
+        HllState *single = nullptr;
+        if (b - a == 1) {  // PFCOUNT key: the header cache
+            single = K.of(grp_key[a]);
+            if (!single) continue;
+            if (!(single->card >> 63)) {
+                out[g] = single->card;
+                continue;
+            }
+            members.push_back(single->d_regs);
+        } else {
+            for (uint64_t i = a; i < b; ++i)
+                if (HllState *h = K.of(grp_key[i])) members.push_back(h->d_regs);
+            if (members.size() == off.back()) continue;  // every key is missing: 0
+        }
+        off.push_back((uint32_t)members.size());
+        at.push_back(g);
+        store.push_back(single);
+    }
+    const uint32_t n = (uint32_t)at.size();
+    if (n) {
+        HllGroupsScratch &gs = c->dev->hll.grp;
+        HgTable t;
+        RBX_TRY(hg_upload(c, off, {}, members, st, &t));
+        RBX_TRY(gs.histo.reserve((size_t)n * 64 * sizeof(int)));
+        RBX_TRY(gs.out.reserve((size_t)n * 8));
+        const int split = hg_split(n);
+        const int e = launch_hllgroups_union_count(t.d_members, t.d_off, n, split, gs.histo.as<int>(),
+                                                   gs.out.as<unsigned long long>(), st);
+        if (e) return fail(RBX_E_DEVICE, hipGetErrorString((hipError_t)e));
+        HIP_TRY(hipGetLastError());
+        stats[kHgLaunches] = 1;
+        stats[kHgSplit] = (uint32_t)split;
+        stats[kHgDeviceGroups] = n;
+        std::vector<unsigned long long> res(n);
+        HIP_TRY(hipMemcpyAsync(res.data(), gs.out.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<int> h;
+        for (uint32_t j = 0; j < n; ++j) {
+            if (res[j] == ~0ULL) {  // tau branch: histogram to host, glibc pow (count_regs)
+                if (h.empty()) {
+                    h.resize((size_t)n * 64);
+                    HIP_TRY(hipMemcpy(h.data(), gs.histo.p, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+                }
+                res[j] = hll_count_from_histo(&h[(size_t)j * 64]);
+            }
+            out[at[j]] = res[j];
+            if (store[j]) store[j]->card = res[j];  // the (valid) cached cardinality; a union stores nothing
+        }
+    }
+    for (int i = 0; i < 4; ++i) g_hllgroups_last[i] = stats[i];
+    if (any_failed) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+    return RBX_OK;
+}
+
+// One phase of a merge call, the groups [p0, p1) that do not fail: no destination is another group's source or
+// destination (hll_groups_plan), so one launch runs them all.
+static int hg_merge_phase(rbx_ctx *c, HgKeys &K, const uint32_t *grp_dest, const uint64_t *grp_off,
+                          const uint32_t *grp_key, const uint8_t *failed, uint32_t p0, uint32_t p1, hipStream_t st,
+                          uint32_t *stats) {
+    HllGroupsScratch &gs = c->dev->hll.grp;
+    stats[kHgPhases]++;
+    std::vector<uint32_t> groups;
+    for (uint32_t g = p0; g < p1; ++g)
+        if (!failed[g]) groups.push_back(g);
+    // the missing destinations (createHLLObject: sparse, one XZERO)
+    for (uint32_t g : groups) {
+        const uint32_t k = K.canon[grp_dest[g]];
+        if (!K.hll[k]) RBX_TRY(hll_get(c, K.nm[k], true, st, &K.hll[k], nullptr));
+    }
+    // the promotion words of the phase's keys that the host does not know to be dense, in one copy
+    std::vector<HllState *> sparse;
+    std::vector<uint32_t *> states;
+    std::unordered_map<HllState *, int> seen;
+    auto note = [&](HllState *h) {
+        if (h && !h->dense && seen.emplace(h, 1).second) {
+            sparse.push_back(h);
+            states.push_back(h->d_promoted);
+        }
+    };
+    std::vector<uint32_t> off{0};
+    std::vector<uint8_t *> dst;
+    std::vector<const uint8_t *> members;
+    std::vector<uint32_t> launched;  // the groups with an existing source
+    for (uint32_t g : groups) {
+        HllState *d = K.of(grp_dest[g]);
+        note(d);
+        const size_t before = members.size();
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i)
+            if (HllState *h = K.of(grp_key[i])) {
+                note(h);
+                members.push_back(h->d_regs);
+            }
+        if (members.size() == before) continue;  // nothing to merge in: the destination stands as it is
+        dst.push_back(d->d_regs);
+        off.push_back((uint32_t)members.size());
+        launched.push_back(g);
+    }
+    std::vector<uint32_t> promoted(states.size());
+    if (!states.empty()) {
+        RBX_TRY(gs.ptrs.reserve(states.size() * sizeof(uint32_t *)));
+        RBX_TRY(gs.out.reserve(states.size() * 4));
+        HIP_TRY(hipMemcpyAsync(gs.ptrs.p, states.data(), states.size() * sizeof(uint32_t *), hipMemcpyHostToDevice, st));
+        launch_hllstream_promoted(gs.ptrs.as<uint32_t *>(), (uint32_t)states.size(), gs.out.as<uint32_t>(), st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(promoted.data(), gs.out.p, states.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (!launched.empty()) {
+        HgTable t;
+        RBX_TRY(hg_upload(c, off, dst, members, st, &t));
+        const int split = hg_split(launched.size());
+        launch_hllgroups_merge(t.d_dst, t.d_members, t.d_off, (uint32_t)launched.size(), split, st);
+        HIP_TRY(hipGetLastError());
+        stats[kHgLaunches]++;
+        stats[kHgSplit] = (uint32_t)split;
+        stats[kHgDeviceGroups] += (uint32_t)launched.size();
+    }
+    if (!states.empty()) {
+        HIP_TRY(hipStreamSynchronize(st));  // the phase's one wait
+        for (size_t j = 0; j < sparse.size(); ++j)
+            if (promoted[j]) sparse[j]->dense = true;
+    }
+    // pfmergeCommand: use_dense if the destination or any existing source is; else the string takes the maxima
+    std::vector<HllState *> back;
+    for (uint32_t g : groups) {
+        HllState *d = K.of(grp_dest[g]);
+        bool had_source = false;
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i)
+            if (HllState *h = K.of(grp_key[i])) {
+                had_source = true;
+                d->dense = d->dense || h->dense;
+            }
+        if (had_source && !d->dense) back.push_back(d);
+        d->card |= 1ULL << 63;  // HLL_INVALIDATE_CACHE: always, also without sources
+    }
+    return replay_merge(c, back, st);
+}
+
+static int hll_merge_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *grp_dest,
+                            const uint64_t *grp_off, const uint32_t *grp_key, uint32_t ngroups, uint8_t *status) {
+    RBX_ENTER(c, c->stream);
+    hipStream_t st = c->stream;
+    HgKeys K;
+    hg_resolve(c, names, nkeys, &K);
+    uint32_t stats[4] = {0, 0, 0, 0};
+    std::vector<uint8_t> failed(ngroups, 0);
+    std::vector<uint32_t> cdest(ngroups), csrc(grp_off[ngroups]);
+    bool any_failed = false;
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        bool f = K.wrong[grp_dest[g]] != 0;
+        cdest[g] = K.canon[grp_dest[g]];
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) {
+            f = f || K.wrong[grp_key[i]] != 0;
+            csrc[i] = K.canon[grp_key[i]];
+        }
+        failed[g] = f;
+        any_failed = any_failed || f;
+        if (status) status[g] = f ? 0xFF : 0;
+    }
+    std::vector<uint32_t> end;
+    hll_groups_plan(cdest.data(), grp_off, csrc.data(), failed.data(), ngroups, nkeys, &end);
+    uint32_t p0 = 0;
+    for (uint32_t p1 : end) {
+        RBX_TRY(hg_merge_phase(c, K, grp_dest, grp_off, grp_key, failed.data(), p0, p1, st, stats));
+        p0 = p1;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < 4; ++i) g_hllgroups_last[i] = stats[i];
+    if (any_failed) return fail(RBX_E_WRONGTYPE, kHllWrongType);
+    return RBX_OK;
+}
+
 // Redis HLL strings: 16-byte header ("HYLL", encoding, 3 unused, 8 cached-cardinality bytes)
 // + dense registers (HLL_DENSE_SET_REGISTER layout, 6 bits each, LSB-first) or sparse opcodes.
 constexpr uint64_t kHllDenseLen = 16 + 12288;
@@ -1214,6 +1463,38 @@ int rbx_hll_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const 
 int rbx_bench_hllstream_last(uint32_t out[4]) {
     if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
     for (int i = 0; i < 4; ++i) out[i] = g_hllstream_last[i];
+    return RBX_OK;
+}
+
+static int hll_groups_args(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint64_t *grp_off,
+                           const uint32_t *grp_key, uint32_t ngroups, bool need_entries) {
+    RBX_TRY(stream_names_check(c, names, nkeys));
+    if (const char *what = hll_groups_check(grp_off, grp_key, ngroups, nkeys, need_entries))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, what);
+    return RBX_OK;
+}
+
+int rbx_hll_count_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint64_t *grp_off,
+                         const uint32_t *grp_key, uint32_t ngroups, uint64_t *out, uint8_t *status) {
+    RBX_TRY(hll_groups_args(c, names, nkeys, grp_off, grp_key, ngroups, true));
+    if (ngroups == 0) return RBX_OK;  // no command is sent
+    if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return hll_count_groups(c, names, nkeys, grp_off, grp_key, ngroups, out, status);
+}
+
+int rbx_hll_merge_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *grp_dest,
+                         const uint64_t *grp_off, const uint32_t *grp_key, uint32_t ngroups, uint8_t *status) {
+    RBX_TRY(hll_groups_args(c, names, nkeys, grp_off, grp_key, ngroups, false));
+    if (ngroups == 0) return RBX_OK;
+    if (!grp_dest) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (uint32_t g = 0; g < ngroups; ++g)
+        if (grp_dest[g] >= nkeys) return fail(RBX_E_ILLEGAL_ARGUMENT, "a group's destination is not below nkeys");
+    return hll_merge_groups(c, names, nkeys, grp_dest, grp_off, grp_key, ngroups, status);
+}
+
+int rbx_bench_hllgroups_last(uint32_t out[4]) {
+    if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (int i = 0; i < 4; ++i) out[i] = g_hllgroups_last[i];
     return RBX_OK;
 }
 

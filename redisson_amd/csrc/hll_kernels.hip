@@ -11,6 +11,7 @@
 // ds_max_u32, then merges into HBM with a bytewise-max CAS per 4-register word; the
 // command's reply ("any register changed") is the OR over its tiles.
 // M/ = /root/reference/redisson/src/main/java/org/redisson/
+#include "hll_device.h"
 #include "rbx_kernels.h"
 
 namespace rbx {
@@ -90,20 +91,6 @@ void launch_hll_pfadd(const KeysDev &elems, int elen_fast, const HllSeg *d_tiles
 // ---------------------------------------------------------------------------------
 // PFCOUNT: register histogram + estimator (hllCount), one 256-thread block per HLL.
 // ---------------------------------------------------------------------------------
-__device__ double hll_sigma(double x) {
-    if (x == 1.) return __builtin_inf();
-    double zPrime;
-    double y = 1;
-    double z = x;
-    do {
-        x *= x;
-        zPrime = z;
-        z += x * y;
-        y += y;
-    } while (zPrime != z);
-    return z;
-}
-
 __global__ __launch_bounds__(256) void k_hll_count(uint8_t *const *__restrict__ regs, int *__restrict__ histo,
                                                    unsigned long long *__restrict__ out) {
     __shared__ int h[4][64];
@@ -128,22 +115,7 @@ __global__ __launch_bounds__(256) void k_hll_count(uint8_t *const *__restrict__ 
         histo[(size_t)blockIdx.x * 64 + t] = s;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int *rh = h[0];
-        if (rh[51] != 0) {  // hllTau path: host evaluates it with glibc pow (redis semantics)
-            out[blockIdx.x] = ~0ULL;
-            return;
-        }
-        const double m = kHllRegs;
-        double z = 0.0;  // m * hllTau(1.0) == 0
-        for (int j = 50; j >= 1; --j) {
-            z += rh[j];
-            z *= 0.5;
-        }
-        z += m * hll_sigma(rh[0] / (double)m);
-        const double E = (double)llround(0.721347520444481703680 * m * m / z);
-        out[blockIdx.x] = (unsigned long long)E;
-    }
+    if (threadIdx.x == 0) out[blockIdx.x] = hll_estimate(h[0]);  // ~0: the hllTau path, the host evaluates it
 }
 
 void launch_hll_count(uint8_t *const *d_regs, uint32_t n, int *d_histo, unsigned long long *d_out,

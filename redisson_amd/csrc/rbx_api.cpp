@@ -334,6 +334,7 @@ static const TuneRow kTuneRows[] = {
     {"hllstream_path", RANGE(0, 2), false, FIELD(hllstream_path)},
     {"hllstream_chunk", RANGE(1, 1 << 30), false, FIELD(hllstream_chunk)},  // positions in a chunk are 32-bit
     {"hllstream_elems_per_round", RANGE(1, kIntMax), false, FIELD(hllstream_elems_per_round)},
+    {"hllgroups_split", ONE_OF(0, 1, 2, 4, 8, 16), false, FIELD(hllgroups_split)},
 };
 #undef RANGE
 #undef ONE_OF

@@ -347,6 +347,15 @@ struct HllStreamScratch {
     CachedTable<rbx::HllKey> keys;  // the key table
 };
 
+// Grouped PFCOUNT unions and PFMERGEs (rbx_hll_count_groups / rbx_hll_merge_groups): one call at a
+// time holds these.
+struct HllGroupsScratch {
+    DevBuf table;  // one launch's offsets | destinations | member pointers, uploaded in one copy
+    DevBuf histo;  // 64 bins per group
+    DevBuf out;    // one count per group; a merge phase's promotion words
+    DevBuf ptrs;   // the state words of a merge phase's keys, for the promotion readback
+};
+
 // HLL register pool (chunks of kHllPerChunk x 16 KiB) and PFADD's uploaded tables.
 struct HllPool {
     struct Slot {
@@ -362,6 +371,7 @@ struct HllPool {
     CachedTable<rbx::HllReplay> replay;  // k_hll_sparse_replay items
     DevBuf pack;                         // contiguous registers for the RCCL merge
     HllStreamScratch strm;
+    HllGroupsScratch grp;
     void free_chunks() {
         for (auto *p : chunks) (void)hipFree(p);
         chunks.clear();

@@ -631,4 +631,18 @@ int launch_hllstream_grouped(const KeysDev &elems, int elen_fast, uint64_t first
 // d_out[i] = d_states[i][0], the sticky promotion word (HllReplay::state) of each sparse HLL of a run
 void launch_hllstream_promoted(uint32_t *const *d_states, uint32_t n, uint32_t *d_out, hipStream_t st);
 
+// ---- hllgroups_kernels.hip
+// Many PFCOUNT unions / PFMERGEs in one launch (rbx_hll_count_groups, rbx_hll_merge_groups).  Group g
+// is the register blocks d_members[d_off[g] .. d_off[g + 1]) (16384 bytes each; a group may be empty); `split` = the
+// workgroups a group's registers are spread over, a power of two in 1 .. kHllGroupsMaxSplit, ngroups * split < 2^31.
+constexpr int kHllGroupsMaxSplit = 16;
+// d_out[g] = the cardinality of group g's union, or ~0 when it holds a register of 51 (launch_hll_count's rule);
+// d_histo: ngroups * 64 ints, the unions' histograms.  Returns 0 or a hipError_t.
+int launch_hllgroups_union_count(const uint8_t *const *d_members, const uint32_t *d_off, uint32_t ngroups, int split,
+                                 int *d_histo, unsigned long long *d_out, hipStream_t st);
+// d_dst[g] = max(d_dst[g], group g's members).  No d_dst[g] may be a member of another group or another group's
+// destination; it may be a member of its own group.
+void launch_hllgroups_merge(uint8_t *const *d_dst, const uint8_t *const *d_members, const uint32_t *d_off,
+                            uint32_t ngroups, int split, hipStream_t st);
+
 }  // namespace rbx

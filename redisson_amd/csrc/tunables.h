@@ -125,7 +125,25 @@ struct Tunables {
     // one-element PFADDs over 4,096 keys (DESIGN 11.7 row d): 10.2 us per round by rounds against 8.97 ns per
     // element grouped, call times with the host's share in both: 1137 elements per round.
     std::atomic<uint64_t> hllstream_elems_per_round{1137};
+
+    // ---- grouped PFCOUNT unions and PFMERGEs (api_hll.cpp) ----
+    // "hllgroups_split": the workgroups P one group's 16,384 registers are spread over: 0 (default) = auto, else
+    // P, a power of two up to 16.  All exact.  Auto (hllgroups_auto_split) takes the smallest P with groups * P >=
+    // kHllGroupsFillBlocks, capped at 16: a handful of groups still fills the device, and from kHllGroupsFillBlocks
+    // groups on each runs in one workgroup, which finishes with the estimator in place (P > 1 costs a fill of the
+    // histograms and the finish launch).  kHllGroupsFillBlocks is 256, one workgroup per CU.  Measured on unions of
+    // 24 members (DESIGN 11.8 row c): at 1 and 16 groups P = 16 is fastest (0.043 / 0.044 ms against 0.051 / 0.054 ms
+    // at P = 1); at 256, 4,096 and 10,000 groups all six settings lie within 4 % (0.088 - 0.092, 0.754 - 0.757 and
+    // 1.777 - 1.795 ms), so from 256 on P = 1 is taken.
+    std::atomic<int> hllgroups_split{0};
 };
+
+constexpr uint32_t kHllGroupsFillBlocks = 256;
+inline int hllgroups_auto_split(uint64_t groups) {
+    int p = 1;
+    while (p < 16 && groups * (uint64_t)p < kHllGroupsFillBlocks) p <<= 1;
+    return p;
+}
 
 extern Tunables g_tune;
 

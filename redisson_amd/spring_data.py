@@ -24,7 +24,8 @@ import numpy as np
 
 from . import _lib as L
 from .client import (GETBIT, PFADD, PFCOUNT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued,
-                     bitset_field_stream_call, bitset_stream_call, hll_stream_call, run_queue)
+                     bitset_field_stream_call, bitset_stream_call, hll_count_groups_call, hll_merge_groups_call,
+                     hll_stream_call, run_queue)
 from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
 
@@ -135,20 +136,34 @@ def _pf_add(key, *values):
 
 
 def _pf_count(*keys):
-    """(key, (PFCOUNT, []), None) of a pipelined single-key pfCount; None for any other (it runs singly, and
-    raises there what it has to raise)"""
+    """(key, (PFCOUNT, []), None) of a pipelined single-key pfCount; None for any other (a pfCount of several keys
+    is _pf_count_group's; what is left runs singly, and raises there what it has to raise)"""
     if len(keys) != 1 or keys[0] is None:
         return None
     return keys[0], (PFCOUNT, []), None
 
 
-def _pipelined(fn=None, *, bit=None, field=None, hll=None):
+def _pf_count_group(*keys):
+    """("count", keys) of a pipelined pfCount with two or more keys; None for any other"""
+    if len(keys) < 2 or any(k is None for k in keys):
+        return None
+    return ("count", [_key(k) for k in keys])
+
+
+def _pf_merge_group(destinationKey, *sourceKeys):
+    """("merge", destination, sources) of a pipelined pfMerge"""
+    return ("merge", _key(destinationKey), [_key(k) for k in sourceKeys])
+
+
+def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None):
     """A command method of RedissonConnection: while a pipeline is open it queues itself and returns None
     (the result comes back from closePipeline); bit = (key, op, index) of a GETBIT / SETBIT, which travels with
     its neighbours in one rbx_bitset_stream call; field = (key, row, convert) of a BITFIELD with one sub-command
     (or None for any other), which travels with its bit and field neighbours in one rbx_bitset_field_stream call;
     hll = (key, (op, elements), convert) of a PFADD / single-key PFCOUNT (or None for any other), which travels
-    with its HLL neighbours in one rbx_hll_stream call."""
+    with its HLL neighbours in one rbx_hll_stream call; group = ("count", keys) of a multi-key PFCOUNT or ("merge",
+    destination, sources) of a PFMERGE (or None for any other), which travels with its like in one
+    rbx_hll_count_groups / rbx_hll_merge_groups call."""
 
     def wrap(f):
         @functools.wraps(f)
@@ -160,6 +175,14 @@ def _pipelined(fn=None, *, bit=None, field=None, hll=None):
                 self._pipeline.append(_Queued(_key(key), op, _bit_index(index)))
                 return None
             single = lambda: f(self, *args, **kwargs)  # noqa: E731
+            if group is not None:
+                try:
+                    row = group(*args, **kwargs)
+                except (IllegalArgumentException, TypeError):
+                    row = None  # the single call raises it at its position
+                if row is not None:
+                    self._pipeline.append(_Queued(row[1] if row[0] == "merge" else row[1][0], fn=single, group=row))
+                    return None
             if hll is not None:
                 try:
                     row = hll(*args, **kwargs)
@@ -204,14 +227,17 @@ class RedissonConnection:
         """:146-163 -- runs the queued commands in order and returns their results; [] outside a pipeline.
         Consecutive getBit / setBit commands, over any keys, are one rbx_bitset_stream call; with a bitField of
         exactly one sub-command among them they are one rbx_bitset_field_stream call.  Consecutive pfAdd and
-        single-key pfCount commands, over any keys, are one rbx_hll_stream call (a multi-key pfCount and pfMerge
-        run singly).  Every command runs; then the first failure is raised."""
+        single-key pfCount commands, over any keys, are one rbx_hll_stream call; consecutive pfCount commands of
+        two or more keys are one rbx_hll_count_groups call, consecutive pfMerge commands one rbx_hll_merge_groups
+        call.  Every command runs; then the first failure is raised."""
         if self._pipeline is None:
             return []
         queue, self._pipeline = self._pipeline, None
         results, error = run_queue(queue, lambda *a: bitset_stream_call(self._client, *a),
                                    lambda *a: bitset_field_stream_call(self._client, *a),
-                                   lambda *a: hll_stream_call(self._client, *a))
+                                   lambda *a: hll_stream_call(self._client, *a),
+                                   lambda *a: hll_count_groups_call(self._client, *a),
+                                   lambda *a: hll_merge_groups_call(self._client, *a))
         if error is not None:
             raise error
         return results
@@ -231,7 +257,7 @@ class RedissonConnection:
                                            ch.ctypes.data_as(L.u8p)))
         return int(ch[0])
 
-    @_pipelined(hll=_pf_count)
+    @_pipelined(hll=_pf_count, group=_pf_count_group)
     def pfCount(self, *keys: bytes) -> int:
         """PFCOUNT k1..kn (union when n > 1)."""
         if not keys:
@@ -243,7 +269,7 @@ class RedissonConnection:
         _check(L.lib().rbx_hll_count_n(self._client.ctx, names, len(keys), C.byref(out)))
         return int(out.value)
 
-    @_pipelined
+    @_pipelined(group=_pf_merge_group)
     def pfMerge(self, destinationKey: bytes, *sourceKeys: bytes) -> None:
         """PFMERGE dest s1..sn (dest's own registers included)."""
         srcs, keep = L.names_array([_key(k) for k in sourceKeys])
