@@ -472,6 +472,55 @@ int rbx_bitset_count_of(const uint8_t *bytes, uint64_t len, int missing, int64_t
                         uint64_t *out);
 int rbx_bitset_pos_of(const uint8_t *bytes, uint64_t len, int missing, int bit, int nargs, int64_t start, int64_t end,
                       int unit, int64_t *out);
+/* Many BITOPs, and many BITCOUNTs of a combination, in one ordered call: what RBitSet.and / or / xor / not and
+ * cardinality send one command at a time (M/RedissonBitSet.java:362-388, :462-464, :482-484), what a batch queues
+ * through RBatch.getBitSet(name).andAsync / orAsync / xorAsync / notAsync / cardinalityAsync
+ * (M/RedissonBatch.java:182-184), and Spring Data's bitOp (S:650-661) / bitCount(key) (S:638-641) between
+ * openPipeline() and closePipeline(): the combinations bitmaps are kept for (users active on day i AND day j for
+ * every pair of days, 24 hourly bitmaps ORed into each daily one, BITCOUNT of each of 10,000 feature bitmaps).
+ *   Commands  group g is BITOP grp_op[g] names[grp_dest[g]] <names[grp_key[grp_off[g] .. grp_off[g + 1])]>
+ *             (grp_off has ngroups + 1 entries and ascends from 0; at least one source).  With grp_dest[g] =
+ *             RBX_BITGROUP_NO_DEST the combination is computed and counted but stored nowhere: a one-source OR
+ *             is BITCOUNT of that key, a two-source AND the size of an intersection with no temporary key.  Two
+ *             entries of `names` with equal bytes are one key.
+ *   Result    exactly that of ngroups single calls in array order.  lens[g] is what rbx_bitset_op puts in
+ *             *result_len, the longest source's length; counts[g] is the number of one bits of the result -- for
+ *             a group with a destination what rbx_bitset_cardinality(dest) answers right after it.  lens, counts
+ *             and status are nullable.  Everything rbx_bitset_op does to dest holds per group: it is created if
+ *             missing, overwritten over max(result, previous length) with the bytes past its length left zero,
+ *             deleted by a result of length 0, loses its timeout otherwise, and never shrinks below the |size|
+ *             of an existing {name}:config.  dest may be among its own sources.  Later groups see earlier ones:
+ *             a destination may be a later group's source or its destination again.  Groups without a
+ *             destination change nothing.
+ *   Failures  the pipelined-batch rule of RBX_E_REDIS above: a group that names a key of another type (an HLL, a
+ *             {name}:config hash) as destination or source fails alone, and so does RBX_BITOP_NOT with other
+ *             than one source.  status[g] is 0xFF, lens[g] = counts[g] = 0, and it changes and creates nothing.
+ *             Every other group runs (status 0) with its exact result.  The call returns the code of the first
+ *             failing group in array order with its message in rbx_last_error(): RBX_E_REDIS with rbx_bitset_op's
+ *             BITOP NOT message (checked first, as there), else RBX_E_WRONGTYPE.
+ *   Caller    an op above RBX_BITOP_NOT, a group without a source, an entry >= nkeys, a destination >= nkeys
+ *             other than RBX_BITGROUP_NO_DEST, offsets that do not ascend from 0, or a NULL grp_op / grp_dest /
+ *             grp_off / grp_key with ngroups > 0 is RBX_E_ILLEGAL_ARGUMENT with nothing changed and nothing
+ *             created.  ngroups = 0 sends nothing.  A call takes fewer than 2^31 groups and 2^32 entries.
+ *   Cost      each distinct name is looked up once; the length words of all existing keys come back through one
+ *             gather launch, one copy and one wait.  From there the host carries every length through the
+ *             groups itself and splits them into phases -- a group closes the phase before it when its
+ *             destination is a destination or a source of an earlier group of the phase, or one of its sources
+ *             is such a destination -- and runs each phase as one table upload and one launch, a segmented sweep
+ *             in tiles of rbx_tune "bitgroups_tile" bytes.  The counts come back in one copy behind the call's
+ *             second and last wait.  Growing an EXISTING destination past its allocation costs one more wait
+ *             each (the old bytes are copied over before the block is freed).  A BITCOUNT of a key that an
+ *             earlier group of the same phase wrote is answered from that group's count and reaches no device:
+ *             `BITOP AND t_i a b; BITCOUNT t_i` over distinct t_i is one phase, over one t a phase per pair.
+ *             Failed groups, and groups whose sources are all missing or empty, are answered on the host
+ *             (DESIGN 11.9).
+ *   Scope     no handle form, no _dev form; the node router and the Java shim do not carry this call.  Ranged
+ *             BITCOUNT stays rbx_bitset_count_ranges'.
+ * All arrays are host memory: the host must know the keys to create the destinations. */
+#define RBX_BITGROUP_NO_DEST 0xFFFFFFFFu
+int rbx_bitset_op_groups(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint8_t *grp_op,
+                         const uint32_t *grp_dest, const uint64_t *grp_off, const uint32_t *grp_key, uint32_t ngroups,
+                         uint64_t *lens, uint64_t *counts, uint8_t *status);
 
 /* ---- replicas ("replicate the bitmap, split contains keys across GPUs") ---------
  * Redisson serves contains' GETBITs as reads that may go to a replica

@@ -57,6 +57,9 @@ int rbx_bench_hllstream_last(uint32_t out[4]);
  * call's; 0 for a count call), out[1] = union-count or merge launches, out[2] = the split P of the last of them
  * (0: none), out[3] = groups that reached the device. */
 int rbx_bench_hllgroups_last(uint32_t out[4]);
+/* What the last rbx_bitset_op_groups call of this process did: out[0] = phases, out[1] = sweep launches, out[2] = the
+ * tile bytes of the last of them (0: none), out[3] = groups that reached the device. */
+int rbx_bench_bitgroups_last(uint32_t out[4]);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -156,6 +159,9 @@ int rbx_bench_hllgroups_last(uint32_t out[4]);
  *   "hllgroups_split"       rbx_hll_count_groups / rbx_hll_merge_groups: the workgroups P one group's registers are
  *                           spread over, 0 auto (default: the smallest power of two with groups * P >= 256, at most
  *                           16), else P in {1, 2, 4, 8, 16}; every setting gives the same answers
+ *   "bitgroups_tile"        rbx_bitset_op_groups: the bytes of a tile of the segmented sweep, 0 auto (default: the
+ *                           largest power of two in 4 KiB .. 64 KiB that still gives a launch 2048 tiles), else a
+ *                           power of two in 4 KiB .. 1 MiB; every setting gives the same answers
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

@@ -72,6 +72,7 @@ RBX_E_REDIS = -9
 RBX_E_TIMEOUT = -10
 
 RBX_BITOP_AND, RBX_BITOP_OR, RBX_BITOP_XOR, RBX_BITOP_NOT = 0, 1, 2, 3
+RBX_BITGROUP_NO_DEST = 0xFFFFFFFF  # rbx_bitset_op_groups: the group stores its result nowhere
 RBX_FIELD_GET, RBX_FIELD_SET, RBX_FIELD_INCRBY = 0, 1, 2
 RBX_RANGE_BYTE, RBX_RANGE_BIT = 0, 1
 RBX_OVERFLOW_WRAP, RBX_OVERFLOW_SAT, RBX_OVERFLOW_FAIL = 0, 1, 2
@@ -230,6 +231,8 @@ SIGNATURES = {
     "rbx_bitset_stream": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, u8p, u64p, C.c_uint64, u8p]),
     "rbx_bitset_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp]),
     "rbx_bitset_op": (C.c_int, [vp, C.c_int, RbxName, C.POINTER(RbxName), C.c_uint32, u64p]),
+    "rbx_bitset_op_groups": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u8p, u32p, u64p, u32p, C.c_uint32, u64p,
+                                       u64p, u8p]),
     "rbx_bitset_cardinality": (C.c_int, [vp, RbxName, u64p]),
     "rbx_bitset_size": (C.c_int, [vp, RbxName, u64p]),
     "rbx_bitset_length": (C.c_int, [vp, RbxName, C.POINTER(C.c_int64)]),
@@ -266,6 +269,7 @@ SIGNATURES = {
     "rbx_bench_fieldstream_last_path": (C.c_int, []),
     "rbx_bench_hllstream_last": (C.c_int, [u32p]),
     "rbx_bench_hllgroups_last": (C.c_int, [u32p]),
+    "rbx_bench_bitgroups_last": (C.c_int, [u32p]),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

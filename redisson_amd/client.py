@@ -974,6 +974,29 @@ def hll_merge_groups(client: RedissonClient, names, dests, groups):
     return status
 
 
+def bitset_op_groups_call(client: RedissonClient, names, ops, dests, groups):
+    """rbx_bitset_op_groups without raising: (rc, message, lens, counts, status).  Group g is BITOP ops[g]
+    names[dests[g]] <names[k] for k in groups[g]>, in order: a later group sees what an earlier one wrote.  ops:
+    RBX_BITOP_* values; dests[g] = None (or RBX_BITGROUP_NO_DEST): the combination is counted and stored nowhere.
+    lens: uint64, each result's length; counts: uint64, its one bits; status: uint8 with 0 = the group ran, 0xFF =
+    it failed alone."""
+    a = _HllGroupArrays(names, groups)
+    if len(ops) != a.n or len(dests) != a.n:
+        raise IllegalArgumentException("ops, dests and groups have one entry per group")
+    op = np.ascontiguousarray(list(ops) or [0], dtype=np.uint8).reshape(-1)
+    dest = np.ascontiguousarray([L.RBX_BITGROUP_NO_DEST if d is None else d for d in dests] or [0],
+                                dtype=np.uint32).reshape(-1)
+    lens, counts = np.zeros(max(a.n, 1), np.uint64), np.zeros(max(a.n, 1), np.uint64)
+    rc = L.lib().rbx_bitset_op_groups(client.ctx, a.names_arr, a.nkeys, op.ctypes.data_as(L.u8p),
+                                      dest.ctypes.data_as(L.u32p), a.off.ctypes.data_as(L.u64p),
+                                      a.key.ctypes.data_as(L.u32p), a.n, lens.ctypes.data_as(L.u64p),
+                                      counts.ctypes.data_as(L.u64p), a.status.ctypes.data_as(L.u8p))
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), lens[: a.n], counts[: a.n], a.status[: a.n]
+
+
+_engine_bitset_op_groups_call = bitset_op_groups_call
+
+
 class BatchFuture:
     """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
     methods), or raises what the command failed with."""
@@ -1003,14 +1026,17 @@ class _Queued:
     runs through fn otherwise, an HLL command (name, hll = (PFADD, [element bytes]) or (PFCOUNT, []), fn) that
     coalesces where an HLL stream call is at hand and runs through fn otherwise, a grouped HLL command (group =
     ("count", [names]) for a multi-key PFCOUNT or ("merge", dest, [sources]) for a PFMERGE, fn) that coalesces with
-    its like where the grouped call is at hand and runs through fn otherwise, or a callable that runs singly.
-    convert: applied to a field or HLL command's reply."""
+    its like where the grouped call is at hand and runs through fn otherwise, a BITOP or whole-string BITCOUNT
+    (bitop = (RBX_BITOP_*, destination or None, [sources]), fn; convert(length, count) is its reply) that coalesces
+    with its like where the grouped bit call is at hand and runs through fn otherwise, or a callable that runs
+    singly.  convert: applied to a field or HLL command's reply."""
 
-    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group")
+    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group", "bitop")
 
-    def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None, group=None):
+    def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None, group=None,
+                 bitop=None):
         self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
-        self.field, self.convert, self.hll, self.group = field, convert, hll, group
+        self.field, self.convert, self.hll, self.group, self.bitop = field, convert, hll, group, bitop
 
     def as_field(self):
         """the command as a BITFIELD sub-command: GETBIT / SETBIT are GET / SET of a u1, which leave the same
@@ -1105,8 +1131,22 @@ def _settle_group(c: _Queued, reply, status) -> None:
         c.future._set(c.convert(value) if c.convert else value)
 
 
+BITGROUP_FAILED = 0xFF  # status of a group of rbx_bitset_op_groups that failed alone
+_BITOP_NOT_MSG = "ERR BITOP NOT must be called with a single source key."
+
+
+def _settle_bitop(c: _Queued, reply, status) -> None:
+    """a BITOP or whole-string BITCOUNT of a grouped bit run; reply = (length, count)"""
+    if int(status) == BITGROUP_FAILED:
+        op, _dest, sources = c.bitop
+        c.future._set(error=RedisException(_BITOP_NOT_MSG if op == L.RBX_BITOP_NOT and len(sources) != 1
+                                           else "WRONGTYPE Operation against a key holding the wrong kind of value"))
+    else:
+        c.future._set(c.convert(int(reply[0]), int(reply[1])))
+
+
 def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, hll_count_groups_call=None,
-              hll_merge_groups_call=None):
+              hll_merge_groups_call=None, bit_groups_call=None):
     """Executes queued commands in submission order.  Every maximal run of consecutive bit commands, over any
     keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies).  With a
     field_stream_call, field commands join the runs, and a run that holds at least one of them is ONE
@@ -1116,9 +1156,12 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
     status); bit and field runs and HLL runs never mix, and each closes the other.  With an hll_count_groups_call,
     every maximal run of consecutive multi-key PFCOUNTs, over any keys, is ONE hll_count_groups_call(names, groups)
     -> (rc, message, counts, status); with an hll_merge_groups_call, every maximal run of consecutive PFMERGEs is
-    ONE hll_merge_groups_call(names, dests, groups) -> (rc, message, status).  A count run, a merge run, an HLL
-    stream run and a bit / field run each close the others.  Every other command runs through its own call at
-    its position.  Each command's future is set; returns (responses, first error)."""
+    ONE hll_merge_groups_call(names, dests, groups) -> (rc, message, status).  With a bit_groups_call, every maximal
+    run of consecutive BITOPs and whole-string BITCOUNTs, over any keys, is ONE bit_groups_call(names, ops, dests,
+    groups) -> (rc, message, lens, counts, status), a BITCOUNT travelling as a one-source OR without a destination.
+    A count run, a merge run, an HLL stream run, a grouped bit run and a bit / field run each close the others.
+    Every other command runs through its own call at its position.  Each command's future is set; returns
+    (responses, first error)."""
     def joins(q):
         return q.op is not None or (q.field is not None and field_stream_call is not None)
 
@@ -1130,6 +1173,9 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
 
     def joins_merges(q):
         return q.group is not None and q.group[0] == "merge" and hll_merge_groups_call is not None
+
+    def joins_bitops(q):
+        return q.bitop is not None and bit_groups_call is not None
 
     def run_from(i, belongs):
         """the maximal run of commands from queue[i] on that belong together"""
@@ -1157,6 +1203,13 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
         rc, msg, status = hll_merge_groups_call(list(ids), dests, groups)
         return rc, msg, [None] * len(status), status
 
+    def bitops_call(run, _names, _keys):
+        ids: dict = {}
+        dests = [None if c.bitop[1] is None else ids.setdefault(c.bitop[1], len(ids)) for c in run]
+        groups = [[ids.setdefault(n, len(ids)) for n in c.bitop[2]] for c in run]
+        rc, msg, lens, counts, status = bit_groups_call(list(ids), [c.bitop[0] for c in run], dests, groups)
+        return rc, msg, list(zip(lens, counts)), status
+
     def field_call(run, names, keys):
         return field_stream_call(names, keys, [c.as_field() for c in run])
 
@@ -1177,6 +1230,9 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
         elif joins_merges(queue[i]):
             run = run_from(i, joins_merges)
             error = _run_stream(run, merges_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_group)
+        elif joins_bitops(queue[i]):
+            run = run_from(i, joins_bitops)
+            error = _run_stream(run, bitops_call, alone, _settle_bitop)
         elif joins(queue[i]):
             run = run_from(i, joins)
             if any(c.field is not None for c in run):
@@ -1211,8 +1267,9 @@ class BatchResult:
 class RBatchBitSet:
     """RBatch.getBitSet(name) (M/RedissonBatch.java:182-184): RBitSetAsync, every method queued.  get / set /
     clearBit and the typed-field methods of consecutive commands travel together (one rbx_bitset_stream call,
-    or one rbx_bitset_field_stream call when a field command is among them); the others run through RBitSet's
-    own call."""
+    or one rbx_bitset_field_stream call when a field command is among them); so do consecutive or / and / xor /
+    not / cardinality commands (one rbx_bitset_op_groups call, in order); the others run through RBitSet's own
+    call."""
 
     def __init__(self, batch: "RBatch", name: str):
         self._batch, self._name = batch, name
@@ -1309,10 +1366,40 @@ class RBatchBitSet:
         return self._single("clearRange", fromIndex, toIndex)
 
     def cardinalityAsync(self) -> BatchFuture:
-        return self._single("cardinality")
+        """:482-484 BITCOUNT: a one-source OR without a destination of the grouped call"""
+        bitset, name = self._batch._bitset, self._name
+        return self._batch._add(_Queued(name, fn=lambda: bitset(name).cardinality(),
+                                        bitop=(L.RBX_BITOP_OR, None, [name]), convert=lambda _length, count: count))
 
     def sizeAsync(self) -> BatchFuture:
         return self._single("size")
+
+    def lengthAsync(self) -> BatchFuture:
+        return self._single("length")
+
+    def toByteArrayAsync(self) -> BatchFuture:
+        return self._single("toByteArray")
+
+    # ---- BITOP (M/api/RBitSetAsync.java:208-353, M/RedissonBitSet.java:362-388, :462-464): consecutive ones, and
+    # cardinalityAsync among them, travel together in one rbx_bitset_op_groups call ----
+    def _bitop(self, method: str, op: int, names) -> BatchFuture:
+        """opAsync :381-388 -- BITOP op name name others..: the destination is also the first source"""
+        bitset, name = self._batch._bitset, self._name
+        return self._batch._add(_Queued(name, fn=lambda: getattr(bitset(name), method)(*names),
+                                        bitop=(op, name, [name, *names]), convert=lambda _length, _count: None))
+
+    def orAsync(self, *bitSetNames: str) -> BatchFuture:
+        return self._bitop("or_", L.RBX_BITOP_OR, bitSetNames)
+
+    def andAsync(self, *bitSetNames: str) -> BatchFuture:
+        return self._bitop("and_", L.RBX_BITOP_AND, bitSetNames)
+
+    def xorAsync(self, *bitSetNames: str) -> BatchFuture:
+        return self._bitop("xor", L.RBX_BITOP_XOR, bitSetNames)
+
+    def notAsync(self) -> BatchFuture:
+        """:462-464 BITOP NOT name name"""
+        return self._bitop("not_", L.RBX_BITOP_NOT, ())
 
     def clearAsync(self) -> BatchFuture:
         return self._single("clear")
@@ -1342,6 +1429,12 @@ class RBatchBitSet:
     clear_range_async = clearRangeAsync
     cardinality_async = cardinalityAsync
     size_async = sizeAsync
+    length_async = lengthAsync
+    to_byte_array_async = toByteArrayAsync
+    or_async = orAsync
+    and_async = andAsync
+    xor_async = xorAsync
+    not_async = notAsync
     clear_async = clearAsync
 
 
@@ -1394,12 +1487,13 @@ class RBatch:
     """RedissonClient.createBatch() (M/RedissonBatch.java): commands queue across any number of keys, execute()
     runs them in submission order (M/command/CommandBatchService.java:115-134,335) and returns their replies
     in that order.  stream_call / bitset / field_stream_call / hll_stream_call / hyperloglog /
-    hll_count_groups_call / hll_merge_groups_call replace the engine's calls (tests); without a client and without
-    a field_stream_call (an hll_stream_call, a grouped call), field (HLL, multi-key PFCOUNT / PFMERGE) commands run
-    singly through bitset(name) (hyperloglog(name, codec))."""
+    hll_count_groups_call / hll_merge_groups_call / bit_groups_call replace the engine's calls (tests); without a
+    client and without a field_stream_call (an hll_stream_call, a grouped call), field (HLL, multi-key PFCOUNT /
+    PFMERGE, BITOP / BITCOUNT) commands run singly through bitset(name) (hyperloglog(name, codec))."""
 
     def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None, field_stream_call=None,
-                 hll_stream_call=None, hyperloglog=None, hll_count_groups_call=None, hll_merge_groups_call=None):
+                 hll_stream_call=None, hyperloglog=None, hll_count_groups_call=None, hll_merge_groups_call=None,
+                 bit_groups_call=None):
         self._client = client
         self._stream_call = stream_call or (lambda *a: bitset_stream_call(client, *a))
         if field_stream_call is None and client is not None:
@@ -1413,6 +1507,9 @@ class RBatch:
         if hll_merge_groups_call is None and client is not None:
             hll_merge_groups_call = lambda *a: _engine_hll_merge_groups_call(client, *a)  # noqa: E731
         self._hll_groups_calls = (hll_count_groups_call, hll_merge_groups_call)
+        if bit_groups_call is None and client is not None:
+            bit_groups_call = lambda *a: _engine_bitset_op_groups_call(client, *a)  # noqa: E731
+        self._bit_groups_call = bit_groups_call
         self._hyperloglog = hyperloglog or (lambda name, codec: RHyperLogLog(client, name, codec))
         self._bitset = bitset or (lambda name: RBitSet(client, name))
         self._queue: list = []
@@ -1436,7 +1533,7 @@ class RBatch:
             raise IllegalStateException("Batch already executed!")
         self._executed = True
         responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call, self._hll_stream_call,
-                                     *self._hll_groups_calls)
+                                     *self._hll_groups_calls, self._bit_groups_call)
         if error is not None:
             raise error
         return BatchResult(responses)

@@ -4,6 +4,8 @@
 // S/ = redisson-spring-data/redisson-spring-data-31/src/main/java/org/redisson/spring/data/connection/
 #include <cstring>
 
+#include "bit_groups_plan.h"
+#include "hll_groups_plan.h"  // hll_groups_check: the grouped calls share their limits
 #include "rbx_ctx.h"
 #include "tunables.h"
 
@@ -677,6 +679,216 @@ static int field_stream_failed(int kind) {
     return fail(RBX_E_REDIS, kind == kFsBadType ? kFieldTypeMsg : kBitOffsetMsg);
 }
 
+// ---- many BITOPs / BITCOUNTs of a combination in one call (rbx_bitset_op_groups) ----
+static const char *const kBitopNotMsg = "ERR BITOP NOT must be called with a single source key.";
+static std::atomic<uint32_t> g_bitgroups_last[4];  // rbx_bench_bitgroups_last shows them
+enum { kBgPhases = 0, kBgLaunches = 1, kBgTile = 2, kBgDeviceGroups = 3 };
+
+// The keys of one grouped call, each distinct name resolved once (stream_names_resolve has the rules), with what
+// the host carries through the groups: per canonical id the bitmap (null = missing) and its Redis length.  A
+// bitmap the call deletes or replaces stays referenced in `retired` to the call's final wait: a launch of an
+// earlier phase may still read it.
+struct BgKeys {
+    std::vector<std::string> nm;
+    std::vector<uint32_t> canon;
+    std::vector<uint8_t> wrong;
+    std::vector<std::shared_ptr<Bitmap>> bm;
+    std::vector<uint64_t> len;
+    std::vector<std::shared_ptr<Bitmap>> retired;
+};
+
+// One phase, the groups [p0, p1) that are not skipped (failed or forwarded): no destination is another group's
+// source or destination (bit_groups_plan), so one launch runs them all.  Every length is the host's: L[g] and the
+// keys' lengths are carried forward here, destinations are created, grown and deleted, and only the groups with a
+// result of some length and something to store or count reach the device.
+static int bg_phase(rbx_ctx *c, BgKeys &K, const uint8_t *grp_op, const uint32_t *grp_dest, const uint64_t *grp_off,
+                    const uint32_t *grp_key, const uint8_t *skip, uint32_t p0, uint32_t p1, uint64_t *L,
+                    unsigned long long *d_counts, hipStream_t st, uint32_t *stats) {
+    stats[kBgPhases]++;
+    std::vector<BitGroup> recs;
+    std::vector<BitopSrc> srcs;
+    std::vector<const Bitmap *> src_bm, rec_dst;  // whose pointers the table takes once every allocation is final
+    uint64_t total = 0;
+    for (uint32_t g = p0; g < p1; ++g) {
+        if (skip[g]) continue;
+        uint64_t out_len = 0, full = ~0ULL;
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) {
+            const uint32_t k = K.canon[grp_key[i]];
+            out_len = std::max(out_len, K.len[k]);
+            full = std::min<uint64_t>(full, K.bm[k] ? K.len[k] : 0);
+        }
+        L[g] = out_len;
+        const bool writes = grp_dest[g] != RBX_BITGROUP_NO_DEST;
+        const uint32_t d = writes ? K.canon[grp_dest[g]] : 0;
+        if (out_len == 0) {  // the empty result: DEL dest; the count is 0
+            if (writes) {
+                c->ks.erase(K.nm[d]);
+                if (K.bm[d]) K.retired.push_back(std::move(K.bm[d]));
+                K.bm[d].reset();
+                K.len[d] = 0;
+            }
+            continue;
+        }
+        if (!writes && !d_counts) continue;  // nothing to store and nothing to count
+        BitGroup r{};
+        r.count = d_counts ? d_counts + g : nullptr;
+        r.out_len = out_len;
+        r.full = full & ~15ULL;
+        r.op = grp_op[g];
+        r.nsrc = (uint32_t)(grp_off[g + 1] - grp_off[g]);
+        r.src_off = (uint32_t)srcs.size();
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) {  // (the lengths before dest takes its new one)
+            const uint32_t k = K.canon[grp_key[i]];
+            srcs.push_back(BitopSrc{nullptr, K.len[k]});
+            src_bm.push_back(K.bm[k].get());
+        }
+        r.span = (out_len + 15) & ~15ULL;
+        if (writes) {
+            uint64_t prev = K.len[d];
+            std::shared_ptr<Bitmap> now;
+            RBX_TRY(bitset_for_write(c, K.nm[d], out_len, st, &now));
+            if (now != K.bm[d]) {  // created (or the key's timeout passed since the names were resolved)
+                if (K.bm[d]) K.retired.push_back(std::move(K.bm[d]));
+                K.bm[d] = now;
+                prev = 0;
+            }
+            // the sweep also clears what a longer previous dest held past the result
+            r.span = std::min<uint64_t>((std::max(out_len, prev) + 15) & ~15ULL, now->cap_bytes);
+            K.len[d] = out_len;
+            if (Entry *e = c->ks.find(K.nm[d])) e->expire_at = -1;  // setKey without KEEPTTL
+        }
+        rec_dst.push_back(writes ? K.bm[d].get() : nullptr);
+        total += r.span;
+        recs.push_back(r);
+    }
+    if (recs.empty()) return RBX_OK;
+    // the table after every dest has its final allocation: a source that is its dest moved with it
+    for (size_t j = 0; j < srcs.size(); ++j) srcs[j].bytes = src_bm[j] ? (const uint8_t *)src_bm[j]->d_words : nullptr;
+    const uint32_t tuned = g_tune.bitgroups_tile;
+    const uint32_t tile = tuned ? tuned : bitgroups_auto_tile(total);
+    const size_t n = recs.size();
+    std::vector<uint64_t> first(n + 1, 0);
+    for (size_t j = 0; j < n; ++j) {
+        if (rec_dst[j]) {
+            recs[j].dst = (uint8_t *)rec_dst[j]->d_words;
+            recs[j].dst_len = rec_dst[j]->d_len;
+        }
+        first[j + 1] = first[j] + (recs[j].span + tile - 1) / tile;
+    }
+    // records | first tiles | sources, in one upload (a pageable source is staged by the runtime before the call
+    // returns; stream order keeps the previous phase's launch ahead of this overwrite)
+    const size_t rec_bytes = n * sizeof(BitGroup), first_bytes = (n + 1) * 8, src_bytes = srcs.size() * sizeof(BitopSrc);
+    std::vector<uint8_t> blob(rec_bytes + first_bytes + src_bytes);
+    memcpy(blob.data(), recs.data(), rec_bytes);
+    memcpy(blob.data() + rec_bytes, first.data(), first_bytes);
+    memcpy(blob.data() + rec_bytes + first_bytes, srcs.data(), src_bytes);
+    DevBuf &tab = c->dev->bits.grp_table;
+    RBX_TRY(tab.reserve(blob.size()));
+    HIP_TRY(hipMemcpyAsync(tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    uint8_t *p = tab.as<uint8_t>();
+    launch_bitgroups_sweep((const BitGroup *)p, (const uint64_t *)(p + rec_bytes), (uint32_t)n, first[n],
+                           (const BitopSrc *)(p + rec_bytes + first_bytes), tile, st);
+    HIP_TRY(hipGetLastError());
+    stats[kBgLaunches]++;
+    stats[kBgTile] = tile;
+    stats[kBgDeviceGroups] += (uint32_t)n;
+    return RBX_OK;
+}
+
+// at least n pinned bytes
+static int bg_pin(PinBuf &pin, size_t n) {
+    if (pin.cap >= n) return RBX_OK;
+    HIP_TRY(pin.alloc(std::max<size_t>(n, 4096), hipHostMallocDefault));
+    return RBX_OK;
+}
+
+static int bitset_op_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint8_t *grp_op,
+                            const uint32_t *grp_dest, const uint64_t *grp_off, const uint32_t *grp_key, uint32_t ngroups,
+                            uint64_t *lens, uint64_t *counts, uint8_t *status) {
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    BitsetScratch &b = c->dev->bits;
+    BgKeys K;
+    K.canon.resize(nkeys);
+    K.wrong.assign(nkeys, 0);
+    K.bm.resize(nkeys);
+    K.len.assign(nkeys, 0);
+    stream_names_resolve(c, names, nkeys, KType::Bitmap, &K.nm, K.canon.data(), K.wrong.data(),
+                         [&](uint32_t i, const Entry &e) { K.bm[i] = e.bm; });
+    // the length words of the existing keys: one gather, one copy back, the call's first wait
+    std::vector<const unsigned long long *> ptrs;
+    std::vector<uint32_t> at;
+    for (uint32_t i = 0; i < nkeys; ++i)
+        if (K.bm[i]) {
+            ptrs.push_back(K.bm[i]->d_len);
+            at.push_back(i);
+        }
+    if (!ptrs.empty()) {
+        const size_t n = ptrs.size();
+        RBX_TRY(b.grp_lens.reserve(n * 16));  // pointers | values
+        auto *d_out = b.grp_lens.as<unsigned long long>() + n;
+        HIP_TRY(hipMemcpyAsync(b.grp_lens.p, ptrs.data(), n * 8, hipMemcpyHostToDevice, st));
+        launch_bitgroups_lens(b.grp_lens.as<const unsigned long long *>(), (uint32_t)n, d_out, st);
+        HIP_TRY(hipGetLastError());
+        RBX_TRY(bg_pin(b.grp_pin, n * 8));
+        const unsigned long long *got = b.grp_pin.as<unsigned long long>();
+        HIP_TRY(hipMemcpyAsync(b.grp_pin.p, d_out, n * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t j = 0; j < n; ++j) K.len[at[j]] = got[j];
+    }
+    // the groups that fail alone, and the canonical ids the planner reads
+    std::vector<uint8_t> failed(ngroups, 0), skip(ngroups, 0);
+    std::vector<uint32_t> cdest(ngroups), csrc(grp_off[ngroups]);
+    int first_code = RBX_OK;
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        const bool writes = grp_dest[g] != RBX_BITGROUP_NO_DEST;
+        bool wrong = writes && K.wrong[grp_dest[g]] != 0;
+        cdest[g] = writes ? K.canon[grp_dest[g]] : kBitGroupNoDest;
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) {
+            wrong = wrong || K.wrong[grp_key[i]] != 0;
+            csrc[i] = K.canon[grp_key[i]];
+        }
+        // (the single call checks NOT's source count before any key's type)
+        const bool bad_not = grp_op[g] == RBX_BITOP_NOT && grp_off[g + 1] - grp_off[g] != 1;
+        failed[g] = bad_not || wrong;
+        if (failed[g] && first_code == RBX_OK) first_code = bad_not ? RBX_E_REDIS : RBX_E_WRONGTYPE;
+        if (status) status[g] = failed[g] ? 0xFF : 0;
+    }
+    std::vector<uint32_t> end, fwd;
+    bit_groups_plan(grp_op, cdest.data(), grp_off, csrc.data(), failed.data(), ngroups, nkeys, &end, &fwd);
+    for (uint32_t g = 0; g < ngroups; ++g) skip[g] = failed[g] || fwd[g] != kBitGroupRuns;
+    unsigned long long *d_counts = nullptr;
+    if (counts) {
+        RBX_TRY(b.grp_counts.reserve((size_t)ngroups * 8));
+        RBX_TRY(bg_pin(b.grp_pin, (size_t)ngroups * 8));
+        d_counts = b.grp_counts.as<unsigned long long>();
+        HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)ngroups * 8, st));
+    }
+    // the largest table a phase can upload, once: growing the buffer between phases would wait for the device
+    RBX_TRY(b.grp_table.reserve((size_t)ngroups * (sizeof(BitGroup) + 8) + 8 + (size_t)grp_off[ngroups] * sizeof(BitopSrc)));
+    uint32_t stats[4] = {0, 0, 0, 0};
+    std::vector<uint64_t> L(ngroups, 0);
+    uint32_t p0 = 0;
+    for (uint32_t p1 : end) {
+        RBX_TRY(bg_phase(c, K, grp_op, grp_dest, grp_off, grp_key, skip.data(), p0, p1, L.data(), d_counts, st, stats));
+        p0 = p1;
+    }
+    if (counts) HIP_TRY(hipMemcpyAsync(b.grp_pin.p, d_counts, (size_t)ngroups * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the call's second wait; K.retired may go
+    if (counts) memcpy(counts, b.grp_pin.p, (size_t)ngroups * 8);
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        if (!failed[g] && fwd[g] != kBitGroupRuns) {  // answered from its writer, an earlier group
+            L[g] = L[fwd[g]];
+            if (counts) counts[g] = counts[fwd[g]];
+        }
+        if (lens) lens[g] = L[g];
+    }
+    for (int i = 0; i < 4; ++i) g_bitgroups_last[i] = stats[i];
+    if (first_code == RBX_E_REDIS) return fail(RBX_E_REDIS, kBitopNotMsg);
+    if (first_code != RBX_OK) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    return RBX_OK;
+}
+
 }  // namespace rbx
 
 using namespace rbx;
@@ -860,7 +1072,7 @@ int rbx_bitset_op(rbx_ctx *c, int op, rbx_name dest, const rbx_name *srcs, uint3
     if (op < RBX_BITOP_AND || op > RBX_BITOP_NOT) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITOP operation");
     if (nsrc == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, "BITOP needs a source key");
     if (op == RBX_BITOP_NOT && nsrc != 1)
-        return fail(RBX_E_REDIS, "ERR BITOP NOT must be called with a single source key.");
+        return fail(RBX_E_REDIS, kBitopNotMsg);
     std::vector<std::string> sn;
     RBX_TRY(names_of(srcs, nsrc, &sn));
     const std::string dn = name_of(dest);
@@ -896,6 +1108,28 @@ int rbx_bitset_op(rbx_ctx *c, int op, rbx_name dest, const rbx_name *srcs, uint3
     launch_bitop(op, (uint8_t *)db->d_words, db->d_len, c->dev->bits.bitop_srcs.as<BitopSrc>(), nsrc, out_len, span, st);
     HIP_TRY(hipGetLastError());
     if (Entry *e = c->ks.find(dn)) e->expire_at = -1;  // setKey without KEEPTTL
+    return RBX_OK;
+}
+
+int rbx_bitset_op_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint8_t *grp_op, const uint32_t *grp_dest,
+                         const uint64_t *grp_off, const uint32_t *grp_key, uint32_t ngroups, uint64_t *lens,
+                         uint64_t *counts, uint8_t *status) {
+    RBX_TRY(stream_names_check(c, names, nkeys));
+    if (const char *what = hll_groups_check(grp_off, grp_key, ngroups, nkeys, true))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, what);
+    if (ngroups == 0) return RBX_OK;  // no command is sent
+    if (!grp_op || !grp_dest) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        if (grp_op[g] > RBX_BITOP_NOT) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown BITOP operation");
+        if (grp_dest[g] >= nkeys && grp_dest[g] != RBX_BITGROUP_NO_DEST)
+            return fail(RBX_E_ILLEGAL_ARGUMENT, "a group's destination is not below nkeys");
+    }
+    return bitset_op_groups(c, names, nkeys, grp_op, grp_dest, grp_off, grp_key, ngroups, lens, counts, status);
+}
+
+int rbx_bench_bitgroups_last(uint32_t out[4]) {
+    if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (int i = 0; i < 4; ++i) out[i] = g_bitgroups_last[i];
     return RBX_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/rbx.h"
+#include "bitop_device.h"
 #include "bloom_common.h"
 #include "rbx_kernels.h"
 
@@ -24,23 +25,6 @@ namespace rbx {
 // A source is read with a 16-byte load only where the whole vector lies inside its string;
 // the vector holding its last bytes is assembled byte by byte, and nothing past len is touched.
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 bitop_load(const BitopSrc &s, uint64_t o) {
-    if (o + 16 <= s.len) return ld_nt16(s.bytes + o);
-    uint32_t w[4] = {0, 0, 0, 0};
-    if (o < s.len) {
-        const int n = (int)(s.len - o);  // 1..15
-#pragma unroll
-        for (int j = 0; j < 15; ++j)  // unrolled: w[] stays in registers
-            if (j < n) w[j >> 2] |= (uint32_t)s.bytes[o + j] << (8 * (j & 3));
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// the low min(max(n, 0), 4) bytes of a word
-__device__ __forceinline__ uint32_t low_bytes(int64_t n) {
-    return n >= 4 ? ~0u : (n <= 0 ? 0u : (1u << (8 * (int)n)) - 1);
-}
-
 template <int OP>
 __global__ __launch_bounds__(256) void k_bitop(uint8_t *dst, unsigned long long *dst_len, const BitopSrc *srcs,
                                                uint32_t nsrc, uint64_t out_len, uint64_t span) {

@@ -263,20 +263,21 @@ static uint64_t mix64_host(uint64_t x) {
 // ---- rbx_tune: one row per key (include/rbx_bench.h documents them) --------------------------------
 struct TuneRow {
     const char *key;
-    enum Kind { kRange, kOneOf, kBits, kPow2 } kind;  // v = {lo, hi} | the n values | {mask of the bits} | {lo, hi}
+    enum Kind { kRange, kOneOf, kBits, kPow2, kPow2Or0 } kind;  // v = {lo, hi} | the n values | {mask of the bits} | {lo, hi}
     int v[7], n;
     bool diag;            // exists only in the profiling build (kDiag, librbx_diag.so)
     void (*store)(int);   // a field of g_tune, or a set_* function of rbx_kernels.h
     bool accepts(int x) const {
         if (kind == kRange) return x >= v[0] && x <= v[1];
         if (kind == kPow2) return x >= v[0] && x <= v[1] && (x & (x - 1)) == 0;
+        if (kind == kPow2Or0) return x == 0 || (x >= v[0] && x <= v[1] && (x & (x - 1)) == 0);
         if (kind == kBits) return (x & ~v[0]) == 0;
         return std::find(v, v + n, x) != v + n;
     }
     std::string wants() const {  // the tail of the rejection message
-        if (kind == kRange || kind == kPow2)
-            return std::string(kind == kPow2 ? ": a power of two" : "") + " in [" + std::to_string(v[0]) + ", " +
-                   std::to_string(v[1]) + "]";
+        if (kind == kRange || kind == kPow2 || kind == kPow2Or0)
+            return std::string(kind == kPow2 ? ": a power of two" : kind == kPow2Or0 ? ": 0 or a power of two" : "") +
+                   " in [" + std::to_string(v[0]) + ", " + std::to_string(v[1]) + "]";
         std::string s;
         if (kind == kOneOf)
             for (int i = 0; i < n; ++i) s += (i ? ", " : "") + std::to_string(v[i]);
@@ -290,6 +291,7 @@ struct TuneRow {
 #define ONE_OF(...) TuneRow::kOneOf, {__VA_ARGS__}, (int)std::initializer_list<int>{__VA_ARGS__}.size()
 #define BITS(mask) TuneRow::kBits, {mask}, 1
 #define POW2(lo, hi) TuneRow::kPow2, {lo, hi}, 2
+#define POW2_OR_0(lo, hi) TuneRow::kPow2Or0, {lo, hi}, 2
 #define FIELD(f) [](int x) { g_tune.f = (decltype(g_tune.f.load()))x; }
 static constexpr int kSegMax = (int)kSegMaxKeys, kIntMax = 0x7fffffff;
 static const TuneRow kTuneRows[] = {
@@ -335,11 +337,13 @@ static const TuneRow kTuneRows[] = {
     {"hllstream_chunk", RANGE(1, 1 << 30), false, FIELD(hllstream_chunk)},  // positions in a chunk are 32-bit
     {"hllstream_elems_per_round", RANGE(1, kIntMax), false, FIELD(hllstream_elems_per_round)},
     {"hllgroups_split", ONE_OF(0, 1, 2, 4, 8, 16), false, FIELD(hllgroups_split)},
+    {"bitgroups_tile", POW2_OR_0(4096, 1 << 20), false, FIELD(bitgroups_tile)},
 };
 #undef RANGE
 #undef ONE_OF
 #undef BITS
 #undef POW2
+#undef POW2_OR_0
 #undef FIELD
 
 }  // namespace rbx

@@ -394,6 +394,10 @@ struct BitsetScratch {
     // the BITFIELD stream shares bst_keys, bst_sum, bst_sort and bst_table (one call at a time holds them);
     // its host form uploads commands | keys here and answers through fld_out and fld_nil
     DevBuf fst_cmds;
+    // grouped BITOPs / BITCOUNTs (rbx_bitset_op_groups): one phase's group records | first tiles |
+    // sources in one upload, the length words' pointers and values of the call's keys, one count per group
+    DevBuf grp_table, grp_lens, grp_counts;
+    PinBuf grp_pin;  // where the lengths and then the counts come back to (a pageable target costs a staging copy)
 };
 
 // Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).

@@ -645,4 +645,29 @@ int launch_hllgroups_union_count(const uint8_t *const *d_members, const uint32_t
 void launch_hllgroups_merge(uint8_t *const *d_dst, const uint8_t *const *d_members, const uint32_t *d_off,
                             uint32_t ngroups, int split, hipStream_t st);
 
+// ---- bitgroups_kernels.hip
+// Many BITOPs / BITCOUNTs of a combination in one launch (rbx_bitset_op_groups).  One record per group;
+// its sources are the nsrc entries of the launch's BitopSrc table from src_off on.
+struct BitGroup {
+    uint8_t *dst;                 // the destination's bytes, or null: the combination is stored nowhere
+    unsigned long long *dst_len;  // its length word (null with dst), which takes out_len
+    unsigned long long *count;    // takes the result's one bits, added onto a zeroed word; null: not counted
+    uint64_t out_len;             // the result's length: the longest source's, > 0
+    uint64_t span;                // the bytes swept: a multiple of 16 within dst's allocation covering out_len and
+                                  // dst's previous length; without dst, out_len rounded up to 16
+    uint64_t full;                // a multiple of 16 that every source's length reaches (0 when one is missing)
+    uint32_t op;                  // RBX_BITOP_*
+    uint32_t nsrc;                // >= 1; exactly 1 under RBX_BITOP_NOT
+    uint32_t src_off;
+    uint32_t pad;
+};
+constexpr uint32_t kBitGroupsMinTile = 4096, kBitGroupsMaxTile = 1u << 20;
+// d_out[i] = *d_ptrs[i] for n length words
+void launch_bitgroups_lens(const unsigned long long *const *d_ptrs, uint32_t n, unsigned long long *d_out, hipStream_t st);
+// The groups' spans cut into tiles of tile_bytes (a power of two in kBitGroupsMinTile .. kBitGroupsMaxTile): group g
+// owns the tiles d_first[g] .. d_first[g + 1), d_first[0] = 0, d_first[ngroups] = tiles, every group at least one.  No
+// dst may be a source or the dst of another group; it may be a source of its own.
+void launch_bitgroups_sweep(const BitGroup *d_groups, const uint64_t *d_first, uint32_t ngroups, uint64_t tiles,
+                            const BitopSrc *d_srcs, uint32_t tile_bytes, hipStream_t st);
+
 }  // namespace rbx

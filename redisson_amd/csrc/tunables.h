@@ -136,6 +136,11 @@ struct Tunables {
     // at P = 1); at 256, 4,096 and 10,000 groups all six settings lie within 4 % (0.088 - 0.092, 0.754 - 0.757 and
     // 1.777 - 1.795 ms), so from 256 on P = 1 is taken.
     std::atomic<int> hllgroups_split{0};
+
+    // ---- grouped BITOPs and BITCOUNTs (api_bitset.cpp) ----
+    // "bitgroups_tile": the bytes T of a tile of the segmented sweep: 0 (default) = auto, else a power of two in
+    // 4 KiB .. 1 MiB.  All exact.  Auto: bitgroups_auto_tile below.
+    std::atomic<uint32_t> bitgroups_tile{0};
 };
 
 constexpr uint32_t kHllGroupsFillBlocks = 256;
@@ -143,6 +148,24 @@ inline int hllgroups_auto_split(uint64_t groups) {
     int p = 1;
     while (p < 16 && groups * (uint64_t)p < kHllGroupsFillBlocks) p <<= 1;
     return p;
+}
+
+// The auto tile of a launch that sweeps `bytes` bytes in all: the largest power of two T in 4 KiB .. kBitGroupsAutoMaxTile
+// with bytes / T >= kBitGroupsFillTiles, so that a launch of little work still spreads over the device (one 1 MiB group
+// is 256 tiles of 4 KiB) and a launch of much work makes tiles of kBitGroupsAutoMaxTile.  Measured call times (DESIGN
+// 11.9 row f; T = 4 / 16 / 64 / 256 KiB / 1 MiB): 1 AND of 2 x 1 MiB 0.051 / 0.053 / 0.063 / 0.114 / 0.253 ms and 16 of
+// them 0.069 / 0.070 / 0.089 / 0.171 / 0.502 ms -- little work wants small tiles; 256 of them 0.417 / 0.298 / 0.264 /
+// 0.298 / 0.631 ms and 10,000 counted ANDs of 2 x 128 KiB 1.944 / 1.144 / 0.856 / 0.838 / 0.876 ms -- much work wants
+// 64 - 256 KiB, which lie within 13 % of each other either way, and 1 MiB is slowest wherever a group is about one
+// tile.  One AND of 2 x 512 MiB runs 0.335 / 0.388 / 0.406 / 0.419 / 0.628 ms: a single huge group would rather have
+// 4 KiB (a workgroup keeps its group across tiles, and neighbouring workgroups then read neighbouring bytes), which
+// this rule, looking at the launch's bytes only, does not give it.
+constexpr uint32_t kBitGroupsFillTiles = 2048;  // kMaxGrid: eight workgroups per CU
+constexpr uint32_t kBitGroupsAutoMaxTile = 64 << 10;
+inline uint32_t bitgroups_auto_tile(uint64_t bytes) {
+    uint32_t t = 4096;
+    while (t < kBitGroupsAutoMaxTile && bytes / (2 * (uint64_t)t) >= kBitGroupsFillTiles) t <<= 1;
+    return t;
 }
 
 extern Tunables g_tune;

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib as L
 from .client import (GETBIT, PFADD, PFCOUNT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued,
-                     bitset_field_stream_call, bitset_stream_call, hll_count_groups_call, hll_merge_groups_call,
+                     bitset_field_stream_call, bitset_op_groups_call, bitset_stream_call, hll_count_groups_call, hll_merge_groups_call,
                      hll_stream_call, run_queue)
 from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
@@ -155,7 +155,39 @@ def _pf_merge_group(destinationKey, *sourceKeys):
     return ("merge", _key(destinationKey), [_key(k) for k in sourceKeys])
 
 
-def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None):
+_BITOPS = {"AND": L.RBX_BITOP_AND, "OR": L.RBX_BITOP_OR, "XOR": L.RBX_BITOP_XOR, "NOT": L.RBX_BITOP_NOT}
+
+
+def _bit_op_code(op, keys) -> int:
+    """bitOp's own checks (S:650-661): the RBX_BITOP_* value of an operation's name or value; NOT takes one source"""
+    code = _BITOPS.get(op.upper()) if isinstance(op, str) else (op if op in _BITOPS.values() else None)
+    if code is None:
+        raise IllegalArgumentException(f"unknown BITOP operation {op!r}")
+    if code == L.RBX_BITOP_NOT and len(keys) > 1:
+        raise UnsupportedOperationException("NOT operation doesn't support more than single source key")
+    return code
+
+
+def _bit_op_group(op, destination, *keys):
+    """((RBX_BITOP_*, destination, sources), convert) of a pipelined bitOp: the reply is the result's length.  NOT with
+    several sources raises before anything is queued (S:652-654)."""
+    try:
+        code = _bit_op_code(op, keys)
+    except IllegalArgumentException:
+        return None  # the single call raises it at its position
+    if not keys:
+        return None
+    return (code, _key(destination), [_key(k) for k in keys]), lambda length, _count: length
+
+
+def _bit_count_group(key, begin=None, end=None):
+    """the same of a pipelined bitCount(key): a one-source OR that is stored nowhere; a ranged one runs singly"""
+    if begin is not None or end is not None:
+        return None
+    return (L.RBX_BITOP_OR, None, [_key(key)]), lambda _length, count: count
+
+
+def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=None):
     """A command method of RedissonConnection: while a pipeline is open it queues itself and returns None
     (the result comes back from closePipeline); bit = (key, op, index) of a GETBIT / SETBIT, which travels with
     its neighbours in one rbx_bitset_stream call; field = (key, row, convert) of a BITFIELD with one sub-command
@@ -163,7 +195,9 @@ def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None):
     hll = (key, (op, elements), convert) of a PFADD / single-key PFCOUNT (or None for any other), which travels
     with its HLL neighbours in one rbx_hll_stream call; group = ("count", keys) of a multi-key PFCOUNT or ("merge",
     destination, sources) of a PFMERGE (or None for any other), which travels with its like in one
-    rbx_hll_count_groups / rbx_hll_merge_groups call."""
+    rbx_hll_count_groups / rbx_hll_merge_groups call; bitop = ((RBX_BITOP_*, destination or None, sources), convert)
+    of a BITOP or a whole-string BITCOUNT (or None for any other), which travels with its like in one
+    rbx_bitset_op_groups call."""
 
     def wrap(f):
         @functools.wraps(f)
@@ -175,6 +209,13 @@ def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None):
                 self._pipeline.append(_Queued(_key(key), op, _bit_index(index)))
                 return None
             single = lambda: f(self, *args, **kwargs)  # noqa: E731
+            if bitop is not None:
+                row = bitop(*args, **kwargs)
+                if row is not None:
+                    self._pipeline.append(_Queued(row[0][2][0], fn=single, bitop=row[0], convert=row[1]))
+                else:
+                    self._pipeline.append(_Queued(fn=single))
+                return None
             if group is not None:
                 try:
                     row = group(*args, **kwargs)
@@ -229,7 +270,8 @@ class RedissonConnection:
         exactly one sub-command among them they are one rbx_bitset_field_stream call.  Consecutive pfAdd and
         single-key pfCount commands, over any keys, are one rbx_hll_stream call; consecutive pfCount commands of
         two or more keys are one rbx_hll_count_groups call, consecutive pfMerge commands one rbx_hll_merge_groups
-        call.  Every command runs; then the first failure is raised."""
+        call.  Consecutive bitOp and bitCount(key) commands, over any keys, are one rbx_bitset_op_groups call.  Every
+        command runs; then the first failure is raised."""
         if self._pipeline is None:
             return []
         queue, self._pipeline = self._pipeline, None
@@ -237,7 +279,8 @@ class RedissonConnection:
                                    lambda *a: bitset_field_stream_call(self._client, *a),
                                    lambda *a: hll_stream_call(self._client, *a),
                                    lambda *a: hll_count_groups_call(self._client, *a),
-                                   lambda *a: hll_merge_groups_call(self._client, *a))
+                                   lambda *a: hll_merge_groups_call(self._client, *a),
+                                   lambda *a: bitset_op_groups_call(self._client, *a))
         if error is not None:
             raise error
         return results
@@ -293,7 +336,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_set(self._client.ctx, nm, int(offset), int(bool(value)), C.byref(old)))
         return bool(old.value)
 
-    @_pipelined
+    @_pipelined(bitop=_bit_count_group)
     def bitCount(self, key: bytes, begin: int | None = None, end: int | None = None) -> int:
         """BITCOUNT key  S:638-641, BITCOUNT key begin end  S:643-646 (bytes, both inclusive)"""
         nm, _keep = L.name_struct(_key(key))
@@ -307,16 +350,11 @@ class RedissonConnection:
                                                   C.byref(out)))
         return int(out.value)
 
-    @_pipelined
+    @_pipelined(bitop=_bit_op_group)
     def bitOp(self, op, destination: bytes, *keys: bytes) -> int:
         """BITOP op destination k1..kn -> the result's length  S:650-661.  op: AND / OR / XOR / NOT (a name or
         an RBX_BITOP_* value).  NOT with more than one source fails before any command is sent (S:652-654)."""
-        ops = {"AND": L.RBX_BITOP_AND, "OR": L.RBX_BITOP_OR, "XOR": L.RBX_BITOP_XOR, "NOT": L.RBX_BITOP_NOT}
-        code = ops.get(op.upper()) if isinstance(op, str) else (op if op in ops.values() else None)
-        if code is None:
-            raise IllegalArgumentException(f"unknown BITOP operation {op!r}")
-        if code == L.RBX_BITOP_NOT and len(keys) > 1:
-            raise UnsupportedOperationException("NOT operation doesn't support more than single source key")
+        code = _bit_op_code(op, keys)
         dest, _keep_d = L.name_struct(_key(destination))
         srcs, _keep = L.names_array([_key(k) for k in keys])
         out = C.c_uint64()
