@@ -72,6 +72,8 @@ int rbx_bench_bitgroups_last(uint32_t out[4]);
  *   "contains_partition"    region-bucketed contains for one large filter (one radix pass by 256 KiB
  *                           region, each region probed from LDS in two 128 KiB slices): 0 never,
  *                           1 always (k in [2,16]), 2 auto (default: bitmap >= 256 MiB, >= 4M keys)
+ *   "contains_stage1_grid"  that contains' stage-1 blocks at most, 1..256 (default 256); a chunk holds at most
+ *                           2^19 keys per block, so tests reach a block's last tile on a small batch
  *   "add_partition"         region-partitioned add: 0 never, 1 always, 2 auto (default:
  *                           bitmap >= 8 MiB and >= max(2^17, bits / 2^12) keys)
  *   "add_records"           how the partitioned add reports new keys: 0 owner bits, 1 non-owner

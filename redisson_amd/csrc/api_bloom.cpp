@@ -231,24 +231,15 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
     const uint32_t k = f.k;
     const uint64_t size = f.mp.size;
     const uint32_t nb = (uint32_t)((size + (1ULL << kBkBucketBits) - 1) >> kBkBucketBits);
-    // keys per chunk: key ids fit 27 bits and a chunk's pairs stay <= 2^30
-    uint64_t chunk = std::min<uint64_t>(1ULL << 27, (1ULL << 30) / (k - 1));
-    const uint64_t nch = (keys.n + chunk - 1) / chunk;
-    chunk = (keys.n + nch - 1) / nch;
-    chunk = (chunk + 1023) / 1024 * 1024;
+    // Chunk rule (bk_entry.h): at most grid * 2^19 keys, so a block-local key index fits an entry's 19 bits
+    // (2^27 at the default grid: key ids fit 27 bits), and a chunk's entries stay <= 2^30.  A smaller
+    // grid ("contains_stage1_grid", tests) splits the batch into more chunks.
+    const uint32_t gcap = std::min<uint32_t>(std::max<uint32_t>(g_tune.stage1_grid, 1u), kBkMaxGrid1);
+    const uint64_t chunk = bk_chunk_keys(keys.n, gcap, k);
     const uint64_t ngroups = (chunk + 63) / 64;
-    // Segment capacity.  Stage-1 block blk owns one segment per region.  With every key surviving
-    // stage 1 and the pairs spread uniformly over [0, size), a segment's fill is Poisson with mean
-    //   lambda = (keys per block) * (k - 1) * min(1, 2^21 / size).
-    // Chernoff: P(X >= lambda + x) <= exp(-x^2 / (2 (lambda + x/3))); x = 7 sqrt(lambda) + 24 keeps
-    // that below 1e-9 per segment for every lambda, i.e. below 1e-3 over the <= 2^19 segments of a
-    // chunk.  A pair past the capacity is probed directly (bk_direct): capacity never changes answers.
-    const uint32_t tile = kBkTileKeys;
-    const uint64_t ntiles0 = (chunk + tile - 1) / tile;
-    const uint64_t g0 = std::min<uint64_t>(ntiles0, kBkMaxGrid1);
-    const double lambda = (double)((ntiles0 + g0 - 1) / g0 * tile) * (k - 1) *
-                          std::min(1.0, (double)(1ULL << kBkBucketBits) / (double)size);
-    const uint64_t capS = ((uint64_t)(lambda + 7.0 * std::sqrt(lambda) + 24.0) + kBkLine - 1) / kBkLine * kBkLine;
+    // Segment capacity in entries, whole 64-byte lines of 12: bk_seg_cap has the Poisson bound.
+    const uint64_t g0 = bk_grid(chunk, gcap);
+    const uint64_t capS = bk_seg_cap(chunk, (uint32_t)g0, k, size);
     PartitionedContainsScratch &pc = c->dev->pc;
     RBX_TRY(pc.bits.reserve(ngroups * 16));
     const uint32_t nmranges = (uint32_t)((chunk + (1ULL << kBkMissRangeBits) - 1) >> kBkMissRangeBits);
@@ -257,7 +248,7 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
     const uint64_t capm = 2ULL << kBkMissRangeBits;
     RBX_TRY(pc.mrec.reserve((uint64_t)nmranges * capm * 4));
     RBX_TRY(pc.cnt.reserve((256 + (uint64_t)nb * g0) * 4));  // mcnt, segment counts
-    RBX_TRY(pc.pairs.reserve((uint64_t)nb * g0 * capS * 8));
+    RBX_TRY(pc.pairs.reserve(bk_seg_line(0, (uint32_t)g0, nb, capS) * kBkLineBytes));  // nb * g0 segments, in lines
     const int fl = fast_len(keys);
     for (uint64_t base = 0; base < keys.n; base += chunk) {
         PcArgs a{};
@@ -268,7 +259,7 @@ static int run_contains_partitioned(rbx_ctx *c, const KeysDev &keys, const Filte
         a.mp = f.mp;
         a.k = k;
         a.nb = nb;
-        a.grid1 = (uint32_t)std::min<uint64_t>((a.nchunk + tile - 1) / tile, kBkMaxGrid1);  // <= g0
+        a.grid1 = bk_grid(a.nchunk, gcap);  // <= g0, and nchunk <= grid1 * 2^19
         a.capS = capS;
         a.nwords4 = (size + 127) / 128 * 4;
         a.alive = pc.bits.as<unsigned long long>();

@@ -3,6 +3,7 @@
 // partitioned contains' geometry, the LDS bucket scan and the phase timer.
 #pragma once
 
+#include "bk_entry.h"
 #include "bloom_common.h"
 
 namespace rbx {
@@ -11,16 +12,15 @@ namespace rbx {
 // L2, measured slower: DESIGN.md r02).
 template <class T> __device__ __forceinline__ void run_store(T v, T *p) { __builtin_nontemporal_store(v, p); }
 
-// Partitioned contains, one radix pass (contains_partitioned.hip).  Stage 1 buckets pairs by
+// Partitioned contains, one radix pass (contains_partitioned.hip).  Stage 1 buckets entries by
 // 2^21-bit (256 KiB) bitmap region, at most 2048 of them; the probe holds one 2^20-bit (128 KiB)
 // slice of a region in LDS, and the two workgroups of a cluster hold the two slices of one region.
+// The region size, the stage-1 tile and grid and the entry's line (kBkLineEntries entries, copied
+// as kBkLineWords u64) are bk_entry.h's.
 constexpr uint32_t kBkCS = 2;                                                   // workgroups per cluster
-constexpr uint32_t kBkBucketBits = 21;                                          // bits per region
 constexpr uint32_t kBkSliceBits = kBkBucketBits - 1;                            // bits per slice
 constexpr uint32_t kBkSliceWords = 1u << (kBkSliceBits - 5);
 constexpr uint32_t kBkMaxBuckets = 1u << (32 - kBkBucketBits);                  // filters hold <= 2^32 bits
-constexpr uint32_t kBkLine = 8;                                                 // pairs per 64-byte line
-constexpr uint32_t kBkMaxGrid1 = 256;                                           // stage-1 blocks (persistent), one per CU
 
 // exclusive scan of cnt[0..nb) (nb <= 64 * PER, PER consecutive buckets per lane) by wave 0 into
 // start[] and pos[]

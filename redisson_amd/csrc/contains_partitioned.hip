@@ -5,19 +5,21 @@
 // ~55 G requests/s chip-wide, flat from 64 MiB to 1 GiB working sets), the same request rate a
 // 128-byte streaming read gets.  A 100M-key batch issues ~4e8 such gathers into a 512 MiB bitmap
 // (4.2M cache lines), i.e. ~100 requests per line.  Routing the probes through one streaming
-// radix pass turns almost all of them into 8-byte slots of whole-line streaming requests, and
-// the bitmap itself is read once, a 128 KiB slice at a time, into LDS.
+// radix pass turns almost all of them into 5-byte entries of whole-line streaming requests (twelve
+// to a 64-byte line: a 21-bit offset inside the region and a 19-bit key index local to the stage-1
+// block that wrote the segment, bk_entry.h), and the bitmap itself is read once, a 128 KiB slice at
+// a time, into LDS.
 //
 //   K1 stage1 : hash every key, test bit 0 with one random gather (a key is absent at its first
 //               0 bit, and on a lightly filled filter most absent keys fail here); `alive` bit per
-//               key; the survivors' k-1 remaining bits become (bit index, key id) pairs, bucketed
+//               key; the survivors' k-1 remaining bits become (bit offset, key index) entries, bucketed
 //               by 256 KiB bitmap region (<= 2048 buckets) through one 64-byte line buffer per
 //               bucket in LDS; a full buffer is stored as one whole line into the segment that
 //               this block owns for the bucket (no global reservations).
 //   K4 probe  : a cluster of two workgroups per region, each holding one 128 KiB slice (half) of it
-//               in LDS.  Both workgroups stream all of the region's segments and test the pairs
+//               in LDS.  Both workgroups stream all of the region's segments and test the entries
 //               that fall into their slice; a clear bit (only keys that survived stage 1 by chance)
-//               records the key id, bucketed by 2^19-key range.  The workgroups of a cluster share
+//               rebuilds the chunk's key id and records it, bucketed by 2^19-key range.  The workgroups of a cluster share
 //               blockIdx % 8 and are adjacent in dispatch order, so they tend to share an XCD and
 //               one of the two reads of a segment is served by its L2.  They never communicate:
 //               placement changes only the speed.
@@ -26,7 +28,7 @@
 // Measured bound (rocprof PMC, C2): every kernel runs at ~50 G memory requests/s at the L2->EA
 // interface (a read moves 128 B, a write 64 B, an atomic is one request), the same rate the
 // direct kernel's random gathers get; fewer requests per key is the only lever.
-// Segments have a fixed capacity sized for "every key survives"; a pair that does not fit (only
+// Segments have a fixed capacity sized for "every key survives"; an entry that does not fit (only
 // for adversarial batches, e.g. one key repeated 1e8 times) is probed directly from HBM where it
 // overflows, so the answer is exact in every case.  The answer per key is the AND of its k bits,
 // exactly as the direct kernel (bloom_kernels.hip) computes it.
@@ -34,23 +36,39 @@
 
 namespace rbx {
 
-// a pair whose segment is full: test its bit in HBM
-__device__ __forceinline__ void bk_direct(unsigned long long e, const uint32_t *__restrict__ bm,
+// The entries [s0, fill) at stride `step` of bucket b's line buffer (at most kBkLineEntries real ones), whose
+// segment is full: decode them (bk_entry.h) and test their bits in HBM
+__device__ __forceinline__ void bk_direct(const unsigned long long *line, uint32_t b, uint32_t s0, uint32_t step,
+                                          uint32_t fill, uint32_t G, const uint32_t *__restrict__ bm,
                                           unsigned long long *__restrict__ miss) {
-    const uint32_t idx = (uint32_t)(e >> 32), key = (uint32_t)e;
-    if ((bm[idx >> 5] & bit_in_word(idx)) == 0u) atomicOr(&miss[key >> 6], 1ULL << (key & 63));
+    const uint32_t *words = (const uint32_t *)line;
+    const uint8_t *his = (const uint8_t *)line + kBkLineHiByte;
+    for (uint32_t s = s0; s < fill; s += step) {
+        const uint32_t w = words[s];
+        const uint32_t idx = (b << kBkBucketBits) | bk_off(w), key = bk_key(bk_q_of(w, his[s]), blockIdx.x, G);
+        if ((bm[idx >> 5] & bit_in_word(idx)) == 0u) atomicOr(&miss[key >> 6], 1ULL << (key & 63));
+    }
+}
+
+// entry (off, q) into slot s < kBkLineEntries of a line buffer: one u32 and one u8 LDS store
+__device__ __forceinline__ void bk_place(unsigned long long *line, uint32_t s, uint32_t off, uint32_t q) {
+    ((uint32_t *)line)[s] = bk_word(off, q);
+    ((uint8_t *)line)[kBkLineHiByte + s] = bk_hi(q);
 }
 
 // K1 -----------------------------------------------------------------------------------
 // Tile = NT * PER keys; a persistent grid of G <= 256 blocks strides over the tiles.  Hash, test
 // bit 0 (one random gather per key), then each of the survivors' k-1 remaining bits takes a slot
-// of its bucket's line buffer (one LDS atomic).  A pair whose slot is past the line stays in its
-// registers until a flush round has stored the line: a round stores every full line (eight lanes
-// per bucket, one 64-byte store each), then the pending pairs move down by one line.  One round
-// per tile is the common case; many pairs of one bucket in one tile (a repeated key) take more.
-// A partial line costs a full write request, and this way only a block's last line per bucket is
-// partial.  Block blk owns segment (b, blk) of every bucket b, so nothing is reserved globally and
-// every block writes its nb counts at its end (segcnt needs no clearing).
+// of its bucket's line buffer (one LDS atomic) and is placed there as a 5-byte entry (bk_entry.h:
+// twelve to a line; the key is the block-local q = tile iteration * 1024 + thread).  An entry whose
+// slot is past the line stays in its registers until a flush round has stored the line: a round
+// stores every full line (eight lanes per bucket copy its eight u64, one 64-byte store; the copy does
+// not interpret entries), then the pending entries move down by one line.  One round per tile is the
+// common case; many entries of one bucket in one tile (a repeated key) take more.  A partial line
+// costs a full write request, and this way only a block's last line per bucket is partial; it is
+// stored whole (the byte plane sits at the line's end), its stale tail is never read as entries: the
+// count says how many are real.  Block blk owns segment (b, blk) of every bucket b, so nothing is
+// reserved globally and every block writes its nb counts at its end (segcnt needs no clearing).
 constexpr uint32_t kBkNoSlot = 0xffffffffu;
 
 template <int KLEN, int KMAX, int NT, int PER>
@@ -62,22 +80,25 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
                                                    unsigned long long *__restrict__ miss, uint32_t flags) {
     if (!kDiag) flags = 0;  // wrong-answer diagnostics exist in the profiling build only (rbx_kernels.h)
     constexpr int TILE = NT * PER, NP = PER * (KMAX - 1);
+    static_assert(TILE == (int)kBkTileKeys, "q = tile iteration * kBkTileKeys + the key's place in the tile");
+    constexpr uint32_t LE = kBkLineEntries, LW = kBkLineWords;
     // 2048 line buffers are 128 KiB, 152 KiB with the counters and lists: one block per CU
-    __shared__ __attribute__((aligned(16))) unsigned long long s_buf[kBkMaxBuckets * kBkLine];
-    __shared__ uint32_t s_fill[kBkMaxBuckets];  // pairs in the bucket's line buffer (and pending past it)
-    __shared__ uint32_t s_out[kBkMaxBuckets];   // pairs of the bucket this block has stored
+    __shared__ __attribute__((aligned(16))) unsigned long long s_buf[kBkMaxBuckets * LW];
+    __shared__ uint32_t s_fill[kBkMaxBuckets];  // entries in the bucket's line buffer (and pending past it)
+    __shared__ uint32_t s_out[kBkMaxBuckets];   // entries of the bucket this block has stored
     // the buckets that hold a full line, for this flush round and the next: the pair that takes a
     // line's last slot lists its bucket, so a round visits full lines only, not all nb buckets
     __shared__ uint16_t s_list[2][kBkMaxBuckets];
     __shared__ uint32_t s_nlist[2];
     const uint64_t ntiles = (nchunk + TILE - 1) / TILE;
-    const uint32_t lane = threadIdx.x & 63, lane8 = threadIdx.x & (kBkLine - 1);
-    // Segment (bucket b, stage-1 block blk) of nb buckets starts at pair (blk * nb + b) * capS.
-    // Block-major: a block's nb segments are adjacent, so its line stores stay inside nb * capS pairs
+    const uint32_t lane = threadIdx.x & 63, lane8 = threadIdx.x & (LW - 1);
+    // Segment (bucket b, stage-1 block blk) of nb buckets starts at line (blk * nb + b) * capS / 12.
+    // Block-major: a block's nb segments are adjacent, so its line stores stay inside nb * capS entries
     // (C2: 23 MB) and the probe reads a region's segments at that stride (bucket-major, a region's
     // segments adjacent, measured slower: DESIGN.md §3.6 r07).
     const uint32_t G = gridDim.x;
-    unsigned long long *seg0 = pairs + blockIdx.x * ((uint64_t)nb * capS);
+    const uint64_t capW = capS / LE * LW;  // a segment in u64
+    unsigned long long *seg0 = pairs + bk_seg_line(0, blockIdx.x, nb, capS) * LW;
     for (uint32_t b = threadIdx.x; b < nb; b += NT) s_fill[b] = s_out[b] = 0;
     if (threadIdx.x < 2) s_nlist[threadIdx.x] = 0;
     uint32_t cur = 0;  // the list the pairs' slots are filling
@@ -118,7 +139,8 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
     };
     if ((uint64_t)blockIdx.x < ntiles) hash_tile(blockIdx.x);
     __syncthreads();
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += G) {
+    uint32_t q0 = threadIdx.x;  // bk_q(tile iteration, thread): the host's chunk rule keeps it below 2^19
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += G, q0 += TILE) {
         const uint64_t t0 = tile * TILE + threadIdx.x;
         uint32_t idx[NP], slot[NP];  // slot: kBkNoSlot = no pair, or the pair is in its line buffer
 #pragma unroll
@@ -138,10 +160,10 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
                     idx[p] = seq.index(mp);
                     const uint32_t b = idx[p] >> kBkBucketBits;
                     const uint32_t s = atomicAdd(&s_fill[b], 1u);
-                    if (s < kBkLine) s_buf[b * kBkLine + s] = w2((uint32_t)t, idx[p]);
+                    if (s < LE) bk_place(s_buf + b * LW, s, idx[p] & kBkOffMask, q0 + q * NT);
                     else slot[p] = s;
-                    // fill was below a line at the tile's start: one pair per bucket and tile gets this slot
-                    if (s == kBkLine - 1) s_list[cur][atomicAdd(&s_nlist[cur], 1u)] = (uint16_t)b;
+                    // fill was below a line at the tile's start: one entry per bucket and tile gets this slot
+                    if (s == LE - 1) s_list[cur][atomicAdd(&s_nlist[cur], 1u)] = (uint16_t)b;
                 }
                 seq.advance(j);
             }
@@ -153,17 +175,17 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
             // eight whole 64-byte lines; a bucket that still holds a full line goes on the next list
             const uint32_t nfull = s_nlist[cur];
             bool more = false;
-            for (uint32_t i = threadIdx.x / kBkLine; i < nfull; i += NT / kBkLine) {
+            for (uint32_t i = threadIdx.x / LW; i < nfull; i += NT / LW) {
                 const uint32_t b = s_list[cur][i];
-                const uint32_t fill = s_fill[b], out = s_out[b];  // fill >= kBkLine
-                const unsigned long long e = s_buf[b * kBkLine + lane8];
-                const bool fits = (uint64_t)out + kBkLine <= capS;
-                if (fits) run_store(e, seg0 + b * capS + out + lane8);
-                else bk_direct(e, bm, miss);
+                const uint32_t fill = s_fill[b], out = s_out[b];  // fill >= LE; out is a multiple of LE
+                const unsigned long long e = s_buf[b * LW + lane8];
+                const bool fits = (uint64_t)out + LE <= capS;
+                if (fits) run_store(e, seg0 + b * capW + out / LE * LW + lane8);
+                else bk_direct(s_buf + b * LW, b, lane8, LW, LE, G, bm, miss);
                 if (lane8 == 0) {  // the eight lanes of a bucket are in one wave: their reads came first
-                    s_fill[b] = fill - kBkLine;
-                    if (fits) s_out[b] = out + kBkLine;
-                    if (fill - kBkLine >= kBkLine) {
+                    s_fill[b] = fill - LE;
+                    if (fits) s_out[b] = out + LE;
+                    if (fill - LE >= LE) {
                         s_list[cur ^ 1][atomicAdd(&s_nlist[cur ^ 1], 1u)] = (uint16_t)b;
                         more = true;
                     }
@@ -171,14 +193,14 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
             }
             // (not read from s_nlist[cur ^ 1]: after the last round the next tile's pairs list there)
             const int again = __syncthreads_or(more);
-            // the stored lines' slots are free: pending pairs move down by one line
+            // the stored lines' slots are free: pending entries move down by one line
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 if (slot[p] != kBkNoSlot) {
-                    slot[p] -= kBkLine;
-                    if (slot[p] < kBkLine) {
-                        const uint32_t key = (uint32_t)(t0 + (p / (KMAX - 1)) * NT);
-                        s_buf[(idx[p] >> kBkBucketBits) * kBkLine + slot[p]] = w2(key, idx[p]);
+                    slot[p] -= LE;
+                    if (slot[p] < LE) {
+                        bk_place(s_buf + (idx[p] >> kBkBucketBits) * LW, slot[p], idx[p] & kBkOffMask,
+                                 q0 + (p / (KMAX - 1)) * NT);
                         slot[p] = kBkNoSlot;
                     }
                 }
@@ -194,14 +216,14 @@ __global__ __launch_bounds__(NT) void k_bk_stage1(KeysDev keys, uint64_t base, u
         }
     }
     __syncthreads();
-    // the block's partial lines (their exact counts: no padding) and its nb segment counts
-    for (uint32_t b = threadIdx.x / kBkLine; b < nb; b += NT / kBkLine) {
-        const uint32_t fill = s_fill[b], out = s_out[b];  // fill < kBkLine
-        const bool fits = (uint64_t)out + kBkLine <= capS;
-        if (lane8 < fill) {
-            const unsigned long long e = s_buf[b * kBkLine + lane8];
-            if (fits) run_store(e, seg0 + b * capS + out + lane8);
-            else bk_direct(e, bm, miss);
+    // the block's partial lines and its nb segment counts.  A partial line is stored whole, all eight u64 (its
+    // byte plane is at its end); the exact count says which of its entries are real, the rest is stale LDS
+    for (uint32_t b = threadIdx.x / LW; b < nb; b += NT / LW) {
+        const uint32_t fill = s_fill[b], out = s_out[b];  // fill < LE
+        const bool fits = (uint64_t)out + LE <= capS;
+        if (fill) {
+            if (fits) run_store(s_buf[b * LW + lane8], seg0 + b * capW + out / LE * LW + lane8);
+            else bk_direct(s_buf + b * LW, b, lane8, LW, fill, G, bm, miss);
         }
         if (lane8 == 0) segcnt[(uint64_t)b * G + blockIdx.x] = out + (fits ? fill : 0u);
     }
@@ -220,12 +242,17 @@ __device__ __forceinline__ void bk_miss_direct(uint32_t key, unsigned long long 
     atomicOr(&miss[key >> 6], 1ULL << (key & 63));
 }
 
-// one pair against the slice in LDS; pairs of the region's other slice are skipped
-__device__ __forceinline__ void bk_test(const uint32_t *s_bm, uint32_t slice, uint32_t key, uint32_t idx,
-                                        unsigned long long *miss, uint32_t *s_mrec, uint32_t *s_mn, uint32_t flags) {
+// One entry against the slice in LDS; entries of the region's other slice are skipped.  The test needs the
+// entry's word alone; on a clear bit the key id is rebuilt from the word, the entry's high byte (bits sh .. sh + 7
+// of hi4), the segment's stage-1 block and the stage-1 grid (bk_entry.h).
+__device__ __forceinline__ void bk_test(const uint32_t *s_bm, uint32_t slice, uint32_t w, uint32_t hi4, uint32_t sh,
+                                        uint32_t blk, uint32_t G, unsigned long long *miss, uint32_t *s_mrec,
+                                        uint32_t *s_mn, uint32_t flags) {
+    const uint32_t idx = bk_off(w);
     if (((idx >> kBkSliceBits) & (kBkCS - 1)) != slice) return;
     const uint32_t off = idx & ((1u << kBkSliceBits) - 1);
     if ((s_bm[off >> 5] & bit_in_word(off)) == 0u) {  // slices are word-aligned: off's low bits = idx's
+        const uint32_t key = bk_key(bk_q_of(w, (hi4 >> sh) & 0xffu), blk, G);
         if (flags & 8) {
             miss[0] = 0;  // diagnostics: one fixed store instead of the miss
         } else if (flags & 16) {
@@ -240,11 +267,22 @@ __device__ __forceinline__ void bk_test(const uint32_t *s_bm, uint32_t slice, ui
 
 // Block bid: x = bid % 8, j = bid / 8; slice = j % 2, cluster = (j / 2) * 8 + x: 128 clusters in a
 // grid of 256.  A cluster walks regions cluster, cluster + nclusters, ...  Wave v of a workgroup reads
-// segments v, v + 16, ... of the region's <= 256 (16 per wave): a lane loads two pairs (16 B) at a
-// time, kBkProbeU loads per segment in flight, and the next segment's loads are issued before the
-// current one's pairs are tested.  Plain loads, not nontemporal ones: the sibling workgroup needs
-// the lines to stay in L2.
-constexpr uint32_t kBkProbeU = 6;  // 768 pairs per segment in one round (C2: ~620)
+// segments v, v + 16, ... of the region's <= 256 (16 per wave): a lane loads 16 B at a time,
+// lane-linear over the segment, so four consecutive lanes hold one line: lanes 0-2 of the quad four
+// entry words each, lane 3 the byte plane.  All four lanes test three entries: lanes 0-2 their first
+// three words, with their high bytes from lane 3 (three quad-broadcast DPP moves); lane 3 the fourth
+// word of lanes 0, 1 and 2 (three more), whose high bytes it holds.  The moves stand outside any branch.
+// (Lanes 0-2 testing four words each left a quarter of the lanes of every LDS gather idle: 0.86 ms against
+// 0.76; the parent's 8-byte pairs: 0.71.  The probe's time follows the tests a wave issues, not the bytes
+// it loads: DESIGN.md 3.6 r09 has the variants.)  kBkProbeU loads per segment are in flight (16 lines
+// each), and the next segment's loads are issued before the current one's entries are tested.  Plain loads,
+// not nontemporal ones: the sibling workgroup needs the lines to stay in L2.
+constexpr uint32_t kBkProbeU = 4;  // 768 entries (64 lines) per segment in one round (C2: ~620); 5 and 6 spill
+
+// lane L of the caller's quad's value of v
+template <int L> __device__ __forceinline__ uint32_t bk_quad(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, L * 0x55 /* quad_perm [L,L,L,L] */, 0xf, 0xf, true);
+}
 
 template <bool STAMP>
 __global__ __launch_bounds__(1024) void k_bk_probe(const unsigned long long *__restrict__ pairs,
@@ -288,23 +326,36 @@ __global__ __launch_bounds__(1024) void k_bk_probe(const unsigned long long *__r
         const uint32_t *rcnt = segcnt + (uint64_t)r * G;
         uint32_t cntv = 0;
         if (lane < nsw) cntv = (uint32_t)min<uint64_t>(rcnt[wave + NW * lane], capS);
-        // capS is a multiple of 8 pairs: every segment is 64-byte aligned
-        const unsigned long long *rseg = pairs + r * capS;
-        auto seg = [&](uint32_t i) { return (const u32x4 *)(rseg + (wave + NW * i) * ((uint64_t)nb * capS)); };
+        // capS is a multiple of 12 entries: a segment is whole 64-byte lines, four 16-byte loads each.  n
+        // entries are ceil(n / 12) lines; the last one's tail past n is stale and is not tested
+        auto seg = [&](uint32_t i) {
+            return (const u32x4 *)(pairs + bk_seg_line(r, wave + NW * i, nb, capS) * kBkLineWords);
+        };
         auto load = [&](u32x4 (&v)[U], const u32x4 *src, uint32_t n, uint32_t q0) {
+            const uint32_t nq = (n + kBkLineEntries - 1) / kBkLineEntries * 4;
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) {
                 const uint32_t q = q0 + u * 64 + lane;
-                if (2 * q < n) v[u] = src[q];
+                if (q < nq) v[u] = src[q];
             }
         };
-        auto test = [&](const u32x4 (&v)[U], uint32_t n, uint32_t q0) {
+        auto test = [&](const u32x4 (&v)[U], uint32_t n, uint32_t q0, uint32_t blk) {
+            const uint32_t sub = lane & 3;
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) {
-                const uint32_t q = q0 + u * 64 + lane;
-                if (2 * q < n) {  // a pair is key id (low word), bit index (high word)
-                    bk_test(s_bm, slice, v[u].x, v[u].y, miss, s_mrec, &s_mn, flags);
-                    if (2 * q + 1 < n) bk_test(s_bm, slice, v[u].z, v[u].w, miss, s_mrec, &s_mn, flags);
+                // the quad's lane 3 holds the line's byte plane: .x entries 0-3, .y 4-7, .z 8-11
+                const uint32_t h0 = bk_quad<3>(v[u].x), h1 = bk_quad<3>(v[u].y), h2 = bk_quad<3>(v[u].z);
+                const uint32_t w3 = bk_quad<0>(v[u].w), w7 = bk_quad<1>(v[u].w), w11 = bk_quad<2>(v[u].w);
+                const bool last = sub == 3;  // lane 3 tests entries 3, 7, 11; lane s < 3 entries 4s, 4s + 1, 4s + 2
+                const uint32_t hi4 = sub == 0 ? h0 : sub == 1 ? h1 : h2;
+                const uint32_t e0 = (q0 + u * 64 + lane) / 4 * kBkLineEntries + (last ? 3 : sub * 4), de = last ? 4 : 1;
+                const uint32_t wa = last ? w3 : v[u].x, wb = last ? w7 : v[u].y, wc = last ? w11 : v[u].z;
+                const uint32_t ha = last ? h0 : hi4, hb = last ? h1 : hi4, hc = last ? h2 : hi4;
+                const uint32_t sa = last ? 24 : 0, sb = last ? 24 : 8, sc = last ? 24 : 16;
+                if (e0 < n) {
+                    bk_test(s_bm, slice, wa, ha, sa, blk, G, miss, s_mrec, &s_mn, flags);
+                    if (e0 + de < n) bk_test(s_bm, slice, wb, hb, sb, blk, G, miss, s_mrec, &s_mn, flags);
+                    if (e0 + 2 * de < n) bk_test(s_bm, slice, wc, hc, sc, blk, G, miss, s_mrec, &s_mn, flags);
                 }
             }
         };
@@ -321,10 +372,10 @@ __global__ __launch_bounds__(1024) void k_bk_probe(const unsigned long long *__r
                 nnxt = __builtin_amdgcn_readlane(cntv, i + 1);
                 load(nxt, seg(i + 1), nnxt, 0);
             }
-            test(cur, ncur, 0);
-            for (uint32_t q0 = U * 64; 2 * q0 < ncur; q0 += U * 64) {  // a segment longer than one round
+            test(cur, ncur, 0, wave + NW * i);
+            for (uint32_t q0 = U * 64; q0 / 4 * kBkLineEntries < ncur; q0 += U * 64) {  // a segment longer than one round
                 load(cur, seg(i), ncur, q0);
-                test(cur, ncur, q0);
+                test(cur, ncur, q0, wave + NW * i);
             }
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) cur[u] = nxt[u];
@@ -446,7 +497,7 @@ static unsigned grid_for_pc(uint64_t n) {
 // Shapes: stage 1 at 1024 threads with one key per thread (1024-key tiles, kBkTileKeys), 152 KiB
 // of LDS, one block per CU; the probe at 1024 threads, one workgroup per CU (a 128 KiB slice + the
 // miss buffers), in whole groups of 8 clusters.  The A/Bs (region size, tile size, segment layout)
-// are in DESIGN.md §3.6 r07 and r08.
+// are in DESIGN.md §3.6 r07 and r08, the entry format's in r09.
 template <int KLEN, int KMAX>
 static void bk_chunk(const PcArgs &a, hipStream_t st) {
     static_assert(kBkTileKeys == 1024, "the stage-1 tile is the block: one key per thread");

@@ -296,6 +296,7 @@ struct TuneRow {
 static constexpr int kSegMax = (int)kSegMaxKeys, kIntMax = 0x7fffffff;
 static const TuneRow kTuneRows[] = {
     {"contains_partition", RANGE(0, 2), false, FIELD(partition_mode)},
+    {"contains_stage1_grid", RANGE(1, 256), false, FIELD(stage1_grid)},
     // DIAGNOSTICS ONLY (tools/microbench.py pflags / padiag through RBX_LIB_PATH): they change answers
     {"contains_partition_flags", ONE_OF(0, 4, 8, 12, 16, 32, 64), true, FIELD(partition_flags)},
     {"add_partition_diag", BITS(4 | 8 | 16 | 64), true, FIELD(add_partition_diag)},

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/rbx.h"
+#include "bk_entry.h"
 #include "rbx_device.h"
 
 namespace rbx {
@@ -128,7 +129,7 @@ void set_contains_qgrid(int v);   // slot contains kernel grid (blocks)
 // ---- contains_partitioned.hip
 // One chunk of keys against one filter, one radix pass.  Stage 1 buckets pairs by 2^21-bit (256 KiB)
 // bitmap region; the probe holds one 2^20-bit (128 KiB) slice of a region in LDS (bucket_common.h).
-constexpr uint32_t kBkTileKeys = 1024;  // keys per stage-1 tile: 1024 threads, one key each
+// The stage-1 tile (kBkTileKeys), grid and the 5-byte entry format are bk_entry.h's.
 constexpr int kBkMissRangeBits = 19;   // probe misses are bucketed by 2^19-key range (64 KiB LDS bitmap)
 struct PcArgs {
     KeysDev keys;
@@ -137,11 +138,12 @@ struct PcArgs {
     ModParams mp;
     uint32_t k;
     uint32_t nb;            // regions (stage-1 buckets) = ceil(size / 2^21) <= 2048
-    uint32_t grid1;         // stage-1 blocks G = min(tiles of the chunk, 256); every block owns a segment per bucket
-    uint64_t capS;          // pair capacity of one segment, a multiple of 8
+    uint32_t grid1;         // stage-1 blocks G = min(tiles of the chunk, 256 or "contains_stage1_grid"); every block owns a
+                            // segment per bucket, and nchunk <= G * 2^19 (a block-local key index fits 19 bits)
+    uint64_t capS;          // entry capacity of one segment, a multiple of 12 (whole 64-byte lines)
     uint64_t nwords4;       // bitmap words rounded up to a multiple of 4
-    unsigned long long *pairs;  // nb * G segments of capS pairs (bit index << 32 | key id): segment (b, blk) at (blk*nb + b) * capS
-    uint32_t *segcnt;       // nb * G pair counts, all written by stage 1
+    unsigned long long *pairs;  // nb * G segments of capS / 12 lines of 12 entries (bk_entry.h): segment (b, blk) at line (blk*nb + b) * capS / 12
+    uint32_t *segcnt;       // nb * G entry counts, all written by stage 1
     unsigned long long *alive;  // ceil(nchunk/64)
     unsigned long long *miss;   // ceil(nchunk/64), zeroed
     uint32_t *mrec;         // nmranges * capm: key ids of the probe's clear bits, by 2^19-key range

@@ -30,6 +30,9 @@ struct Tunables {
     // "contains_partition_flags" (profiling build only): 4 = stage 1 emits no pairs, 8 = the probe records
     // no misses, 16 = one atomicOr per clear bit, 32 = no bit-0 gather, 64 = phase stamps
     std::atomic<int> partition_flags{0};
+    // "contains_stage1_grid": caps the partitioned contains' stage-1 grid (default 256, one block per CU).  A chunk
+    // holds at most grid * 2^19 keys (bk_entry.h), so tests reach a block's 512th tile on a small batch
+    std::atomic<uint32_t> stage1_grid{256};
 
     // "wide_subchunk": bloom_wide_op's keys per sub-chunk cap (0 = default 2^29 / k; tests split small batches)
     std::atomic<uint64_t> wide_subchunk{0};
