@@ -515,12 +515,63 @@ int rbx_bitset_pos_of(const uint8_t *bytes, uint64_t len, int missing, int bit, 
  *             Failed groups, and groups whose sources are all missing or empty, are answered on the host
  *             (DESIGN 11.9).
  *   Scope     no handle form, no _dev form; the node router and the Java shim do not carry this call.  Ranged
- *             BITCOUNT stays rbx_bitset_count_ranges'.
+ *             BITCOUNT is rbx_bitset_count_ranges' on one key and rbx_bitset_range_stream's over many.
  * All arrays are host memory: the host must know the keys to create the destinations. */
 #define RBX_BITGROUP_NO_DEST 0xFFFFFFFFu
 int rbx_bitset_op_groups(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint8_t *grp_op,
                          const uint32_t *grp_dest, const uint64_t *grp_off, const uint32_t *grp_key, uint32_t ngroups,
                          uint64_t *lens, uint64_t *counts, uint8_t *status);
+/* The read queries over many keys in one call: ranged and whole-string BITCOUNT, BITPOS, STRLEN and
+ * RBitSet.length()'s script, one command per entry, each on its own key -- the per-entity bitmap workload (one
+ * short string per user, "active days in the last 30" = BITCOUNT user:i -30 -1 BIT for every user at once), what
+ * RBatch.getBitSet(name).sizeAsync / lengthAsync / bitCountAsync / bitPosAsync queue and Spring Data's
+ * bitCount(key, begin, end) / bitPos / strLen send between openPipeline() and closePipeline().
+ *   Commands  command i runs on names[cmd_key[i]].  RBX_RANGE_COUNT with nargs 0 is BITCOUNT key
+ *             (rbx_bitset_cardinality), with nargs 2 BITCOUNT key start end unit (rbx_bitset_count_range);
+ *             RBX_RANGE_POS is rbx_bitset_pos(bit, nargs, start, end, unit); RBX_RANGE_STRLEN is the string's
+ *             length in bytes (rbx_bitset_size is 8 times that); RBX_RANGE_LENGTH is rbx_bitset_length, the script
+ *             of RBitSet.length(), which looks at the first and the last byte only.  start / end / bit / unit are
+ *             ignored where the command or nargs does not use them.  Two entries of `names` with equal bytes are
+ *             one key.
+ *   Result    exactly that of n single calls: replies[i] is what call i returns, status[i] is 0 for a command that
+ *             ran and 0xFF, with replies[i] = 0, for one that failed alone.  replies and status are nullable.  The
+ *             commands only read: nothing is created, grown or touched, key timeouts included, and the order
+ *             between commands is immaterial.  A missing key answers as the single calls do: COUNT 0, POS -1 for
+ *             bit 1 and 0 for bit 0, STRLEN 0, LENGTH what rbx_bitset_length gives (the script fails).
+ *   Failures  the pipelined-batch rule of RBX_E_REDIS above: a command fails alone and every other command gets
+ *             its exact reply.  A POS command fails when its bit is not 0 / 1 (RBX_E_REDIS "ERR The bit argument
+ *             must be 1 or 0.") or its unit is RBX_RANGE_BIT with nargs < 2 (RBX_E_REDIS "ERR syntax error"); any
+ *             command fails when its key holds another type (RBX_E_WRONGTYPE, HLL keys included) -- looked at in
+ *             that order, as the single calls do; a LENGTH command fails when the script fails (RBX_E_REDIS, as
+ *             rbx_bitset_length reports it), the one failure that depends on data.  The call returns the code of
+ *             the first failing command in array order with its message in rbx_last_error().
+ *   Caller    cmd_key[i] >= nkeys, an op above RBX_RANGE_LENGTH, a unit above RBX_RANGE_BIT, nargs above 2,
+ *             RBX_RANGE_COUNT with nargs 1, or a NULL names / cmd_key / cmds with n > 0 is
+ *             RBX_E_ILLEGAL_ARGUMENT; replies and status are then unspecified.  n = 0 sends nothing.
+ *   Cost      each distinct name is looked up once.  One kernel gives every command a group of rbx_tune
+ *             "rangestream_lanes" lanes, which answers it when its interval covers at most "rangestream_short_max"
+ *             bytes; longer intervals are cut into tiles of "rangestream_tile" bytes that the whole device sweeps
+ *             in a second launch, so no lane group walks a long string alone.  The _dev form waits once on the
+ *             stream, for the call's summary (the caller's errors, the first failures, the number of long
+ *             commands); the host form uploads the commands, makes at most two waits and copies replies and
+ *             status back.  More than "rangestream_chunk" commands run as consecutive chunks, each with its own
+ *             summary and wait.
+ *   Scope     no handle form; the node router and the Java shim do not carry this call.
+ * `names` is host memory in both forms; the _dev form takes device arrays and enqueues on `stream`. */
+enum { RBX_RANGE_COUNT = 0, RBX_RANGE_POS = 1, RBX_RANGE_STRLEN = 2, RBX_RANGE_LENGTH = 3 };
+typedef struct {
+    int64_t start, end;           /* as rbx_bitset_count_range / rbx_bitset_pos; ignored where nargs says so */
+    uint8_t op, bit, nargs, unit; /* RBX_RANGE_*, 0 / 1 (POS), 0 / 1 / 2, RBX_RANGE_BYTE / _BIT */
+    uint8_t pad[4];
+} rbx_range_cmd; /* 24 bytes */
+int rbx_bitset_range_stream(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                            const rbx_range_cmd *cmds, uint64_t n, int64_t *replies, uint8_t *status);
+int rbx_bitset_range_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                                const rbx_range_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
+                                void *stream);
+/* one command over a host string, no context (as rbx_bitset_count_of / _pos_of / _length_of); missing != 0 = a
+ * missing key.  Returns what the single call returns, *reply = 0 when it fails. */
+int rbx_bitset_range_of(const uint8_t *bytes, uint64_t len, int missing, const rbx_range_cmd *cmd, int64_t *reply);
 
 /* ---- replicas ("replicate the bitmap, split contains keys across GPUs") ---------
  * Redisson serves contains' GETBITs as reads that may go to a replica

@@ -60,6 +60,9 @@ int rbx_bench_hllgroups_last(uint32_t out[4]);
 /* What the last rbx_bitset_op_groups call of this process did: out[0] = phases, out[1] = sweep launches, out[2] = the
  * tile bytes of the last of them (0: none), out[3] = groups that reached the device. */
 int rbx_bench_bitgroups_last(uint32_t out[4]);
+/* What the last rbx_bitset_range_stream[_dev] call of this process did: out[0] = commands the group kernel finished,
+ * out[1] = long commands (their intervals went to the tiles), out[2] = tiles, out[3] = waits on the stream. */
+int rbx_bench_rangestream_last(uint32_t out[4]);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -164,6 +167,15 @@ int rbx_bench_bitgroups_last(uint32_t out[4]);
  *   "bitgroups_tile"        rbx_bitset_op_groups: the bytes of a tile of the segmented sweep, 0 auto (default: the
  *                           largest power of two in 4 KiB .. 64 KiB that still gives a launch 2048 tiles), else a
  *                           power of two in 4 KiB .. 1 MiB; every setting gives the same answers
+ *   "rangestream_lanes"     rbx_bitset_range_stream: the lanes of the group that answers one command, 4, 8, 16, 32
+ *                           or 64 (default 16; within 1 % of every other setting on short strings); every setting gives
+ *                           the same answers
+ *   "rangestream_short_max" bytes of the longest interval a lane group walks alone, a power of two in 64 .. 1 MiB
+ *                           (default 4096, a guess no measurement decides); a longer one is cut into tiles
+ *   "rangestream_tile"      bytes of a tile of a long interval, a power of two in 4 KiB .. 1 MiB (default 65536,
+ *                           the large-work optimum of bitgroups_tile's table and of DESIGN 11.10 row e)
+ *   "rangestream_chunk"     commands per chunk, 1 .. 2^30 (default 2^25: 8 bytes of long list per command); each
+ *                           chunk has its own summary and wait
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

@@ -4,7 +4,8 @@ structures (RBloomFilter / RHyperLogLog), behind a C ABI (include/rbx.h, librbx.
 Host mirror of the reference API: RedissonClient.getBloomFilter / getHyperLogLog / getBitSet / createBatch.
 """
 from .client import (BatchResult, BloomHandle, RBatch, RBitSet, RBloomFilter, RedissonClient, RHyperLogLog,
-                     bitset_op_groups_call, bitset_field_stream, bitset_field_stream_dev, bitset_stream, bitset_stream_dev, bloom_add_multi, bloom_stream, bloom_contains_multi, calc_slot,
+                     bitset_op_groups_call, bitset_range_stream, bitset_range_stream_call, bitset_range_stream_dev,
+                     bitset_field_stream, bitset_field_stream_dev, bitset_stream, bitset_stream_dev, bloom_add_multi, bloom_stream, bloom_contains_multi, calc_slot,
                      crc16, hll_add_multi, hll_count_each, hll_count_groups, hll_count_groups_call, hll_merge_groups,
                      hll_merge_groups_call, hll_stream, hll_stream_call, hll_stream_dev, slot_to_gpu)
 from .codec import ByteArrayCodec, StringCodec
@@ -20,5 +21,6 @@ __all__ = [
     "RedisException", "Redisson", "RedissonClient", "StringCodec", "UnsupportedOperationException",
     "bitset_field_stream", "bitset_field_stream_dev", "bitset_stream", "bitset_stream_dev", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
     "hll_add_multi", "hll_count_each", "hll_count_groups", "hll_count_groups_call", "hll_merge_groups",
-    "hll_merge_groups_call", "bitset_op_groups_call", "hll_stream", "hll_stream_call", "hll_stream_dev", "slot_to_gpu",
+    "hll_merge_groups_call", "bitset_op_groups_call", "bitset_range_stream", "bitset_range_stream_call",
+    "bitset_range_stream_dev", "hll_stream", "hll_stream_call", "hll_stream_dev", "slot_to_gpu",
 ]

@@ -75,6 +75,7 @@ RBX_BITOP_AND, RBX_BITOP_OR, RBX_BITOP_XOR, RBX_BITOP_NOT = 0, 1, 2, 3
 RBX_BITGROUP_NO_DEST = 0xFFFFFFFF  # rbx_bitset_op_groups: the group stores its result nowhere
 RBX_FIELD_GET, RBX_FIELD_SET, RBX_FIELD_INCRBY = 0, 1, 2
 RBX_RANGE_BYTE, RBX_RANGE_BIT = 0, 1
+RBX_RANGE_COUNT, RBX_RANGE_POS, RBX_RANGE_STRLEN, RBX_RANGE_LENGTH = 0, 1, 2, 3  # op of rbx_range_cmd
 RBX_OVERFLOW_WRAP, RBX_OVERFLOW_SAT, RBX_OVERFLOW_FAIL = 0, 1, 2
 RBX_HLL_PFADD, RBX_HLL_PFCOUNT = 0, 1  # cmd_op of rbx_hll_stream
 
@@ -84,6 +85,14 @@ class RbxFieldCmd(C.Structure):
 
     _fields_ = [("offset", C.c_uint64), ("value", C.c_int64), ("op", C.c_uint8), ("is_signed", C.c_uint8),
                 ("size", C.c_uint8), ("overflow", C.c_uint8), ("pad", C.c_uint8 * 4)]
+
+
+class RbxRangeCmd(C.Structure):
+    """struct rbx_range_cmd {start, end, op, bit, nargs, unit, pad[4]}: 24 bytes"""
+
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("op", C.c_uint8), ("bit", C.c_uint8),
+                ("nargs", C.c_uint8), ("unit", C.c_uint8), ("pad", C.c_uint8 * 4)]
+
 
 # name -> (restype, argtypes); every function declared in include/rbx.h
 SIGNATURES = {
@@ -237,6 +246,10 @@ SIGNATURES = {
     "rbx_bitset_size": (C.c_int, [vp, RbxName, u64p]),
     "rbx_bitset_length": (C.c_int, [vp, RbxName, C.POINTER(C.c_int64)]),
     "rbx_bitset_length_of": (C.c_int, [u8p, C.c_uint64, C.POINTER(C.c_int64)]),
+    "rbx_bitset_range_stream": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, C.POINTER(RbxRangeCmd), C.c_uint64,
+                                          i64p, u8p]),
+    "rbx_bitset_range_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp]),
+    "rbx_bitset_range_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.POINTER(RbxRangeCmd), C.POINTER(C.c_int64)]),
     "rbx_bitset_export_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64, u64p]),
     "rbx_bitset_import_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64]),
     "rbx_bitset_rename": (C.c_int, [vp, RbxName, RbxName]),
@@ -270,6 +283,7 @@ SIGNATURES = {
     "rbx_bench_hllstream_last": (C.c_int, [u32p]),
     "rbx_bench_hllgroups_last": (C.c_int, [u32p]),
     "rbx_bench_bitgroups_last": (C.c_int, [u32p]),
+    "rbx_bench_rangestream_last": (C.c_int, [u32p]),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

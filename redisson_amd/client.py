@@ -64,7 +64,7 @@ class RedissonClient:
 
     def createBatch(self) -> "RBatch":
         """M/api/RedissonClient.java createBatch()"""
-        return RBatch(self)
+        return RBatch(self, range_stream_call=lambda *a: _engine_bitset_range_stream_call(self, *a))
 
     def shutdown(self) -> None:
         if self._ctx:
@@ -996,6 +996,53 @@ def bitset_op_groups_call(client: RedissonClient, names, ops, dests, groups):
 
 _engine_bitset_op_groups_call = bitset_op_groups_call
 
+RANGE_FAILED = 0xFF  # status of a command of rbx_bitset_range_stream that failed alone
+
+
+def _range_cmds_array(rows):
+    """rows of (op, bit, nargs, start, end, unit) -> an array of rbx_range_cmd"""
+    arr = (L.RbxRangeCmd * max(len(rows), 1))()
+    for a, (op, bit, nargs, start, end, unit) in zip(arr, rows):
+        a.op, a.bit, a.nargs, a.start, a.end, a.unit = op, bit, nargs, start, end, unit
+    return arr
+
+
+def bitset_range_stream_call(client: RedissonClient, names, cmd_key, rows):
+    """rbx_bitset_range_stream over host arrays without raising: (rc, message, replies, status).  Command i runs on
+    names[cmd_key[i]]; rows: (op, bit, nargs, start, end, unit) with RBX_RANGE_* codes, or an array of RbxRangeCmd.
+    replies: int64, what the single calls return; status: uint8 with 0 = the command ran, 0xFF = it failed alone."""
+    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+    arr = rows if isinstance(rows, C.Array) else _range_cmds_array(list(rows))
+    n = key.size
+    if len(arr) < n or (not isinstance(rows, C.Array) and len(rows) != n):
+        raise IllegalArgumentException("cmd_key and rows have one entry per command")
+    names_arr, _keep = L.names_array(names)
+    out, status = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint8)
+    rc = L.lib().rbx_bitset_range_stream(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p), arr, n,
+                                         out.ctypes.data_as(L.i64p), status.ctypes.data_as(L.u8p))
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), out[:n], status[:n]
+
+
+def bitset_range_stream(client: RedissonClient, names, cmd_key, rows):
+    """BITCOUNT / BITPOS / STRLEN / length() commands over many keys in one call (rbx_bitset_range_stream):
+    (replies, status) in order.  Raises the first failing command's exception after every other command ran."""
+    rc, msg, out, status = bitset_range_stream_call(client, names, cmd_key, rows)
+    raise_for(rc, msg)
+    return out, status
+
+
+def bitset_range_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmds: int, n: int,
+                            d_replies: int | None = None, d_status: int | None = None,
+                            stream: int | None = None) -> None:
+    """bitset_range_stream over device arrays (u32 keys, 24-byte rbx_range_cmd records, i64 replies, u8 status),
+    enqueued on `stream`."""
+    arr, _keep = L.names_array(names)
+    _check(L.lib().rbx_bitset_range_stream_dev(client.ctx, arr, len(names), d_cmd_key, d_cmds, int(n), d_replies,
+                                               d_status, stream))
+
+
+_engine_bitset_range_stream_call = bitset_range_stream_call
+
 
 class BatchFuture:
     """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
@@ -1029,14 +1076,17 @@ class _Queued:
     its like where the grouped call is at hand and runs through fn otherwise, a BITOP or whole-string BITCOUNT
     (bitop = (RBX_BITOP_*, destination or None, [sources]), fn; convert(length, count) is its reply) that coalesces
     with its like where the grouped bit call is at hand and runs through fn otherwise, or a callable that runs
-    singly.  convert: applied to a field or HLL command's reply."""
+    singly.  A read query (range = (RBX_RANGE_*, bit, nargs, start, end, unit), fn; convert(reply) is its reply)
+    coalesces with its like where the range stream call is at hand and runs through fn otherwise; a whole-string
+    BITCOUNT carries both a bitop and a range row.  convert: applied to a field or HLL command's reply."""
 
-    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group", "bitop")
+    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group", "bitop", "range")
 
     def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None, group=None,
-                 bitop=None):
+                 bitop=None, range=None):  # noqa: A002
         self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
         self.field, self.convert, self.hll, self.group, self.bitop = field, convert, hll, group, bitop
+        self.range = range
 
     def as_field(self):
         """the command as a BITFIELD sub-command: GETBIT / SETBIT are GET / SET of a u1, which leave the same
@@ -1145,8 +1195,42 @@ def _settle_bitop(c: _Queued, reply, status) -> None:
         c.future._set(c.convert(int(reply[0]), int(reply[1])))
 
 
+_RANGE_BIT_MSG = "ERR The bit argument must be 1 or 0."
+_WRONGTYPE_MSG = "WRONGTYPE Operation against a key holding the wrong kind of value"
+
+
+def _range_row(op: int, bit: int = 0, nargs: int = 0, start: int = 0, end: int = 0, unit: int = L.RBX_RANGE_BYTE):
+    """one row of bitset_range_stream_call; a bit outside a byte is as wrong as 2"""
+    return (op, bit if 0 <= bit <= 255 else 2, nargs, start, end, unit)
+
+
+def _settle_range(c: _Queued, reply, status) -> None:
+    """a read query of a range run; a failure is worked out in the order of the single calls: BITPOS's bit, its
+    unit without an end, then the key's type.  A failed length() has either the wrong type or a failing script,
+    which the status does not tell apart: its own call, which only reads, says which."""
+    if int(status) != RANGE_FAILED:
+        # a whole-string BITCOUNT keeps the converter of its bitop row: convert(length, count)
+        c.future._set(c.convert(0, int(reply)) if c.bitop is not None else
+                      c.convert(int(reply)) if c.convert else int(reply))
+        return
+    op, bit, nargs, _start, _end, unit = c.range
+    if op == L.RBX_RANGE_POS and bit > 1:
+        msg = _RANGE_BIT_MSG
+    elif op == L.RBX_RANGE_POS and nargs < 2 and unit == L.RBX_RANGE_BIT:
+        msg = "ERR syntax error"
+    elif op == L.RBX_RANGE_LENGTH:
+        try:
+            c.future._set(c.fn())
+        except RedissonAmdError as e:
+            c.future._set(error=e)
+        return
+    else:
+        msg = _WRONGTYPE_MSG
+    c.future._set(error=RedisException(msg))
+
+
 def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, hll_count_groups_call=None,
-              hll_merge_groups_call=None, bit_groups_call=None):
+              hll_merge_groups_call=None, bit_groups_call=None, range_stream_call=None):
     """Executes queued commands in submission order.  Every maximal run of consecutive bit commands, over any
     keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies).  With a
     field_stream_call, field commands join the runs, and a run that holds at least one of them is ONE
@@ -1159,7 +1243,11 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
     ONE hll_merge_groups_call(names, dests, groups) -> (rc, message, status).  With a bit_groups_call, every maximal
     run of consecutive BITOPs and whole-string BITCOUNTs, over any keys, is ONE bit_groups_call(names, ops, dests,
     groups) -> (rc, message, lens, counts, status), a BITCOUNT travelling as a one-source OR without a destination.
-    A count run, a merge run, an HLL stream run, a grouped bit run and a bit / field run each close the others.
+    With a range_stream_call, every maximal run of consecutive read queries (ranged and whole-string BITCOUNT,
+    BITPOS, STRLEN, length()), over any keys, is ONE range_stream_call(names, cmd_key, rows) -> (rc, message,
+    replies, status); a whole-string BITCOUNT joins an open range run and otherwise starts a grouped bit run as
+    before.  A count run, a merge run, an HLL stream run, a grouped bit run, a range run and a bit / field run each
+    close the others.
     Every other command runs through its own call at its position.  Each command's future is set; returns
     (responses, first error)."""
     def joins(q):
@@ -1176,6 +1264,12 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
 
     def joins_bitops(q):
         return q.bitop is not None and bit_groups_call is not None
+
+    def joins_ranges(q):
+        return q.range is not None and range_stream_call is not None
+
+    def starts_ranges(q):  # a whole-string BITCOUNT starts a grouped bit run where that call is at hand
+        return joins_ranges(q) and not joins_bitops(q)
 
     def run_from(i, belongs):
         """the maximal run of commands from queue[i] on that belong together"""
@@ -1210,6 +1304,9 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
         rc, msg, lens, counts, status = bit_groups_call(list(ids), [c.bitop[0] for c in run], dests, groups)
         return rc, msg, list(zip(lens, counts)), status
 
+    def ranges_call(run, names, keys):
+        return range_stream_call(names, keys, [c.range for c in run])
+
     def field_call(run, names, keys):
         return field_stream_call(names, keys, [c.as_field() for c in run])
 
@@ -1230,6 +1327,9 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
         elif joins_merges(queue[i]):
             run = run_from(i, joins_merges)
             error = _run_stream(run, merges_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_group)
+        elif starts_ranges(queue[i]):
+            run = run_from(i, joins_ranges)
+            error = _run_stream(run, ranges_call, alone, _settle_range)
         elif joins_bitops(queue[i]):
             run = run_from(i, joins_bitops)
             error = _run_stream(run, bitops_call, alone, _settle_bitop)
@@ -1369,13 +1469,40 @@ class RBatchBitSet:
         """:482-484 BITCOUNT: a one-source OR without a destination of the grouped call"""
         bitset, name = self._batch._bitset, self._name
         return self._batch._add(_Queued(name, fn=lambda: bitset(name).cardinality(),
-                                        bitop=(L.RBX_BITOP_OR, None, [name]), convert=lambda _length, count: count))
+                                        bitop=(L.RBX_BITOP_OR, None, [name]), convert=lambda _length, count: count,
+                                        range=_range_row(L.RBX_RANGE_COUNT)))
+
+    def _range(self, method: str, args: tuple, row: tuple, convert=None) -> BatchFuture:
+        """a read query: consecutive ones, over any keys, travel together in one rbx_bitset_range_stream call"""
+        bitset, name = self._batch._bitset, self._name
+        return self._batch._add(_Queued(name, fn=lambda: getattr(bitset(name), method)(*args), range=row,
+                                        convert=convert))
 
     def sizeAsync(self) -> BatchFuture:
-        return self._single("size")
+        """:472-474 STRLEN * 8"""
+        return self._range("size", (), _range_row(L.RBX_RANGE_STRLEN), lambda length: 8 * length)
 
     def lengthAsync(self) -> BatchFuture:
-        return self._single("length")
+        return self._range("length", (), _range_row(L.RBX_RANGE_LENGTH))
+
+    def bitCountAsync(self, start: int | None = None, end: int | None = None, unit="BYTE") -> BatchFuture:
+        """Engine extension, RBitSet.bitCount queued: BITCOUNT name [start end [BYTE|BIT]]"""
+        if start is None and end is None:
+            return self.cardinalityAsync()
+        if start is None or end is None:
+            raise IllegalArgumentException("BITCOUNT takes both start and end, or neither")
+        row = _range_row(L.RBX_RANGE_COUNT, 0, 2, RBitSet._java(start, 64, "start"), RBitSet._java(end, 64, "end"),
+                         RBitSet._unit(unit))
+        return self._range("bitCount", (start, end, unit), row)
+
+    def bitPosAsync(self, bit, start: int | None = None, end: int | None = None, unit="BYTE") -> BatchFuture:
+        """Engine extension, RBitSet.bitPos queued: BITPOS name bit [start [end [BYTE|BIT]]]"""
+        if start is None and end is not None:
+            raise IllegalArgumentException("BITPOS takes an end only after a start")
+        nargs = 0 if start is None else (1 if end is None else 2)
+        row = _range_row(L.RBX_RANGE_POS, RBitSet._java(int(bit), 32, "bit"), nargs,
+                         RBitSet._java(start or 0, 64, "start"), RBitSet._java(end or 0, 64, "end"), RBitSet._unit(unit))
+        return self._range("bitPos", (bit, start, end, unit), row)
 
     def toByteArrayAsync(self) -> BatchFuture:
         return self._single("toByteArray")
@@ -1430,6 +1557,8 @@ class RBatchBitSet:
     cardinality_async = cardinalityAsync
     size_async = sizeAsync
     length_async = lengthAsync
+    bit_count_async = bitCountAsync
+    bit_pos_async = bitPosAsync
     to_byte_array_async = toByteArrayAsync
     or_async = orAsync
     and_async = andAsync
@@ -1489,11 +1618,13 @@ class RBatch:
     in that order.  stream_call / bitset / field_stream_call / hll_stream_call / hyperloglog /
     hll_count_groups_call / hll_merge_groups_call / bit_groups_call replace the engine's calls (tests); without a
     client and without a field_stream_call (an hll_stream_call, a grouped call), field (HLL, multi-key PFCOUNT /
-    PFMERGE, BITOP / BITCOUNT) commands run singly through bitset(name) (hyperloglog(name, codec))."""
+    PFMERGE, BITOP / BITCOUNT) commands run singly through bitset(name) (hyperloglog(name, codec)).
+    range_stream_call carries the read queries (size / length / bitCount / bitPos); createBatch() passes the
+    engine's, and without one they run singly."""
 
     def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None, field_stream_call=None,
                  hll_stream_call=None, hyperloglog=None, hll_count_groups_call=None, hll_merge_groups_call=None,
-                 bit_groups_call=None):
+                 bit_groups_call=None, range_stream_call=None):
         self._client = client
         self._stream_call = stream_call or (lambda *a: bitset_stream_call(client, *a))
         if field_stream_call is None and client is not None:
@@ -1510,6 +1641,7 @@ class RBatch:
         if bit_groups_call is None and client is not None:
             bit_groups_call = lambda *a: _engine_bitset_op_groups_call(client, *a)  # noqa: E731
         self._bit_groups_call = bit_groups_call
+        self._range_stream_call = range_stream_call
         self._hyperloglog = hyperloglog or (lambda name, codec: RHyperLogLog(client, name, codec))
         self._bitset = bitset or (lambda name: RBitSet(client, name))
         self._queue: list = []
@@ -1533,7 +1665,7 @@ class RBatch:
             raise IllegalStateException("Batch already executed!")
         self._executed = True
         responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call, self._hll_stream_call,
-                                     *self._hll_groups_calls, self._bit_groups_call)
+                                     *self._hll_groups_calls, self._bit_groups_call, self._range_stream_call)
         if error is not None:
             raise error
         return BatchResult(responses)

@@ -889,6 +889,94 @@ static int bitset_op_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, c
     return RBX_OK;
 }
 
+// ---- BITCOUNT / BITPOS / STRLEN / length() over many keys (rbx_bitset_range_stream) ----
+static std::atomic<uint32_t> g_rangestream_last[4];  // rbx_bench_rangestream_last shows them
+enum { kRsShortDone = 0, kRsLongCmds = 1, kRsTiles = 2, kRsWaits = 3 };
+static const char *const kRangeIllegalMsg =
+    "a command's key is not below nkeys, its op, unit or nargs is unknown, or a BITCOUNT has a start without an end";
+
+// what a command that failed alone reports (range_cmd.h kRange*), as the single calls do
+static int range_cmd_failed(int kind) {
+    if (kind == kRangeOk) return RBX_OK;
+    if (kind == kRangeWrongType) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    return fail(RBX_E_REDIS, kind == kRangeBadBit   ? "ERR The bit argument must be 1 or 0."
+                             : kind == kRangeSyntax ? "ERR syntax error"
+                                                    : kBitOffsetMsg);
+}
+
+// A batch of n > 0 commands over device arrays inside the caller's scope on `st`; d_replies and d_status
+// nullable.  *failed = the failure kind of the first command in array order that failed alone.  The names are
+// resolved once and the key table built with every per-key maximum 0, which creates nothing; then per chunk the
+// group kernel, the one wait for its summary, and -- when it listed long commands -- the tiles.  replies / status:
+// the host form's targets (null for the _dev form), copied behind the group kernel, so that the summary's wait
+// brings them too, and once more behind the tiles, with the chunk's second wait.
+static int range_stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_key,
+                            const rbx_range_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
+                            int64_t *replies, uint8_t *status, hipStream_t st, int *failed) {
+    *failed = kRangeOk;
+    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, kRangeIllegalMsg);
+    BitsetScratch &b = c->dev->bits;
+    StreamKeys sk;
+    sk.nkeys = nkeys;
+    sk.kinfo.assign((size_t)nkeys * 5, 0);
+    stream_names_resolve(c, names, nkeys, KType::Bitmap, &sk.nm, sk.canon(), sk.wrong(), [](uint32_t, const Entry &) {});
+    const std::vector<unsigned long long> no_writes(nkeys, 0);
+    const BitKey *d_tab;
+    bool writes;
+    RBX_TRY(stream_keys_table(c, sk, no_writes.data(), st, &d_tab, &writes));
+    uint64_t max_bytes = 0;
+    for (const BitKey &k : b.bst_table.host) max_bytes = std::max(max_bytes, k.cap_bits >> 3);
+
+    const uint32_t tile = g_tune.rangestream_tile, short_max = g_tune.rangestream_short_max;
+    const int lanes = g_tune.rangestream_lanes;
+    // one summary word hands out a chunk's list slots and tile numbers: its tiles stay below 2^kRsTileBits
+    const uint64_t chunk = std::min<uint64_t>(g_tune.rangestream_chunk, ((1ULL << kRsTileBits) - 1) / (max_bytes / tile + 2));
+    RBX_TRY(b.rs_long.reserve(std::min(n, chunk) * 8));
+    RBX_TRY(b.rs_sum.reserve(kRsSummaryWords * 8));
+    auto *d_sum = b.rs_sum.as<unsigned long long>(), *d_long = b.rs_long.as<unsigned long long>();
+    unsigned long long *w = c->dev->stage.words();
+    uint64_t stats[4] = {0, 0, 0, 0};
+    for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
+        const uint32_t m = (uint32_t)std::min(chunk, n - i0);
+        int64_t *d_r = d_replies ? d_replies + i0 : nullptr;
+        uint8_t *d_s = d_status ? d_status + i0 : nullptr;
+        HIP_TRY(hipMemsetAsync(d_sum, 0xFF, kRangeKinds * 8, st));
+        HIP_TRY(hipMemsetAsync(d_sum + kRangeKinds, 0, (kRsSummaryWords - kRangeKinds) * 8, st));
+        launch_rangestream_short(lanes, d_tab, d_key + i0, d_cmds + i0, m, nkeys, short_max, tile, d_r, d_s, d_sum, d_long, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w, d_sum, kRsSummaryWords * 8, hipMemcpyDeviceToHost, st));
+        if (replies) HIP_TRY(hipMemcpyAsync(replies + i0, d_r, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+        if (status) HIP_TRY(hipMemcpyAsync(status + i0, d_s, m, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));  // the chunk's one wait
+        ++stats[kRsWaits];
+        if (w[kRsFlags] & kRsIllegal) return fail(RBX_E_ILLEGAL_ARGUMENT, kRangeIllegalMsg);
+        const uint64_t nlong = w[kRsLong] >> kRsTileBits, tiles = w[kRsLong] & ((1ULL << kRsTileBits) - 1);
+        if (*failed == kRangeOk) {
+            uint64_t first = ~0ULL;
+            for (int k = 0; k < kRangeKinds; ++k)
+                if (w[kRsFirst + k] < first) first = w[kRsFirst + k], *failed = k + 1;
+        }
+        stats[kRsShortDone] += m - nlong;
+        stats[kRsLongCmds] += nlong;
+        stats[kRsTiles] += tiles;
+        if (nlong == 0 || !d_r) continue;  // (without replies a long command has nothing left to answer)
+        launch_rangestream_tiles(d_tab, d_key + i0, d_cmds + i0, tile, d_long, (uint32_t)nlong, tiles, d_r, st);
+        HIP_TRY(hipGetLastError());
+        if (replies) {
+            HIP_TRY(hipMemcpyAsync(replies + i0, d_r, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            ++stats[kRsWaits];
+        }
+    }
+    for (int i = 0; i < 4; ++i) g_rangestream_last[i] = (uint32_t)std::min<uint64_t>(stats[i], 0xFFFFFFFFu);
+    return RBX_OK;
+}
+
+static int range_stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, uint64_t n, bool arrays) {
+    if (n && !arrays) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    return stream_names_check(c, names, nkeys);
+}
+
 }  // namespace rbx
 
 using namespace rbx;
@@ -1130,6 +1218,67 @@ int rbx_bitset_op_groups(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, cons
 int rbx_bench_bitgroups_last(uint32_t out[4]) {
     if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
     for (int i = 0; i < 4; ++i) out[i] = g_bitgroups_last[i];
+    return RBX_OK;
+}
+
+int rbx_bitset_range_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                                const rbx_range_cmd *d_cmds, uint64_t n, int64_t *d_replies, uint8_t *d_status,
+                                void *stream) {
+    RBX_TRY(range_stream_args_check(c, names, nkeys, n, d_cmd_key && d_cmds));
+    if (n == 0) return RBX_OK;  // no command is sent
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    int failed;
+    RBX_TRY(range_stream_run(c, names, nkeys, d_cmd_key, d_cmds, n, d_replies, d_status, nullptr, nullptr, st, &failed));
+    return range_cmd_failed(failed);
+}
+
+int rbx_bitset_range_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                            const rbx_range_cmd *cmds, uint64_t n, int64_t *replies, uint8_t *status) {
+    RBX_TRY(range_stream_args_check(c, names, nkeys, n, cmd_key && cmds));
+    if (n == 0) return RBX_OK;
+    for (uint64_t i = 0; i < n; ++i)  // the caller's errors, before any device work
+        if (cmd_key[i] >= nkeys || range_cmd_illegal(cmds[i])) return fail(RBX_E_ILLEGAL_ARGUMENT, kRangeIllegalMsg);
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.rs_cmds.reserve(n * (sizeof(rbx_range_cmd) + 4)));  // commands | keys
+    if (replies) RBX_TRY(b.rs_out.reserve(n * 8));
+    if (status) RBX_TRY(b.rs_status.reserve(n));
+    rbx_range_cmd *d_cmds = b.rs_cmds.as<rbx_range_cmd>();
+    uint32_t *d_key = (uint32_t *)(d_cmds + n);
+    HIP_TRY(hipMemcpyAsync(d_cmds, cmds, n * sizeof(rbx_range_cmd), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_key, cmd_key, n * 4, hipMemcpyHostToDevice, st));
+    int failed;
+    RBX_TRY(range_stream_run(c, names, nkeys, d_key, d_cmds, n, replies ? b.rs_out.as<int64_t>() : nullptr,
+                             status ? b.rs_status.as<uint8_t>() : nullptr, replies, status, st, &failed));
+    return range_cmd_failed(failed);
+}
+
+int rbx_bitset_range_of(const uint8_t *bytes, uint64_t len, int missing, const rbx_range_cmd *cmd, int64_t *reply) {
+    if ((len && !bytes) || !cmd || !reply) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (range_cmd_illegal(*cmd)) return fail(RBX_E_ILLEGAL_ARGUMENT, kRangeIllegalMsg);
+    *reply = 0;
+    if (const int kind = range_cmd_fails(*cmd)) return range_cmd_failed(kind);
+    if (missing) len = 0;
+    if (cmd->op == RBX_RANGE_LENGTH)
+        return bitset_length_rule(len, len ? bytes[0] : 0, len ? bytes[len - 1] : 0, reply) ? RBX_OK : range_cmd_failed(kRangeScript);
+    uint64_t lo, hi;
+    if (!range_cmd_plan(*cmd, len, missing != 0, &lo, &hi, reply)) return RBX_OK;
+    const bool pos = cmd->op == RBX_RANGE_POS;
+    uint64_t ones = 0, found = kBitsNone;
+    for (uint64_t p = lo; p <= hi && found == kBitsNone; ++p) {
+        const int bit = (bytes[p >> 3] >> (7 - (p & 7))) & 1;
+        ones += bit;
+        if (pos && bit == cmd->bit) found = p;
+    }
+    *reply = pos ? range_cmd_pos_reply(*cmd, found, hi) : (int64_t)ones;
+    return RBX_OK;
+}
+
+int rbx_bench_rangestream_last(uint32_t out[4]) {
+    if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (int i = 0; i < 4; ++i) out[i] = g_rangestream_last[i];
     return RBX_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <ctime>
 
 #include "../../include/rbx.h"
+#include "range_cmd.h"
 
 namespace rbx {
 
@@ -384,18 +385,9 @@ int ks_pexpiretime(Keyspace &ks, const std::string &name, int64_t *out) {
 // fromBit = -1 (last byte zero, empty or missing string): toBit = 8 * 0.875 - 7 = 0, the loop tests
 // bit 0 -- set only when a longer string's FIRST byte has it: returns 1 -- and then GETBIT key -1,
 // which Redis refuses: the script fails.
+// (the rule itself is range_cmd.h's bitset_length_rule, which a device lane applies too)
 int bitset_length(uint64_t len, uint8_t first, uint8_t last, int64_t *out) {
-    if (len && last) {
-        int low = 0;  // lowest set bit of the byte = the highest MSB-first index
-        while (!((last >> low) & 1)) ++low;
-        *out = (int64_t)((len - 1) * 8 + (uint64_t)(7 - low) + 1);
-        return RBX_OK;
-    }
-    if (len && (first & 0x80)) {
-        *out = 1;
-        return RBX_OK;
-    }
-    return fail(RBX_E_REDIS, kBitOffsetMsg);
+    return bitset_length_rule(len, first, last, out) ? RBX_OK : fail(RBX_E_REDIS, kBitOffsetMsg);
 }
 
 int bitset_length_of(const uint8_t *bytes, uint64_t len, int64_t *out) {

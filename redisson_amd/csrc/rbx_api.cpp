@@ -339,6 +339,10 @@ static const TuneRow kTuneRows[] = {
     {"hllstream_elems_per_round", RANGE(1, kIntMax), false, FIELD(hllstream_elems_per_round)},
     {"hllgroups_split", ONE_OF(0, 1, 2, 4, 8, 16), false, FIELD(hllgroups_split)},
     {"bitgroups_tile", POW2_OR_0(4096, 1 << 20), false, FIELD(bitgroups_tile)},
+    {"rangestream_lanes", ONE_OF(4, 8, 16, 32, 64), false, FIELD(rangestream_lanes)},
+    {"rangestream_short_max", POW2(64, 1 << 20), false, FIELD(rangestream_short_max)},
+    {"rangestream_tile", POW2(4096, 1 << 20), false, FIELD(rangestream_tile)},
+    {"rangestream_chunk", RANGE(1, 1 << 30), false, FIELD(rangestream_chunk)},  // positions in a chunk are 30-bit
 };
 #undef RANGE
 #undef ONE_OF

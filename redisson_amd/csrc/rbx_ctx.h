@@ -398,6 +398,9 @@ struct BitsetScratch {
     // sources in one upload, the length words' pointers and values of the call's keys, one count per group
     DevBuf grp_table, grp_lens, grp_counts;
     PinBuf grp_pin;  // where the lengths and then the counts come back to (a pageable target costs a staging copy)
+    // the read queries over many keys (rbx_bitset_range_stream): the host form's uploaded commands |
+    // keys, its replies and status, a chunk's summary words, and its long list (8 bytes per command of a chunk)
+    DevBuf rs_cmds, rs_out, rs_status, rs_sum, rs_long;
 };
 
 // Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).

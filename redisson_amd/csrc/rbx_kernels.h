@@ -10,6 +10,7 @@
 #include "../../include/rbx.h"
 #include "bk_entry.h"
 #include "rbx_device.h"
+#include "range_cmd.h"  // after rbx_device.h: it keeps an RBX_HD that is already defined
 
 namespace rbx {
 
@@ -384,37 +385,7 @@ void launch_field_one(uint32_t *words, unsigned long long *len, uint64_t cap_byt
 // Ranged BITCOUNT / BITPOS ([redis-7.2] bitops.c bitcountCommand / bitposCommand as DESIGN §11.2 restates
 // them).  The reply rules are host and device code: single calls and the host-string forms apply them on the
 // host, the batch kernels in their query prologue.  unit: RBX_RANGE_BYTE (0) or RBX_RANGE_BIT of rbx.h.
-constexpr unsigned long long kBitsNone = 1ULL << 40;  // "no such bit": above every bit position
-// Normalise(start, end) over a string of len bytes: the bit interval [*lo, *hi], or false = empty
-RBX_HD bool bits_normalise(int64_t start, int64_t end, int unit, uint64_t len, uint64_t *lo, uint64_t *hi) {
-    const int64_t t = (int64_t)(unit ? len * 8 : len);
-    if (start < 0) start += t;
-    if (end < 0) end += t;
-    if (start < 0) start = 0;
-    if (end < 0) end = 0;
-    if (end > t - 1) end = t - 1;
-    if (start > end) return false;
-    *lo = unit ? (uint64_t)start : (uint64_t)start * 8;
-    *hi = unit ? (uint64_t)end : (uint64_t)end * 8 + 7;
-    return true;
-}
-// BITCOUNT's interval: "start < 0 && end < 0 && start > end" answers 0 before anything is normalised
-RBX_HD bool bits_count_interval(int64_t start, int64_t end, int unit, uint64_t len, uint64_t *lo, uint64_t *hi) {
-    if (start < 0 && end < 0 && start > end) return false;
-    return bits_normalise(start, end, unit, len, lo, hi);
-}
-// BITPOS's reply over a non-empty interval ending at hi; found >= kBitsNone = no position holds the bit: -1,
-// but hi + 1 for a clear bit when no end was given (the string counts as zero-padded on the right)
-RBX_HD int64_t bits_pos_reply(uint64_t found, int bit, bool end_given, uint64_t hi) {
-    if (found < kBitsNone) return (int64_t)found;
-    return (bit || end_given) ? -1 : (int64_t)hi + 1;
-}
-// the bytes a query's clamped interval covers (0 = empty): the batch's work summary adds them up
-RBX_HD uint64_t bits_interval_bytes(int64_t start, int64_t end, int unit, uint64_t len, bool pos) {
-    uint64_t lo, hi;
-    const bool any = pos ? bits_normalise(start, end, unit, len, &lo, &hi) : bits_count_interval(start, end, unit, len, &lo, &hi);
-    return any ? (hi >> 3) - (lo >> 3) + 1 : 0;
-}
+// (kBitsNone and the bits_* range rules: range_cmd.h, which compiles without HIP)
 // the directory's 4 KiB blocks over a string of len bytes; the directory holds one more word than that
 RBX_HD uint64_t bits_dir_blocks(uint64_t len) { return (len + 4095) >> 12; }
 // Every interval below is normalised: lo <= hi < 8 * length.
@@ -482,6 +453,27 @@ int launch_bitstream_grouped(const BitKey *d_tab, const uint32_t *d_key, const u
                              void *d_scratch, size_t scratch_bytes, hipStream_t st);
 // *len = max(*len, bytes up to the key's largest SETBIT) for every key with an entry in d_keymax
 void launch_bitstream_lengths(const BitKey *d_tab, const unsigned long long *d_keymax, uint32_t nkeys, hipStream_t st);
+
+// ---- rangestream_kernels.hip
+// The read queries over many strings (rbx_bitset_range_stream): command i is (key[i], cmds[i]),
+// the strings are reached through the BitKey table above, range_cmd.h has the rules.
+// the summary words (u64) of one chunk: the first position of each failure kind (kRange* - 1; the caller sets
+// them to ~0 and the others to 0), the flags, and one word that hands out the long list's slots and the tile
+// numbers together: long commands << kRsTileBits | tiles
+enum { kRsFirst = 0, kRsFlags = kRangeKinds, kRsLong = kRangeKinds + 1, kRsSummaryWords = kRangeKinds + 2 };
+constexpr uint32_t kRsIllegal = 1;
+constexpr int kRsTileBits = 33, kRsPosBits = 30;  // a chunk has <= 2^30 commands and fewer than 2^33 tiles
+// One group of `lanes` lanes (4, 8, 16, 32 or 64) per command, n <= 2^30: every command whose interval covers
+// at most short_max bytes is answered (d_replies, d_status nullable); a longer one presets its reply (0 for
+// COUNT, kBitsNone for POS) and appends (first tile << kRsPosBits | position) to d_long (n entries), ascending.
+void launch_rangestream_short(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_range_cmd *d_cmds,
+                              uint32_t n, uint32_t nkeys, uint32_t short_max, uint32_t tile_bytes, int64_t *d_replies,
+                              uint8_t *d_status, unsigned long long *d_sum, unsigned long long *d_long, hipStream_t st);
+// the long commands' tiles (ntiles > 0 in all, nlong commands) swept by the whole grid, then one lane per long POS
+// command turns the minimum into its reply
+void launch_rangestream_tiles(const BitKey *d_tab, const uint32_t *d_key, const rbx_range_cmd *d_cmds,
+                              uint32_t tile_bytes, const unsigned long long *d_long, uint32_t nlong, uint64_t ntiles,
+                              int64_t *d_replies, hipStream_t st);
 
 // ---- fieldstream_kernels.hip
 // The ordered stream of single-sub-command BITFIELDs over many strings (rbx_bitset_field_stream, DESIGN

@@ -144,6 +144,23 @@ struct Tunables {
     // "bitgroups_tile": the bytes T of a tile of the segmented sweep: 0 (default) = auto, else a power of two in
     // 4 KiB .. 1 MiB.  All exact.  Auto: bitgroups_auto_tile below.
     std::atomic<uint32_t> bitgroups_tile{0};
+
+    // ---- the read queries over many keys (api_bitset.cpp) ----
+    // "rangestream_lanes": the lanes G of the group that answers one command, 4, 8, 16, 32 or 64.  All exact.
+    // Measured (DESIGN 11.10 row d): on 20,000 strings of 46 bytes and of 1 KiB the five settings lie within 1 % (the
+    // call is host-bound there); 16 is kept.
+    std::atomic<int> rangestream_lanes{16};
+    // "rangestream_short_max": the bytes of the longest interval a lane group walks alone, a power of two in
+    // 64 .. 1 MiB; a longer one is cut into tiles for the whole device.  4096 is a guess: no measurement decides it (DESIGN 11.10
+    // row e's strings lie on one side of every setting).
+    std::atomic<uint32_t> rangestream_short_max{4096};
+    // "rangestream_tile": the bytes of a tile of a long interval, a power of two in 4 KiB .. 1 MiB.  65536 is the
+    // large-work optimum of bitgroups_auto_tile's table below, and measured here (DESIGN 11.10 row e): 4 KiB tiles cost
+    // 17 %, 16 KiB 2 %, and 64 KiB .. 1 MiB lie within 0.3 %.
+    std::atomic<uint32_t> rangestream_tile{65536};
+    // "rangestream_chunk": commands per chunk, 1 .. 2^30 (8 bytes of long list per command of a chunk; each chunk
+    // has its own summary and wait)
+    std::atomic<uint64_t> rangestream_chunk{1 << 25};
 };
 
 constexpr uint32_t kHllGroupsFillBlocks = 256;

@@ -23,9 +23,9 @@ import functools
 import numpy as np
 
 from . import _lib as L
-from .client import (GETBIT, PFADD, PFCOUNT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued,
-                     bitset_field_stream_call, bitset_op_groups_call, bitset_stream_call, hll_count_groups_call, hll_merge_groups_call,
-                     hll_stream_call, run_queue)
+from .client import (GETBIT, PFADD, PFCOUNT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued, _range_row,
+                     bitset_field_stream_call, bitset_op_groups_call, bitset_range_stream_call, bitset_stream_call,
+                     hll_count_groups_call, hll_merge_groups_call, hll_stream_call, run_queue)
 from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
 
@@ -187,7 +187,26 @@ def _bit_count_group(key, begin=None, end=None):
     return (L.RBX_BITOP_OR, None, [_key(key)]), lambda _length, count: count
 
 
-def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=None):
+def _bit_count_range(key, begin=None, end=None):
+    """(key, row, convert) of a pipelined bitCount as a read query: BITCOUNT key, or BITCOUNT key begin end"""
+    if begin is None and end is None:
+        return key, _range_row(L.RBX_RANGE_COUNT), None
+    if begin is None or end is None:
+        return None  # the single call raises it at its position
+    return key, _range_row(L.RBX_RANGE_COUNT, 0, 2, int(begin), int(end), L.RBX_RANGE_BYTE), None
+
+
+def _bit_pos_range(key, bit, range=(None, None)):  # noqa: A002
+    """the same of a pipelined bitPos: the upper bound travels only behind a bounded lower one (S:2351-2356)"""
+    if range is None:
+        return None
+    lower, upper = range
+    nargs = 0 if lower is None else (1 if upper is None else 2)
+    return key, _range_row(L.RBX_RANGE_POS, int(bool(bit)), nargs, int(lower or 0), int(upper or 0) if nargs == 2 else 0,
+                           L.RBX_RANGE_BYTE), None
+
+
+def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=None, rng=None):
     """A command method of RedissonConnection: while a pipeline is open it queues itself and returns None
     (the result comes back from closePipeline); bit = (key, op, index) of a GETBIT / SETBIT, which travels with
     its neighbours in one rbx_bitset_stream call; field = (key, row, convert) of a BITFIELD with one sub-command
@@ -197,7 +216,8 @@ def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=Non
     destination, sources) of a PFMERGE (or None for any other), which travels with its like in one
     rbx_hll_count_groups / rbx_hll_merge_groups call; bitop = ((RBX_BITOP_*, destination or None, sources), convert)
     of a BITOP or a whole-string BITCOUNT (or None for any other), which travels with its like in one
-    rbx_bitset_op_groups call."""
+    rbx_bitset_op_groups call; rng = (key, row, convert) of a read query (BITCOUNT, BITPOS, STRLEN; or None for any
+    other), which travels with its like in one rbx_bitset_range_stream call -- a whole-string BITCOUNT carries both."""
 
     def wrap(f):
         @functools.wraps(f)
@@ -209,12 +229,22 @@ def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=Non
                 self._pipeline.append(_Queued(_key(key), op, _bit_index(index)))
                 return None
             single = lambda: f(self, *args, **kwargs)  # noqa: E731
+            query = None
+            if rng is not None:
+                try:
+                    query = rng(*args, **kwargs)
+                except (IllegalArgumentException, TypeError, ValueError):
+                    query = None  # the single call raises it at its position
+            row = bitop(*args, **kwargs) if bitop is not None else None
+            if row is not None:
+                self._pipeline.append(_Queued(row[0][2][0], fn=single, bitop=row[0], convert=row[1],
+                                              range=query[1] if query else None))
+                return None
+            if query is not None:
+                self._pipeline.append(_Queued(_key(query[0]), fn=single, range=query[1], convert=query[2]))
+                return None
             if bitop is not None:
-                row = bitop(*args, **kwargs)
-                if row is not None:
-                    self._pipeline.append(_Queued(row[0][2][0], fn=single, bitop=row[0], convert=row[1]))
-                else:
-                    self._pipeline.append(_Queued(fn=single))
+                self._pipeline.append(_Queued(fn=single))
                 return None
             if group is not None:
                 try:
@@ -270,8 +300,9 @@ class RedissonConnection:
         exactly one sub-command among them they are one rbx_bitset_field_stream call.  Consecutive pfAdd and
         single-key pfCount commands, over any keys, are one rbx_hll_stream call; consecutive pfCount commands of
         two or more keys are one rbx_hll_count_groups call, consecutive pfMerge commands one rbx_hll_merge_groups
-        call.  Consecutive bitOp and bitCount(key) commands, over any keys, are one rbx_bitset_op_groups call.  Every
-        command runs; then the first failure is raised."""
+        call.  Consecutive bitOp and bitCount(key) commands, over any keys, are one rbx_bitset_op_groups call;
+        consecutive bitCount(key, begin, end), bitPos and strLen commands one rbx_bitset_range_stream call, which a
+        bitCount(key) behind them joins.  Every command runs; then the first failure is raised."""
         if self._pipeline is None:
             return []
         queue, self._pipeline = self._pipeline, None
@@ -280,7 +311,8 @@ class RedissonConnection:
                                    lambda *a: hll_stream_call(self._client, *a),
                                    lambda *a: hll_count_groups_call(self._client, *a),
                                    lambda *a: hll_merge_groups_call(self._client, *a),
-                                   lambda *a: bitset_op_groups_call(self._client, *a))
+                                   lambda *a: bitset_op_groups_call(self._client, *a),
+                                   lambda *a: bitset_range_stream_call(self._client, *a))
         if error is not None:
             raise error
         return results
@@ -336,7 +368,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_set(self._client.ctx, nm, int(offset), int(bool(value)), C.byref(old)))
         return bool(old.value)
 
-    @_pipelined(bitop=_bit_count_group)
+    @_pipelined(bitop=_bit_count_group, rng=_bit_count_range)
     def bitCount(self, key: bytes, begin: int | None = None, end: int | None = None) -> int:
         """BITCOUNT key  S:638-641, BITCOUNT key begin end  S:643-646 (bytes, both inclusive)"""
         nm, _keep = L.name_struct(_key(key))
@@ -361,7 +393,7 @@ class RedissonConnection:
         _check(L.lib().rbx_bitset_op(self._client.ctx, code, dest, srcs, len(keys), C.byref(out)))
         return int(out.value)
 
-    @_pipelined
+    @_pipelined(rng=lambda key: (key, _range_row(L.RBX_RANGE_STRLEN), None))
     def strLen(self, key: bytes) -> int:
         """STRLEN key  S:663-666"""
         nm, _keep = L.name_struct(_key(key))
@@ -391,7 +423,7 @@ class RedissonConnection:
 
     bit_field = bitField
 
-    @_pipelined
+    @_pipelined(rng=_bit_pos_range)
     def bitPos(self, key: bytes, bit: bool, range=(None, None)) -> int:
         """BITPOS key bit [lower [upper]]  S:2337-2359.  range = (lower, upper), each an int or None
         (Range.unbounded()).  As in the reference the upper bound is sent only when the lower one is bounded
