@@ -279,10 +279,87 @@ int rbx_bitset_size(rbx_ctx *ctx, rbx_name name, uint64_t *out);
 int rbx_bitset_length(rbx_ctx *ctx, rbx_name name, int64_t *out);
 /* the same script over a host string (no context) */
 int rbx_bitset_length_of(const uint8_t *bytes, uint64_t len, int64_t *out);
-/* toByteArray() = GET  :327-334 and set(BitSet) = SET  :457-459: rbx_bloom_export / rbx_bloom_import
- * with a binary name */
+/* toByteArray() = GET  :327-334 and the SET of set(BitSet)  :457-459 once its bytes exist: rbx_bloom_export /
+ * rbx_bloom_import with a binary name.  set(BitSet) itself, conversion included, is rbx_bitset_set_words below. */
 int rbx_bitset_export_n(rbx_ctx *ctx, rbx_name name, uint8_t *out, uint64_t cap, uint64_t *redis_len);
 int rbx_bitset_import_n(rbx_ctx *ctx, rbx_name name, const uint8_t *bytes, uint64_t len);
+/* asBitSet()  :391-408 and set(BitSet)  :411-420, :457-459 -- the exchange with java.util.BitSet, whose long[]
+ * words hold bit j of word w = bit 64 w + j (LSB first) where the string holds bit i in byte i >> 3 under the mask
+ * 0x80 >> (i & 7): the conversion reverses the bits of every byte, on the device next to the data.
+ *   as_words   asBitSet().toLongArray().  *nwords = BitSet's words in use: the highest set bit / 64 + 1, or 0 for
+ *              no set bit, a missing key or an empty string.  min(cap_words, *nwords) words are written (as
+ *              rbx_bloom_export does with bytes; `words` may be NULL with cap_words 0).  It reads only.
+ *   set_words  set(BitSet.valueOf(words)): the stored string is toByteArrayReverse's, bs.length() / 8 + 1 bytes
+ *              with bs.length() = the highest set bit + 1 -- the empty BitSet stores ONE ZERO BYTE, a highest bit of
+ *              7 stores two bytes -- and it is stored exactly as rbx_bitset_import_n stores those bytes (the key is
+ *              replaced whatever it held, its timeout goes, the allocation covers an existing {name}:config's
+ *              |size|).  Trailing zero words are allowed.  A highest set bit >= 2^31 - 1 is
+ *              RBX_E_ILLEGAL_ARGUMENT: Java's int length() overflows there and the reference throws.
+ * The _dev forms take device arrays and enqueue on `stream`.  as_words_dev does not wait: its kernels take the
+ * length from the device length word, and *d_nwords is a device word.  set_words_dev waits once, for the highest
+ * set bit.  The host forms without a context (as rbx_bitset_count_of): rbx_bitset_as_words_of is as_words over a
+ * host string; rbx_bitset_bytes_of_words writes min(cap, *len) bytes of set_words' string and its length. */
+int rbx_bitset_as_words(rbx_ctx *ctx, rbx_name name, uint64_t *words, uint64_t cap_words, uint64_t *nwords);
+int rbx_bitset_as_words_dev(rbx_ctx *ctx, rbx_name name, uint64_t *d_words, uint64_t cap_words, uint64_t *d_nwords,
+                            void *stream);
+int rbx_bitset_set_words(rbx_ctx *ctx, rbx_name name, const uint64_t *words, uint64_t nwords);
+int rbx_bitset_set_words_dev(rbx_ctx *ctx, rbx_name name, const uint64_t *d_words, uint64_t nwords, void *stream);
+int rbx_bitset_as_words_of(const uint8_t *bytes, uint64_t len, uint64_t *words, uint64_t cap_words, uint64_t *nwords);
+int rbx_bitset_bytes_of_words(const uint64_t *words, uint64_t nwords, uint8_t *out, uint64_t cap, uint64_t *len);
+/* ENGINE EXTENSION (no RBitSet method; the inverse of rbx_bitset_set_indexes): the positions of the set bits.
+ *   Interval  nargs 0: the whole string.  nargs 2: the bit interval of BITCOUNT key start end unit, normalised
+ *             exactly as rbx_bitset_count_range does, the "start < 0 && end < 0 && start > end" pre-check included.
+ *   total     *total = the ones of the interval: what rbx_bitset_count_range (rbx_bitset_cardinality for nargs 0)
+ *             answers.  A missing key and an empty string give 0.
+ *   out       the absolute bit positions of the ones of rank skip .. min(total, skip + cap) - 1, ascending, as
+ *             uint64_t like rbx_bitset_set_indexes' indexes; *written = their number.  A cap smaller than what is
+ *             left is pagination, not an error; cap = 0 with a NULL out is a legal "count only" call.
+ *   Errors    a key of another type (an HLL key too) is RBX_E_WRONGTYPE; an unknown unit, nargs other than 0 or 2
+ *             and a NULL out with cap > 0 are RBX_E_ILLEGAL_ARGUMENT.  Nothing is created, grown or touched,
+ *             timeouts included.
+ *   Cost      one block directory over the string per call (4 KiB blocks, living for the call only), then only the
+ *             blocks that hold a rank of the page are read again: a page costs the directory plus the page.
+ * The _dev form writes d_counts[0] = written, d_counts[1] = total and waits once on `stream`, for the string's
+ * length.  rbx_bitset_members_of is the same over a host string without a context (as rbx_bitset_count_of): the
+ * command's skip is the first rank and min(limit, cap) the page. */
+typedef struct {
+    int64_t start, end;   /* BITCOUNT's arguments; ignored for nargs 0 */
+    uint64_t skip, limit; /* the ones of rank skip .. skip + limit - 1; limit UINT64_MAX = all */
+    uint8_t nargs, unit;  /* 0 or 2; RBX_RANGE_BYTE / RBX_RANGE_BIT */
+    uint8_t pad[6];
+} rbx_members_cmd; /* 40 bytes */
+int rbx_bitset_members(rbx_ctx *ctx, rbx_name name, int nargs, int64_t start, int64_t end, int unit, uint64_t skip,
+                       uint64_t cap, uint64_t *out, uint64_t *written, uint64_t *total);
+int rbx_bitset_members_dev(rbx_ctx *ctx, rbx_name name, int nargs, int64_t start, int64_t end, int unit, uint64_t skip,
+                           uint64_t cap, uint64_t *d_out, uint64_t *d_counts, void *stream);
+int rbx_bitset_members_of(const uint8_t *bytes, uint64_t len, int missing, const rbx_members_cmd *cmd, uint64_t cap,
+                          uint64_t *out, uint64_t *written, uint64_t *total);
+/* ENGINE EXTENSION: the members of many keys in one call (the per-entity workload of rbx_bitset_range_stream: every
+ * user's active days).  Command i runs on names[cmd_key[i]] and yields the ones of rank skip .. skip + limit - 1 of its
+ * interval (limit UINT64_MAX = all).
+ *   off      n + 1 words, the exclusive prefix sums of the commands' yields: always written in full and exact, whatever
+ *            cap is.  *total = off[n].
+ *   out      the first min(total, cap) positions of the concatenation; command i's slice is out[off[i] .. off[i + 1]).
+ *            What lies past min(total, cap) stays untouched.  The caller compares total with cap and asks again if it
+ *            was short; cap = 0 (out may be NULL) only counts.
+ *   status   (nullable) status[i] = 0, or 0xFF for a command that fails alone: its key holds another type
+ *            (RBX_E_WRONGTYPE; an HLL key and a {name}:config hash too).  Such a command yields nothing, the others
+ *            run, and the call returns the code -- the rule of rbx_bitset_range_stream.
+ *   Errors   the caller's own are RBX_E_ILLEGAL_ARGUMENT with the outputs unspecified: a key id not below nkeys, an
+ *            unknown unit, nargs other than 0 or 2, NULL arrays with n > 0, a NULL out with cap > 0.  n = 0 sends
+ *            nothing (off[0] = 0).  Two names with equal bytes are one key.  Nothing is created, grown or touched.
+ *   Paths    two passes around one scan, in the two tiers of rbx_bitset_range_stream: a group of lanes counts and
+ *            expands an interval of at most "members_short_max" bytes itself; a longer one is cut into tiles of
+ *            "members_tile" bytes that the whole device counts and expands (rbx_tune; every setting is exact).
+ * The _dev form takes device arrays (off[n] is the total) and waits once per chunk of "members_chunk" commands on
+ * `stream`; the host form runs the counting pass twice, once to size the output.  Scope as rbx_bitset_range_stream:
+ * no handle form; the node router and the Java shim do not carry it. */
+int rbx_bitset_members_stream(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                              const rbx_members_cmd *cmds, uint64_t n, uint64_t cap, uint64_t *off, uint64_t *out,
+                              uint8_t *status, uint64_t *total);
+int rbx_bitset_members_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                                  const rbx_members_cmd *d_cmds, uint64_t n, uint64_t cap, uint64_t *d_off,
+                                  uint64_t *d_out, uint8_t *d_status, void *stream);
 /* rename(newName) = RENAME name newName, `name` alone (M/RedissonObject.java:151-153) */
 int rbx_bitset_rename(rbx_ctx *ctx, rbx_name name, rbx_name new_name);
 /* getSigned / setSigned / incrementAndGetSigned, the Unsigned three, and the Byte / Short / Integer /

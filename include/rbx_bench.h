@@ -63,6 +63,8 @@ int rbx_bench_bitgroups_last(uint32_t out[4]);
 /* What the last rbx_bitset_range_stream[_dev] call of this process did: out[0] = commands the group kernel finished,
  * out[1] = long commands (their intervals went to the tiles), out[2] = tiles, out[3] = waits on the stream. */
 int rbx_bench_rangestream_last(uint32_t out[4]);
+/* The same four numbers for the last rbx_bitset_members_stream[_dev] call (the host form's second run). */
+int rbx_bench_members_last(uint32_t out[4]);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -176,6 +178,14 @@ int rbx_bench_rangestream_last(uint32_t out[4]);
  *                           the large-work optimum of bitgroups_tile's table and of DESIGN 11.10 row e)
  *   "rangestream_chunk"     commands per chunk, 1 .. 2^30 (default 2^25: 8 bytes of long list per command); each
  *                           chunk has its own summary and wait
+ *   "members_lanes"         rbx_bitset_members_stream: the lanes of the group that counts and expands one short
+ *                           command, 4, 8, 16, 32 or 64 (default 16; within 0.5 % of every other setting on short strings); every
+ *                           setting gives the same answers
+ *   "members_short_max"     bytes of the longest interval a lane group enumerates alone, a power of two in 64 .. 1 MiB
+ *                           (default 4096, a guess no measurement decides); a longer one is cut into tiles
+ *   "members_tile"          bytes of a tile of a long interval, a power of two in 4 KiB .. 1 MiB (default 65536:
+ *                           4 KiB tiles cost 29 % and 1 MiB tiles 10 %, DESIGN 11.11 row f)
+ *   "members_chunk"         commands per chunk, 1 .. 2^30 (default 2^25); each chunk has its own summary and wait
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

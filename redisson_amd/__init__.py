@@ -7,7 +7,8 @@ from .client import (BatchResult, BloomHandle, RBatch, RBitSet, RBloomFilter, Re
                      bitset_op_groups_call, bitset_range_stream, bitset_range_stream_call, bitset_range_stream_dev,
                      bitset_field_stream, bitset_field_stream_dev, bitset_stream, bitset_stream_dev, bloom_add_multi, bloom_stream, bloom_contains_multi, calc_slot,
                      crc16, hll_add_multi, hll_count_each, hll_count_groups, hll_count_groups_call, hll_merge_groups,
-                     hll_merge_groups_call, hll_stream, hll_stream_call, hll_stream_dev, slot_to_gpu)
+                     hll_merge_groups_call, hll_stream, hll_stream_call, hll_stream_dev, slot_to_gpu,
+                     bitset_members_stream, bitset_members_stream_call, bitset_members_stream_dev)
 from .codec import ByteArrayCodec, StringCodec
 from .exceptions import (ArithmeticException, DeviceError, IllegalArgumentException, IllegalStateException,
                          RedisException, UnsupportedOperationException)
@@ -22,5 +23,6 @@ __all__ = [
     "bitset_field_stream", "bitset_field_stream_dev", "bitset_stream", "bitset_stream_dev", "bloom_add_multi", "bloom_contains_multi", "calc_slot", "crc16", "device_keys",
     "hll_add_multi", "hll_count_each", "hll_count_groups", "hll_count_groups_call", "hll_merge_groups",
     "hll_merge_groups_call", "bitset_op_groups_call", "bitset_range_stream", "bitset_range_stream_call",
-    "bitset_range_stream_dev", "hll_stream", "hll_stream_call", "hll_stream_dev", "slot_to_gpu",
+    "bitset_range_stream_dev", "bitset_members_stream", "bitset_members_stream_call", "bitset_members_stream_dev",
+    "hll_stream", "hll_stream_call", "hll_stream_dev", "slot_to_gpu",
 ]

@@ -94,6 +94,13 @@ class RbxRangeCmd(C.Structure):
                 ("nargs", C.c_uint8), ("unit", C.c_uint8), ("pad", C.c_uint8 * 4)]
 
 
+class RbxMembersCmd(C.Structure):
+    """struct rbx_members_cmd {start, end, skip, limit, nargs, unit, pad[6]}: 40 bytes"""
+
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("skip", C.c_uint64), ("limit", C.c_uint64),
+                ("nargs", C.c_uint8), ("unit", C.c_uint8), ("pad", C.c_uint8 * 6)]
+
+
 # name -> (restype, argtypes); every function declared in include/rbx.h
 SIGNATURES = {
     "rbx_abi_version": (C.c_int, []),
@@ -252,6 +259,22 @@ SIGNATURES = {
     "rbx_bitset_range_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.POINTER(RbxRangeCmd), C.POINTER(C.c_int64)]),
     "rbx_bitset_export_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64, u64p]),
     "rbx_bitset_import_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64]),
+    "rbx_bitset_as_words": (C.c_int, [vp, RbxName, u64p, C.c_uint64, u64p]),
+    "rbx_bitset_as_words_dev": (C.c_int, [vp, RbxName, vp, C.c_uint64, vp, vp]),
+    "rbx_bitset_set_words": (C.c_int, [vp, RbxName, u64p, C.c_uint64]),
+    "rbx_bitset_set_words_dev": (C.c_int, [vp, RbxName, vp, C.c_uint64, vp]),
+    "rbx_bitset_as_words_of": (C.c_int, [u8p, C.c_uint64, u64p, C.c_uint64, u64p]),
+    "rbx_bitset_bytes_of_words": (C.c_int, [u64p, C.c_uint64, u8p, C.c_uint64, u64p]),
+    "rbx_bitset_members": (C.c_int, [vp, RbxName, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, u64p,
+                                     u64p, u64p]),
+    "rbx_bitset_members_dev": (C.c_int, [vp, RbxName, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, vp,
+                                         vp, vp]),
+    "rbx_bitset_members_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.POINTER(RbxMembersCmd), C.c_uint64, u64p, u64p,
+                                        u64p]),
+    "rbx_bitset_members_stream": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, C.POINTER(RbxMembersCmd), C.c_uint64,
+                                            C.c_uint64, u64p, u64p, u8p, u64p]),
+    "rbx_bitset_members_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, vp, vp, C.c_uint64, C.c_uint64, vp, vp,
+                                                vp, vp]),
     "rbx_bitset_rename": (C.c_int, [vp, RbxName, RbxName]),
     "rbx_bitset_field": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, i64p]),
     "rbx_bitset_fields": (C.c_int, [vp, RbxName, C.c_int, C.c_int, C.c_int, u64p, i64p, C.c_uint64, i64p]),
@@ -284,6 +307,7 @@ SIGNATURES = {
     "rbx_bench_hllgroups_last": (C.c_int, [u32p]),
     "rbx_bench_bitgroups_last": (C.c_int, [u32p]),
     "rbx_bench_rangestream_last": (C.c_int, [u32p]),
+    "rbx_bench_members_last": (C.c_int, [u32p]),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

@@ -64,7 +64,8 @@ class RedissonClient:
 
     def createBatch(self) -> "RBatch":
         """M/api/RedissonClient.java createBatch()"""
-        return RBatch(self, range_stream_call=lambda *a: _engine_bitset_range_stream_call(self, *a))
+        return RBatch(self, range_stream_call=lambda *a: _engine_bitset_range_stream_call(self, *a),
+                      members_stream_call=lambda *a: _engine_bitset_members_stream_call(self, *a))
 
     def shutdown(self) -> None:
         if self._ctx:
@@ -684,6 +685,79 @@ class RBitSet(_Expirable):
         nm, _keep = self._n()
         _check(L.lib().rbx_bitset_import_n(self._client.ctx, nm, buf.ctypes.data_as(L.u8p), len(data)))
 
+    # ---- the exchange with java.util.BitSet: asBitSet() :391-408, set(BitSet) :411-420, :457-459 ----
+    def asBitSet(self) -> np.ndarray:
+        """asBitSet().toLongArray(): the BitSet's words in use as uint64, bit j of word w = bit 64 w + j
+        (rbx_bitset_as_words; empty for no set bit or a missing key)."""
+        nm, _keep = self._n()
+        n = C.c_uint64()
+        _check(L.lib().rbx_bitset_as_words(self._client.ctx, nm, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint64)
+        _check(L.lib().rbx_bitset_as_words(self._client.ctx, nm, out.ctypes.data_as(L.u64p), n.value, C.byref(n)))
+        return out[: n.value]
+
+    def asBitSetDev(self, d_words: int | None, cap_words: int, d_nwords: int, stream: int | None = None) -> None:
+        """asBitSet over device memory: min(cap_words, nwords) u64 words at d_words, the u64 nwords at d_nwords
+        (rbx_bitset_as_words_dev; does not wait)."""
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_as_words_dev(self._client.ctx, nm, d_words, int(cap_words), d_nwords, stream))
+
+    def setBitSet(self, words) -> None:
+        """set(BitSet.valueOf(words)): stores toByteArrayReverse's string, length() / 8 + 1 bytes -- one zero byte
+        for the empty BitSet (rbx_bitset_set_words)."""
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.uint64)).reshape(-1)
+        buf = w if w.size else np.zeros(1, np.uint64)
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_set_words(self._client.ctx, nm, buf.ctypes.data_as(L.u64p), w.size))
+
+    def setBitSetDev(self, d_words: int | None, nwords: int, stream: int | None = None) -> None:
+        """setBitSet of nwords u64 device words (rbx_bitset_set_words_dev; waits once on the stream)."""
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_set_words_dev(self._client.ctx, nm, d_words, int(nwords), stream))
+
+    # ---- set-bit enumeration: an engine extension, the inverse of setIndexes ----
+    def _members_args(self, start, end, unit):
+        if (start is None) != (end is None):
+            raise IllegalArgumentException("members takes both start and end, or neither")
+        nargs = 0 if start is None else 2
+        return nargs, self._java(start or 0, 64, "start"), self._java(end or 0, 64, "end"), self._unit(unit)
+
+    def members(self, start: int | None = None, end: int | None = None, unit="BYTE", skip: int = 0,
+                limit: int | None = None) -> np.ndarray:
+        """Engine extension (rbx_bitset_members): the positions of the set bits of bitCount(start, end, unit)'s
+        interval, ascending, as uint64 -- those of rank skip .. skip + limit - 1; limit=None means all.  Two calls: a
+        count-only one sizes the array (each builds the string's block directory; membersDev into a buffer of the
+        caller's is the one-call form)."""
+        nargs, s, e, u = self._members_args(start, end, unit)
+        if skip < 0 or (limit is not None and limit < 0):
+            raise IllegalArgumentException("skip and limit are not negative")
+        nm, _keep = self._n()
+        written, total = C.c_uint64(), C.c_uint64()
+        # size the page first, by a count-only call: the array then holds what is left, whatever limit says
+        _check(L.lib().rbx_bitset_members(self._client.ctx, nm, nargs, s, e, u, int(skip), 0, None,
+                                          C.byref(written), C.byref(total)))
+        cap = total.value - min(int(skip), total.value)
+        if limit is not None:
+            cap = min(cap, int(limit))
+        out = np.zeros(max(cap, 1), np.uint64)
+        if cap:
+            _check(L.lib().rbx_bitset_members(self._client.ctx, nm, nargs, s, e, u, int(skip), cap,
+                                              out.ctypes.data_as(L.u64p), C.byref(written), C.byref(total)))
+        return out[: written.value]
+
+    def membersDev(self, d_out: int | None, cap: int, d_counts: int, start: int | None = None, end: int | None = None,
+                   unit="BYTE", skip: int = 0, stream: int | None = None) -> None:
+        """members over device memory: up to cap u64 positions at d_out, {written, total} as two u64 at d_counts
+        (rbx_bitset_members_dev; waits once on the stream)."""
+        nargs, s, e, u = self._members_args(start, end, unit)
+        nm, _keep = self._n()
+        _check(L.lib().rbx_bitset_members_dev(self._client.ctx, nm, nargs, s, e, u, int(skip), int(cap), d_out,
+                                              d_counts, stream))
+
+    def toString(self) -> str:
+        """toString() :423-425 = asBitSet().toString(): java.util.BitSet's "{1, 5, 9}" form, built on members()."""
+        return "{" + ", ".join(str(int(p)) for p in self.members()) + "}"
+
     # ---- BITOP ------------------------------------------------------------------------------
     def _op(self, op: int, names) -> int:
         """opAsync :381-388 -- BITOP op name name others..; returns the reply (the result's length)"""
@@ -1044,6 +1118,67 @@ def bitset_range_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmd
 _engine_bitset_range_stream_call = bitset_range_stream_call
 
 
+def _members_cmds_array(rows):
+    """rows of (nargs, start, end, unit, skip, limit) -> an array of rbx_members_cmd; limit None = all"""
+    arr = (L.RbxMembersCmd * max(len(rows), 1))()
+    for a, (nargs, start, end, unit, skip, limit) in zip(arr, rows):
+        a.nargs, a.start, a.end, a.unit, a.skip = nargs, start, end, unit, skip
+        a.limit = (1 << 64) - 1 if limit is None else limit
+    return arr
+
+
+def bitset_members_stream_call(client: RedissonClient, names, cmd_key, rows, cap: int | None = None):
+    """rbx_bitset_members_stream over host arrays without raising: (rc, message, off, out, status).  Command i runs on
+    names[cmd_key[i]]; rows: (nargs, start, end, unit, skip, limit) with RBX_RANGE_* units, or an array of
+    RbxMembersCmd.  off: n + 1 uint64, exact whatever cap is; out: the first min(off[n], cap) positions of the
+    concatenation (cap None: all of them -- one counting call, then one with room for the total); status: uint8, 0xFF =
+    the command failed alone and yields nothing."""
+    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+    arr = rows if isinstance(rows, C.Array) else _members_cmds_array(list(rows))
+    n = key.size
+    if len(arr) < n or (not isinstance(rows, C.Array) and len(rows) != n):
+        raise IllegalArgumentException("cmd_key and rows have one entry per command")
+    names_arr, _keep = L.names_array(names)
+    off, status, total = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8), C.c_uint64()
+
+    def call(room, out):
+        return L.lib().rbx_bitset_members_stream(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p), arr, n, room,
+                                                 off.ctypes.data_as(L.u64p),
+                                                 None if out is None else out.ctypes.data_as(L.u64p),
+                                                 status.ctypes.data_as(L.u8p), C.byref(total))
+
+    out = None
+    rc = call(0, None) if cap is None else L.RBX_OK
+    if rc in (L.RBX_OK, L.RBX_E_WRONGTYPE):
+        room = int(total.value) if cap is None else int(cap)
+        if room or cap is not None:
+            out = np.zeros(max(room, 1), np.uint64)
+            rc = call(room, out)
+    msg = L.last_error() if rc != L.RBX_OK else ""
+    got = min(int(total.value), 0 if out is None else out.size)
+    return rc, msg, off, (np.zeros(0, np.uint64) if out is None else out[:got]), status[:n]
+
+
+def bitset_members_stream(client: RedissonClient, names, cmd_key, rows, cap: int | None = None):
+    """The members of many keys in one call (rbx_bitset_members_stream): (off, out, status); command i's positions are
+    out[off[i]: off[i + 1]].  Raises the first failing command's exception after every other command ran."""
+    rc, msg, off, out, status = bitset_members_stream_call(client, names, cmd_key, rows, cap)
+    raise_for(rc, msg)
+    return off, out, status
+
+
+def bitset_members_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmds: int, n: int, cap: int, d_off: int,
+                              d_out: int | None = None, d_status: int | None = None, stream: int | None = None) -> None:
+    """bitset_members_stream over device arrays (u32 keys, 40-byte rbx_members_cmd records, n + 1 u64 offsets, cap u64
+    positions, u8 status), enqueued on `stream`."""
+    arr, _keep = L.names_array(names)
+    _check(L.lib().rbx_bitset_members_stream_dev(client.ctx, arr, len(names), d_cmd_key, d_cmds, int(n), int(cap), d_off,
+                                                 d_out, d_status, stream))
+
+
+_engine_bitset_members_stream_call = bitset_members_stream_call
+
+
 class BatchFuture:
     """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
     methods), or raises what the command failed with."""
@@ -1078,15 +1213,17 @@ class _Queued:
     with its like where the grouped bit call is at hand and runs through fn otherwise, or a callable that runs
     singly.  A read query (range = (RBX_RANGE_*, bit, nargs, start, end, unit), fn; convert(reply) is its reply)
     coalesces with its like where the range stream call is at hand and runs through fn otherwise; a whole-string
-    BITCOUNT carries both a bitop and a range row.  convert: applied to a field or HLL command's reply."""
+    BITCOUNT carries both a bitop and a range row.  An enumeration (members = (nargs, start, end, unit, skip,
+    limit), fn) coalesces with its like where the members stream call is at hand and runs through fn otherwise.
+    convert: applied to a field or HLL command's reply."""
 
-    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group", "bitop", "range")
+    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group", "bitop", "range", "members")
 
     def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None, group=None,
-                 bitop=None, range=None):  # noqa: A002
+                 bitop=None, range=None, members=None):  # noqa: A002
         self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
         self.field, self.convert, self.hll, self.group, self.bitop = field, convert, hll, group, bitop
-        self.range = range
+        self.range, self.members = range, members
 
     def as_field(self):
         """the command as a BITFIELD sub-command: GETBIT / SETBIT are GET / SET of a u1, which leave the same
@@ -1229,8 +1366,19 @@ def _settle_range(c: _Queued, reply, status) -> None:
     c.future._set(error=RedisException(msg))
 
 
+MEMBERS_FAILED = 0xFF  # status of a command of rbx_bitset_members_stream that failed alone
+
+
+def _settle_members(c: _Queued, reply, status) -> None:
+    """an enumeration of a members run: its slice of the positions"""
+    if int(status) == MEMBERS_FAILED:
+        c.future._set(error=RedisException(_WRONGTYPE_MSG))
+    else:
+        c.future._set(reply)
+
+
 def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, hll_count_groups_call=None,
-              hll_merge_groups_call=None, bit_groups_call=None, range_stream_call=None):
+              hll_merge_groups_call=None, bit_groups_call=None, range_stream_call=None, members_stream_call=None):
     """Executes queued commands in submission order.  Every maximal run of consecutive bit commands, over any
     keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies).  With a
     field_stream_call, field commands join the runs, and a run that holds at least one of them is ONE
@@ -1246,8 +1394,9 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
     With a range_stream_call, every maximal run of consecutive read queries (ranged and whole-string BITCOUNT,
     BITPOS, STRLEN, length()), over any keys, is ONE range_stream_call(names, cmd_key, rows) -> (rc, message,
     replies, status); a whole-string BITCOUNT joins an open range run and otherwise starts a grouped bit run as
-    before.  A count run, a merge run, an HLL stream run, a grouped bit run, a range run and a bit / field run each
-    close the others.
+    before.  With a members_stream_call, every maximal run of consecutive enumerations (membersAsync), over any
+    keys, is ONE members_stream_call(names, cmd_key, rows) -> (rc, message, off, out, status).  A count run, a merge
+    run, an HLL stream run, a grouped bit run, a range run, a members run and a bit / field run each close the others.
     Every other command runs through its own call at its position.  Each command's future is set; returns
     (responses, first error)."""
     def joins(q):
@@ -1267,6 +1416,13 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
 
     def joins_ranges(q):
         return q.range is not None and range_stream_call is not None
+
+    def joins_members(q):
+        return q.members is not None and members_stream_call is not None
+
+    def members_call(run, names, keys):
+        rc, msg, off, out, status = members_stream_call(names, keys, [c.members for c in run])
+        return rc, msg, [out[int(off[i]): int(off[i + 1])] for i in range(len(run))], status
 
     def starts_ranges(q):  # a whole-string BITCOUNT starts a grouped bit run where that call is at hand
         return joins_ranges(q) and not joins_bitops(q)
@@ -1330,6 +1486,9 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
         elif starts_ranges(queue[i]):
             run = run_from(i, joins_ranges)
             error = _run_stream(run, ranges_call, alone, _settle_range)
+        elif joins_members(queue[i]):
+            run = run_from(i, joins_members)
+            error = _run_stream(run, members_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_members)
         elif joins_bitops(queue[i]):
             run = run_from(i, joins_bitops)
             error = _run_stream(run, bitops_call, alone, _settle_bitop)
@@ -1504,6 +1663,19 @@ class RBatchBitSet:
                          RBitSet._java(start or 0, 64, "start"), RBitSet._java(end or 0, 64, "end"), RBitSet._unit(unit))
         return self._range("bitPos", (bit, start, end, unit), row)
 
+    def membersAsync(self, start: int | None = None, end: int | None = None, unit="BYTE", skip: int = 0,
+                     limit: int | None = None) -> BatchFuture:
+        """Engine extension, RBitSet.members queued: consecutive ones, over any keys, travel together in one
+        rbx_bitset_members_stream call"""
+        if (start is None) != (end is None):
+            raise IllegalArgumentException("members takes both start and end, or neither")
+        if skip < 0 or (limit is not None and limit < 0):
+            raise IllegalArgumentException("skip and limit are not negative")
+        bitset, name = self._batch._bitset, self._name
+        row = (0 if start is None else 2, RBitSet._java(start or 0, 64, "start"), RBitSet._java(end or 0, 64, "end"),
+               RBitSet._unit(unit), int(skip), None if limit is None else int(limit))
+        return self._batch._add(_Queued(name, fn=lambda: bitset(name).members(start, end, unit, skip, limit), members=row))
+
     def toByteArrayAsync(self) -> BatchFuture:
         return self._single("toByteArray")
 
@@ -1619,12 +1791,12 @@ class RBatch:
     hll_count_groups_call / hll_merge_groups_call / bit_groups_call replace the engine's calls (tests); without a
     client and without a field_stream_call (an hll_stream_call, a grouped call), field (HLL, multi-key PFCOUNT /
     PFMERGE, BITOP / BITCOUNT) commands run singly through bitset(name) (hyperloglog(name, codec)).
-    range_stream_call carries the read queries (size / length / bitCount / bitPos); createBatch() passes the
-    engine's, and without one they run singly."""
+    range_stream_call carries the read queries (size / length / bitCount / bitPos) and members_stream_call the
+    enumerations (membersAsync); createBatch() passes the engine's, and without one they run singly."""
 
     def __init__(self, client: RedissonClient | None, stream_call=None, bitset=None, field_stream_call=None,
                  hll_stream_call=None, hyperloglog=None, hll_count_groups_call=None, hll_merge_groups_call=None,
-                 bit_groups_call=None, range_stream_call=None):
+                 bit_groups_call=None, range_stream_call=None, members_stream_call=None):
         self._client = client
         self._stream_call = stream_call or (lambda *a: bitset_stream_call(client, *a))
         if field_stream_call is None and client is not None:
@@ -1642,6 +1814,7 @@ class RBatch:
             bit_groups_call = lambda *a: _engine_bitset_op_groups_call(client, *a)  # noqa: E731
         self._bit_groups_call = bit_groups_call
         self._range_stream_call = range_stream_call
+        self._members_stream_call = members_stream_call
         self._hyperloglog = hyperloglog or (lambda name, codec: RHyperLogLog(client, name, codec))
         self._bitset = bitset or (lambda name: RBitSet(client, name))
         self._queue: list = []
@@ -1665,7 +1838,8 @@ class RBatch:
             raise IllegalStateException("Batch already executed!")
         self._executed = True
         responses, error = run_queue(self._queue, self._stream_call, self._field_stream_call, self._hll_stream_call,
-                                     *self._hll_groups_calls, self._bit_groups_call, self._range_stream_call)
+                                     *self._hll_groups_calls, self._bit_groups_call, self._range_stream_call,
+                                     self._members_stream_call)
         if error is not None:
             raise error
         return BatchResult(responses)

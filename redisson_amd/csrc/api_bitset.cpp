@@ -10,6 +10,7 @@
 #include "tunables.h"
 
 #include "field_rule.h"  // after rbx_device.h, whose RBX_HD it then uses
+#include "members_rule.h"
 
 namespace rbx {
 
@@ -977,6 +978,151 @@ static int range_stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t n
     return stream_names_check(c, names, nkeys);
 }
 
+// ---- set-bit enumeration and the java.util.BitSet exchange (rules: members_rule.h) ----
+static int members_args_check(rbx_ctx *c, rbx_name name, int nargs, int unit, uint64_t cap, const void *out,
+                              const void *counts, const void *counts2) {
+    if (!c || bad_name(name) || !counts || !counts2 || (cap && !out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (members_cmd_illegal(nargs, unit)) return fail(RBX_E_ILLEGAL_ARGUMENT, "nargs is 0 or 2, the unit BYTE or BIT");
+    return RBX_OK;
+}
+
+// The key of one enumeration and its interval, inside the caller's scope on `st`, with the call's one wait for
+// the length word.  *any = false: a missing key, an empty string or an empty interval, total = 0.
+static int members_plan(rbx_ctx *c, rbx_name name, int nargs, int64_t start, int64_t end, int unit, hipStream_t st,
+                        std::shared_ptr<Bitmap> *bm, uint64_t *len, uint64_t *lo, uint64_t *hi, bool *any) {
+    *any = false;
+    RBX_TRY(bitset_find(c, name_of(name), bm));
+    if (!*bm) return RBX_OK;
+    std::vector<uint64_t> lens;
+    RBX_TRY(bitset_lens(c, {bm->get()}, st, &lens));
+    *len = lens[0];
+    *any = members_interval(nargs, start, end, unit, *len, lo, hi);
+    return RBX_OK;
+}
+
+// The directory of the string (for this call only: any write would invalidate it), the page's state and counts,
+// and -- d_out given -- the page itself.  The state words stay in mem_state for a later members_expand.
+static int members_page_run(rbx_ctx *c, const Bitmap &bm, uint64_t len, uint64_t lo, uint64_t hi, uint64_t skip,
+                            uint64_t cap, uint64_t *d_out, unsigned long long *d_counts, hipStream_t st) {
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.rng_dir.reserve((bits_dir_blocks(len) + 1) * 8));
+    RBX_TRY(b.mem_state.reserve(64));
+    auto *d_dir = b.rng_dir.as<unsigned long long>();
+    launch_bits_directory(bm.d_words, len, d_dir, st);
+    launch_members_head(bm.d_words, len, lo, hi, skip, cap, d_dir, b.mem_state.as<unsigned long long>(), d_counts, st);
+    if (d_out) launch_members_expand(bm.d_words, len, lo, hi, d_dir, b.mem_state.as<unsigned long long>(), d_out, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+// ---- the enumeration over many keys (rbx_bitset_members_stream) ----
+static std::atomic<uint32_t> g_members_last[4];  // rbx_bench_members_last shows them (as g_rangestream_last)
+static const char *const kMembersIllegalMsg = "a command's key is not below nkeys, its nargs is not 0 or 2, or its unit is unknown";
+
+// A batch of n > 0 commands over device arrays inside the caller's scope on `st`: d_off (n + 1 words) always in
+// full, d_out (nullable with cap 0: count only) as far as below cap, d_status nullable.  *failed = some command ran
+// on a key of another type.  As range_stream_run: the names resolved once and a table that creates nothing; then per
+// chunk the count kernel with its one wait for the summary, the tiles of the listed commands, the scan of the chunk's
+// yields in place (k_bits_block_scan) plus the carry -- the chunk before's total, kept on the device -- and the two
+// expand kernels.
+static int members_stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_key,
+                              const rbx_members_cmd *d_cmds, uint64_t n, uint64_t cap, uint64_t *d_off, uint64_t *d_out,
+                              uint8_t *d_status, hipStream_t st, bool *failed) {
+    *failed = false;
+    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, kMembersIllegalMsg);
+    BitsetScratch &b = c->dev->bits;
+    StreamKeys sk;
+    sk.nkeys = nkeys;
+    sk.kinfo.assign((size_t)nkeys * 5, 0);
+    stream_names_resolve(c, names, nkeys, KType::Bitmap, &sk.nm, sk.canon(), sk.wrong(), [](uint32_t, const Entry &) {});
+    const std::vector<unsigned long long> no_writes(nkeys, 0);
+    const BitKey *d_tab;
+    bool writes;
+    RBX_TRY(stream_keys_table(c, sk, no_writes.data(), st, &d_tab, &writes));
+    uint64_t max_bytes = 0;
+    for (const BitKey &k : b.bst_table.host) max_bytes = std::max(max_bytes, k.cap_bits >> 3);
+
+    const uint32_t tile = g_tune.members_tile, short_max = g_tune.members_short_max;
+    const int lanes = g_tune.members_lanes;
+    const uint64_t chunk = std::min<uint64_t>(g_tune.members_chunk, ((1ULL << kRsTileBits) - 1) / (max_bytes / tile + 2));
+    RBX_TRY(b.rs_long.reserve(std::min(n, chunk) * 8));
+    RBX_TRY(b.rs_sum.reserve(kMsSummaryWords * 8));
+    RBX_TRY(b.mem_state.reserve(64));
+    auto *d_sum = b.rs_sum.as<unsigned long long>(), *d_long = b.rs_long.as<unsigned long long>();
+    auto *d_carry = b.mem_state.as<unsigned long long>() + 3, *off = (unsigned long long *)d_off;
+    unsigned long long *w = c->dev->stage.words();
+    HIP_TRY(hipMemsetAsync(d_carry, 0, 8, st));
+    uint64_t stats[4] = {0, 0, 0, 0};
+    for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
+        const uint32_t m = (uint32_t)std::min(chunk, n - i0);
+        HIP_TRY(hipMemsetAsync(d_sum, 0xFF, 8, st));
+        HIP_TRY(hipMemsetAsync(d_sum + 1, 0, (kMsSummaryWords - 1) * 8, st));
+        launch_members_count(lanes, d_tab, d_key + i0, d_cmds + i0, m, nkeys, short_max, tile, off + i0,
+                             d_status ? d_status + i0 : nullptr, d_sum, d_long, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w, d_sum, kMsSummaryWords * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));  // the chunk's one wait
+        ++stats[kRsWaits];
+        if (w[kMsFlags] & kMsIllegal) return fail(RBX_E_ILLEGAL_ARGUMENT, kMembersIllegalMsg);
+        if (w[kMsFirstWrong] != ~0ULL) *failed = true;
+        const uint64_t nlong = w[kMsLong] >> kRsTileBits, tiles = w[kMsLong] & ((1ULL << kRsTileBits) - 1);
+        stats[kRsShortDone] += m - nlong;
+        stats[kRsLongCmds] += nlong;
+        stats[kRsTiles] += tiles;
+        if (nlong) {
+            RBX_TRY(b.mem_tiles.reserve(tiles * 8));
+            launch_members_tiles_count(d_tab, d_key + i0, d_cmds + i0, tile, d_long, (uint32_t)nlong, tiles,
+                                       b.mem_tiles.as<unsigned long long>(), off + i0, st);
+        }
+        launch_bits_scan(off + i0, m, st);  // off[i0 + m] = the chunk's total
+        launch_members_carry(off + i0, (uint64_t)m + 1, d_carry, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(d_carry, off + i0 + m, 8, hipMemcpyDeviceToDevice, st));  // the next chunk overwrites that word
+        if (d_out && cap) {
+            launch_members_expand_short(lanes, d_tab, d_key + i0, d_cmds + i0, m, short_max, off + i0, d_out, cap, st);
+            if (nlong)
+                launch_members_expand_tiles(d_tab, d_key + i0, d_cmds + i0, tile, d_long, (uint32_t)nlong, tiles,
+                                            b.mem_tiles.as<unsigned long long>(), off + i0, d_out, cap, st);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    for (int i = 0; i < 4; ++i) g_members_last[i] = (uint32_t)std::min<uint64_t>(stats[i], 0xFFFFFFFFu);
+    return RBX_OK;
+}
+
+static int members_stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, uint64_t n, uint64_t cap,
+                                     const void *key, const void *cmds, const void *off, const void *out) {
+    if ((n && (!key || !cmds)) || !off || (cap && !out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n > (1ULL << 32)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes at most 2^32 commands");
+    return stream_names_check(c, names, nkeys);
+}
+
+// set(BitSet) of n device words inside the caller's scope on `st`: one wait, for the highest set bit; then the key
+// is replaced as bitmap_import replaces it
+static int words_store(rbx_ctx *c, rbx_name name, const uint64_t *d_words, uint64_t n, hipStream_t st) {
+    unsigned long long h1 = 0;
+    if (n) {
+        RBX_TRY(c->dev->bits.mem_state.reserve(64));
+        auto *d_h = c->dev->bits.mem_state.as<unsigned long long>() + 7;
+        HIP_TRY(hipMemsetAsync(d_h, 0, 8, st));
+        launch_words_highest(d_words, n, d_h, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->dev->stage.words(), d_h, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        h1 = *c->dev->stage.words();
+    }
+    if (h1 && words_bit_illegal(h1 - 1))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "the highest set bit must be below 2^31 - 1 (java.util.BitSet.length() is an int)");
+    const uint64_t bytes = words_string_len(h1 != 0, h1 ? h1 - 1 : 0);
+    const std::string nm = name_of(name);
+    std::shared_ptr<Bitmap> b;
+    RBX_TRY(new_bitmap(c, import_bits(c, nm, bytes), st, &b));
+    launch_words_import(d_words, n, bytes, b->d_words, b->d_len, st);
+    HIP_TRY(hipGetLastError());
+    c->ks.put(nm, Entry{KType::Bitmap, nullptr, b, nullptr});
+    return RBX_OK;
+}
+
 }  // namespace rbx
 
 using namespace rbx;
@@ -1325,6 +1471,223 @@ int rbx_bitset_export_n(rbx_ctx *c, rbx_name name, uint8_t *out, uint64_t cap, u
 int rbx_bitset_import_n(rbx_ctx *c, rbx_name name, const uint8_t *bytes, uint64_t len) {
     if (!c || bad_name(name) || (len && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
     return bitmap_import(c, name_of(name), bytes, len);
+}
+
+int rbx_bitset_as_words_dev(rbx_ctx *c, rbx_name name, uint64_t *d_words, uint64_t cap_words, uint64_t *d_nwords,
+                            void *stream) {
+    if (!c || bad_name(name) || !d_nwords || (cap_words && !d_words)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name_of(name), &bm));
+    HIP_TRY(hipMemsetAsync(d_nwords, 0, 8, st));
+    if (!bm) return RBX_OK;
+    launch_words_last(bm->d_words, bm->cap_bytes, bm->d_len, (unsigned long long *)d_nwords, st);
+    launch_words_export(bm->d_words, bm->cap_bytes, (const unsigned long long *)d_nwords, cap_words, d_words, st);
+    HIP_TRY(hipGetLastError());
+    return RBX_OK;
+}
+
+int rbx_bitset_as_words(rbx_ctx *c, rbx_name name, uint64_t *words, uint64_t cap_words, uint64_t *nwords) {
+    if (!c || bad_name(name) || !nwords || (cap_words && !words)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    std::shared_ptr<Bitmap> bm;
+    RBX_TRY(bitset_find(c, name_of(name), &bm));
+    *nwords = 0;
+    if (!bm) return RBX_OK;
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.mem_state.reserve(64));
+    auto *d_n = b.mem_state.as<unsigned long long>() + 6;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, st));
+    launch_words_last(bm->d_words, bm->cap_bytes, bm->d_len, d_n, st);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    *nwords = read_dev_u64(c, d_n, &rc);
+    RBX_TRY(rc);
+    const uint64_t m = std::min(cap_words, *nwords);
+    if (m == 0) return RBX_OK;
+    RBX_TRY(b.mem_buf.reserve(m * 8));
+    launch_words_export(bm->d_words, bm->cap_bytes, d_n, m, b.mem_buf.as<uint64_t>(), st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(words, b.mem_buf.p, m * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RBX_OK;
+}
+
+int rbx_bitset_set_words_dev(rbx_ctx *c, rbx_name name, const uint64_t *d_words, uint64_t nwords, void *stream) {
+    if (!c || bad_name(name) || (nwords && !d_words)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    return words_store(c, name, d_words, nwords, st);
+}
+
+int rbx_bitset_set_words(rbx_ctx *c, rbx_name name, const uint64_t *words, uint64_t nwords) {
+    if (!c || bad_name(name) || (nwords && !words)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    while (nwords && words[nwords - 1] == 0) --nwords;  // trailing zero words are not uploaded
+    if (nwords > (1ULL << 25)) return fail(RBX_E_ILLEGAL_ARGUMENT, "the highest set bit must be below 2^31 - 1 (java.util.BitSet.length() is an int)");
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    RBX_TRY(c->dev->bits.mem_buf.reserve(nwords * 8));
+    if (nwords) HIP_TRY(hipMemcpyAsync(c->dev->bits.mem_buf.p, words, nwords * 8, hipMemcpyHostToDevice, st));
+    RBX_TRY(words_store(c, name, c->dev->bits.mem_buf.as<uint64_t>(), nwords, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RBX_OK;
+}
+
+int rbx_bitset_as_words_of(const uint8_t *bytes, uint64_t len, uint64_t *words, uint64_t cap_words, uint64_t *nwords) {
+    if ((len && !bytes) || !nwords || (cap_words && !words)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    uint64_t last = len;  // the bytes up to the last non-zero one
+    while (last && bytes[last - 1] == 0) --last;
+    *nwords = words_in_use(last != 0, last ? (last - 1) / 8 : 0);
+    const uint64_t m = std::min(cap_words, *nwords);
+    for (uint64_t w = 0; w < m; ++w) {
+        uint64_t v = 0;
+        for (uint64_t k = 0; k < 8 && 8 * w + k < last; ++k) v |= (uint64_t)(rev_bytes(bytes[8 * w + k]) & 0xFFu) << (8 * k);
+        words[w] = v;
+    }
+    return RBX_OK;
+}
+
+int rbx_bitset_bytes_of_words(const uint64_t *words, uint64_t nwords, uint8_t *out, uint64_t cap, uint64_t *len) {
+    if ((nwords && !words) || !len || (cap && !out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    while (nwords && words[nwords - 1] == 0) --nwords;
+    const uint64_t highest = nwords ? words_highest(nwords - 1, words[nwords - 1]) : 0;
+    if (nwords && words_bit_illegal(highest))
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "the highest set bit must be below 2^31 - 1 (java.util.BitSet.length() is an int)");
+    *len = words_string_len(nwords != 0, highest);
+    const uint64_t m = std::min(cap, *len);
+    for (uint64_t i = 0; i < m; ++i)
+        out[i] = i / 8 < nwords ? (uint8_t)rev_bytes((uint32_t)(words[i / 8] >> (8 * (i % 8))) & 0xFFu) : 0;
+    return RBX_OK;
+}
+
+int rbx_bitset_members_dev(rbx_ctx *c, rbx_name name, int nargs, int64_t start, int64_t end, int unit, uint64_t skip,
+                           uint64_t cap, uint64_t *d_out, uint64_t *d_counts, void *stream) {
+    RBX_TRY(members_args_check(c, name, nargs, unit, cap, d_out, d_counts, d_counts));
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t len, lo, hi;
+    bool any;
+    RBX_TRY(members_plan(c, name, nargs, start, end, unit, st, &bm, &len, &lo, &hi, &any));
+    if (!any) {
+        HIP_TRY(hipMemsetAsync(d_counts, 0, 16, st));
+        return RBX_OK;
+    }
+    return members_page_run(c, *bm, len, lo, hi, skip, cap, cap ? d_out : nullptr, (unsigned long long *)d_counts, st);
+}
+
+int rbx_bitset_members(rbx_ctx *c, rbx_name name, int nargs, int64_t start, int64_t end, int unit, uint64_t skip,
+                       uint64_t cap, uint64_t *out, uint64_t *written, uint64_t *total) {
+    RBX_TRY(members_args_check(c, name, nargs, unit, cap, out, written, total));
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t len, lo, hi;
+    bool any;
+    RBX_TRY(members_plan(c, name, nargs, start, end, unit, st, &bm, &len, &lo, &hi, &any));
+    *written = *total = 0;
+    if (!any) return RBX_OK;
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.mem_state.reserve(64));
+    auto *d_counts = b.mem_state.as<unsigned long long>() + 4;  // behind the state words
+    RBX_TRY(members_page_run(c, *bm, len, lo, hi, skip, cap, nullptr, d_counts, st));
+    unsigned long long *w = c->dev->stage.words();
+    HIP_TRY(hipMemcpyAsync(w, d_counts, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *written = w[0];
+    *total = w[1];
+    if (*written == 0) return RBX_OK;
+    RBX_TRY(b.mem_buf.reserve(*written * 8));  // the page's size is known only now
+    launch_members_expand(bm->d_words, len, lo, hi, b.rng_dir.as<unsigned long long>(), b.mem_state.as<unsigned long long>(),
+                          b.mem_buf.as<uint64_t>(), st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b.mem_buf.p, *written * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RBX_OK;
+}
+
+int rbx_bitset_members_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                                  const rbx_members_cmd *d_cmds, uint64_t n, uint64_t cap, uint64_t *d_off, uint64_t *d_out,
+                                  uint8_t *d_status, void *stream) {
+    RBX_TRY(members_stream_args_check(c, names, nkeys, n, cap, d_cmd_key, d_cmds, d_off, d_out));
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    if (n == 0) {  // no command is sent
+        HIP_TRY(hipMemsetAsync(d_off, 0, 8, st));
+        return RBX_OK;
+    }
+    bool failed;
+    RBX_TRY(members_stream_run(c, names, nkeys, d_cmd_key, d_cmds, n, cap, d_off, d_out, d_status, st, &failed));
+    return failed ? fail(RBX_E_WRONGTYPE, kWrongTypeMsg) : RBX_OK;
+}
+
+int rbx_bitset_members_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                              const rbx_members_cmd *cmds, uint64_t n, uint64_t cap, uint64_t *off, uint64_t *out,
+                              uint8_t *status, uint64_t *total) {
+    if (!total) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_TRY(members_stream_args_check(c, names, nkeys, n, cap, cmd_key, cmds, off, out));
+    *total = off[0] = 0;
+    if (n == 0) return RBX_OK;
+    for (uint64_t i = 0; i < n; ++i)  // the caller's errors, before any device work
+        if (cmd_key[i] >= nkeys || members_cmd_illegal(cmds[i].nargs, cmds[i].unit))
+            return fail(RBX_E_ILLEGAL_ARGUMENT, kMembersIllegalMsg);
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.rs_cmds.reserve(n * (sizeof(rbx_members_cmd) + 4)));  // commands | keys
+    RBX_TRY(b.rs_out.reserve((n + 1) * 8));
+    if (status) RBX_TRY(b.rs_status.reserve(n));
+    rbx_members_cmd *d_cmds = b.rs_cmds.as<rbx_members_cmd>();
+    uint32_t *d_key = (uint32_t *)(d_cmds + n);
+    uint64_t *d_off = b.rs_out.as<uint64_t>();
+    uint8_t *d_status = status ? b.rs_status.as<uint8_t>() : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_cmds, cmds, n * sizeof(rbx_members_cmd), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_key, cmd_key, n * 4, hipMemcpyHostToDevice, st));
+    // The output's size is known only with the offsets: a counting run, then -- when there is anything to write --
+    // the same run again with the positions' buffer.  (The device form, whose caller owns the buffer, runs once.)
+    bool failed;
+    RBX_TRY(members_stream_run(c, names, nkeys, d_key, d_cmds, n, 0, d_off, nullptr, d_status, st, &failed));
+    HIP_TRY(hipMemcpyAsync(off, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *total = off[n];
+    const uint64_t wr = std::min(*total, cap);
+    if (wr) {
+        RBX_TRY(b.mem_buf.reserve(wr * 8));
+        RBX_TRY(members_stream_run(c, names, nkeys, d_key, d_cmds, n, wr, d_off, b.mem_buf.as<uint64_t>(), nullptr, st, &failed));
+        HIP_TRY(hipMemcpyAsync(out, b.mem_buf.p, wr * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return failed ? fail(RBX_E_WRONGTYPE, kWrongTypeMsg) : RBX_OK;
+}
+
+int rbx_bench_members_last(uint32_t out[4]) {
+    if (!out) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    for (int i = 0; i < 4; ++i) out[i] = g_members_last[i];
+    return RBX_OK;
+}
+
+int rbx_bitset_members_of(const uint8_t *bytes, uint64_t len, int missing, const rbx_members_cmd *cmd, uint64_t cap,
+                          uint64_t *out, uint64_t *written, uint64_t *total) {
+    if ((len && !bytes) || !cmd || !written || !total || (cap && !out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (members_cmd_illegal(cmd->nargs, cmd->unit)) return fail(RBX_E_ILLEGAL_ARGUMENT, "nargs is 0 or 2, the unit BYTE or BIT");
+    *written = *total = 0;
+    uint64_t lo, hi;
+    if (!members_interval(cmd->nargs, cmd->start, cmd->end, cmd->unit, missing ? 0 : len, &lo, &hi)) return RBX_OK;
+    uint64_t ones = 0;
+    for (uint64_t p = lo; p <= hi; ++p) ones += (bytes[p >> 3] >> (7 - (p & 7))) & 1;
+    uint64_t first, count, rank = 0;
+    members_page(ones, cmd->skip, cmd->limit, cap, &first, &count);
+    for (uint64_t p = lo; p <= hi && rank < first + count; ++p) {
+        if (!((bytes[p >> 3] >> (7 - (p & 7))) & 1)) continue;
+        if (rank >= first) out[rank - first] = p;
+        ++rank;
+    }
+    *written = count;
+    *total = ones;
+    return RBX_OK;
 }
 
 int rbx_bitset_rename(rbx_ctx *c, rbx_name name, rbx_name new_name) {

@@ -12,6 +12,9 @@
 
 namespace rbx {
 
+constexpr uint32_t kBlockBits = 32768;  // a directory block (launch_bits_directory): 4 KiB of the string
+constexpr int kBlockLog2 = 15;
+
 // string positions >= a / <= b of a byte-swapped word (a, b relative to the word's first position)
 __device__ __forceinline__ uint32_t pos_from(int64_t a) { return a <= 0 ? ~0u : (a >= 32 ? 0u : ~0u >> (int)a); }
 __device__ __forceinline__ uint32_t pos_to(int64_t b) { return b < 0 ? 0u : (b >= 31 ? ~0u : ~0u << (31 - (int)b)); }
@@ -66,6 +69,19 @@ __device__ __forceinline__ uint64_t wave_find(const uint4 *__restrict__ vecs, ui
         }
     }
     return kBitsNone;
+}
+
+// ---- what the kernels over many strings share (rangestream_kernels.hip, members_kernels.hip) ----
+// the string of command (k, c) as the kernels read it: its length (clamped to the allocation, which the host
+// keeps at or above it) and whether the key is missing
+__device__ __forceinline__ uint64_t rs_len(const BitKey &k, bool *missing) {
+    *missing = k.len == nullptr;
+    return *missing ? 0 : min((uint64_t)*k.len, k.cap_bits >> 3);
+}
+
+// the tiles of an interval: its vectors cut into runs of tile_vecs, from the interval's first vector
+__device__ __forceinline__ uint64_t rs_tiles(uint64_t lo, uint64_t hi, uint32_t tile_lg) {
+    return (((hi >> 7) - (lo >> 7)) >> (tile_lg - 4)) + 1;
 }
 
 }  // namespace rbx

@@ -16,8 +16,7 @@
 
 namespace rbx {
 
-constexpr uint32_t kBlockBits = 32768;  // a directory block: 4 KiB of the string
-constexpr int kBlockLog2 = 15;
+// (kBlockBits / kBlockLog2, the directory's 4 KiB block: bitrange_device.h)
 
 // ---------------------------------------------------------------------------------
 // 1. BITCOUNT over one interval, the whole GPU: k_bitcount's grid-stride sweep over the vectors of the
@@ -296,6 +295,10 @@ void launch_bits_directory(const uint32_t *words, uint64_t len, unsigned long lo
     hipLaunchKernelGGL(k_bits_block_ones, dim3(std::min<uint32_t>((nblocks + 3) / 4, kMaxGrid)), dim3(256), 0, st,
                        (const uint4 *)words, (len + 15) >> 4, nblocks, d_dir);
     hipLaunchKernelGGL(k_bits_block_scan, dim3(1), dim3(1024), 0, st, d_dir, nblocks);
+}
+
+void launch_bits_scan(unsigned long long *d_counts, uint32_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_bits_block_scan, dim3(1), dim3(1024), 0, st, d_counts, n);
 }
 
 void launch_bits_ranges_summary(const int64_t *d_starts, const int64_t *d_ends, uint64_t n, int unit, bool pos,

@@ -21,17 +21,7 @@ namespace rbx {
 
 constexpr uint8_t kRsFailedStatus = 0xFF;
 
-// the string of command (k, c) as the kernels read it: its length (clamped to the allocation, which the host
-// keeps at or above it) and whether the key is missing
-__device__ __forceinline__ uint64_t rs_len(const BitKey &k, bool *missing) {
-    *missing = k.len == nullptr;
-    return *missing ? 0 : min((uint64_t)*k.len, k.cap_bits >> 3);
-}
-
-// the tiles of an interval: its vectors cut into runs of tile_vecs, from the interval's first vector
-__device__ __forceinline__ uint64_t rs_tiles(uint64_t lo, uint64_t hi, uint32_t tile_lg) {
-    return (((hi >> 7) - (lo >> 7)) >> (tile_lg - 4)) + 1;
-}
+// (rs_len, the string of a table entry, and rs_tiles, the tiles of an interval: bitrange_device.h)
 
 // ---------------------------------------------------------------------------------
 // 1. One group of G lanes per command; the grid strides over the commands, and the trip count is the same in

@@ -343,6 +343,10 @@ static const TuneRow kTuneRows[] = {
     {"rangestream_short_max", POW2(64, 1 << 20), false, FIELD(rangestream_short_max)},
     {"rangestream_tile", POW2(4096, 1 << 20), false, FIELD(rangestream_tile)},
     {"rangestream_chunk", RANGE(1, 1 << 30), false, FIELD(rangestream_chunk)},  // positions in a chunk are 30-bit
+    {"members_lanes", ONE_OF(4, 8, 16, 32, 64), false, FIELD(members_lanes)},
+    {"members_short_max", POW2(64, 1 << 20), false, FIELD(members_short_max)},
+    {"members_tile", POW2(4096, 1 << 20), false, FIELD(members_tile)},
+    {"members_chunk", RANGE(1, 1 << 30), false, FIELD(members_chunk)},
 };
 #undef RANGE
 #undef ONE_OF

@@ -401,6 +401,13 @@ struct BitsetScratch {
     // the read queries over many keys (rbx_bitset_range_stream): the host form's uploaded commands |
     // keys, its replies and status, a chunk's summary words, and its long list (8 bytes per command of a chunk)
     DevBuf rs_cmds, rs_out, rs_status, rs_sum, rs_long;
+    // set-bit enumeration and the BitSet exchange (rbx_bitset_members / _as_words / _set_words): the
+    // page's state words | the host forms' counts, and the host forms' positions or words on the device (the
+    // enumeration's directory is rng_dir)
+    DevBuf mem_state, mem_buf;
+    // the enumeration over many keys (rbx_bitset_members_stream) shares bst_table, rs_cmds (commands | keys), rs_out
+    // (the host form's offsets), rs_status, rs_sum and rs_long with the range stream; its own: the tiles' counts
+    DevBuf mem_tiles;
 };
 
 // Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).

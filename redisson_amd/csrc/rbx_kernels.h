@@ -399,6 +399,8 @@ void launch_bits_pos(const uint32_t *words, uint64_t lo, uint64_t hi, int bit, u
                      unsigned long long *d_state, int64_t none_reply, int64_t *d_out, hipStream_t st);
 // d_dir[b] = the ones below 4 KiB block b, b = 0 .. bits_dir_blocks(len) (len > 0)
 void launch_bits_directory(const uint32_t *words, uint64_t len, unsigned long long *d_dir, hipStream_t st);
+// the directory's scan alone: d_counts[0 .. n) := their exclusive prefix sums, d_counts[n] := their sum
+void launch_bits_scan(unsigned long long *d_counts, uint32_t n, hipStream_t st);
 // d_out3 (zeroed by the caller) = {*d_len, sum of bits_interval_bytes, their maximum}; d_ends nullable (pos)
 void launch_bits_ranges_summary(const int64_t *d_starts, const int64_t *d_ends, uint64_t n, int unit, bool pos,
                                 const unsigned long long *d_len, unsigned long long *d_out3, hipStream_t st);
@@ -408,6 +410,58 @@ void launch_bits_count_ranges(const uint32_t *words, uint64_t len, const int64_t
                               uint64_t n, int unit, const unsigned long long *d_dir, uint64_t *d_out, hipStream_t st);
 void launch_bits_pos_ranges(const uint32_t *words, uint64_t len, int bit, const int64_t *d_starts, const int64_t *d_ends,
                             uint64_t n, int unit, const unsigned long long *d_dir, int64_t *d_out, hipStream_t st);
+
+// ---- members_kernels.hip
+// Set-bit enumeration and the java.util.BitSet exchange (rules: members_rule.h).
+// [lo, hi] is normalised over a string of len > 0 bytes and d_dir is launch_bits_directory's over that string.
+// d_state (kMembersStateWords u64) = {the ones below lo, the page's first rank, its end rank} for the expand
+// kernel; d_counts = {written, total} with written = min(cap, total - min(skip, total)).
+constexpr size_t kMembersStateWords = 3;
+constexpr unsigned kMembersMaxGrid = 8192;  // the expand kernel's grid-stride cap: a block outside the page costs two loads
+void launch_members_head(const uint32_t *words, uint64_t len, uint64_t lo, uint64_t hi, uint64_t skip, uint64_t cap,
+                         const unsigned long long *d_dir, unsigned long long *d_state, unsigned long long *d_counts,
+                         hipStream_t st);
+// d_out[r - first] = the position of the interval's one of rank r, for the page's ranks [first, end) of d_state
+void launch_members_expand(const uint32_t *words, uint64_t len, uint64_t lo, uint64_t hi, const unsigned long long *d_dir,
+                           const unsigned long long *d_state, uint64_t *d_out, hipStream_t st);
+// *d_nwords (zeroed by the caller) = BitSet's words in use of the string at `words` (its length: *d_len)
+void launch_words_last(const uint32_t *words, uint64_t cap_bytes, const unsigned long long *d_len,
+                       unsigned long long *d_nwords, hipStream_t st);
+// d_out[0 .. min(cap_words, *d_nwords)) = those words, *d_nwords read on the device
+void launch_words_export(const uint32_t *words, uint64_t cap_bytes, const unsigned long long *d_nwords, uint64_t cap_words,
+                         uint64_t *d_out, hipStream_t st);
+// *d_highest1 (zeroed by the caller) = 1 + the highest set bit of the n words, 0 = none
+void launch_words_highest(const uint64_t *d_words, uint64_t n, unsigned long long *d_highest1, hipStream_t st);
+// the string of `bytes` bytes of the n words into a zeroed allocation of at least that size; *d_len = bytes
+void launch_words_import(const uint64_t *d_words, uint64_t n, uint64_t bytes, uint32_t *words, unsigned long long *d_len,
+                         hipStream_t st);
+
+// Many keys (rbx_bitset_members_stream): command i is (d_key[i], d_cmds[i]) over the BitKey table below, n <= 2^30
+// commands per chunk.  The summary words (u64) of one chunk: the first command on a key of another type (the caller
+// sets it to ~0 and the others to 0), the flags, and the range stream's list word (long commands << kRsTileBits | tiles).
+struct BitKey;
+enum { kMsFirstWrong = 0, kMsFlags = 1, kMsLong = 2, kMsSummaryWords = 3 };
+constexpr uint32_t kMsIllegal = 1;
+// d_off[i] = command i's yield (0 for a listed long command, whose (first tile << kRsPosBits | position) goes to
+// d_long, ascending); d_status[i] (nullable) = 0, or 0xFF on a key of another type
+void launch_members_count(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_members_cmd *d_cmds, uint32_t n,
+                          uint32_t nkeys, uint32_t short_max, uint32_t tile_bytes, unsigned long long *d_off,
+                          uint8_t *d_status, unsigned long long *d_sum, unsigned long long *d_long, hipStream_t st);
+// d_tiles[t] = the ones of its command before flattened tile t (ntiles entries); d_off[i] = the yield of each listed command
+void launch_members_tiles_count(const BitKey *d_tab, const uint32_t *d_key, const rbx_members_cmd *d_cmds, uint32_t tile_bytes,
+                                const unsigned long long *d_long, uint32_t nlong, uint64_t ntiles,
+                                unsigned long long *d_tiles, unsigned long long *d_off, hipStream_t st);
+// d_off[0 .. m1) += *d_carry
+void launch_members_carry(unsigned long long *d_off, uint64_t m1, const unsigned long long *d_carry, hipStream_t st);
+// the positions of the commands not listed / listed, from the final d_off (n + 1 entries): d_out[d_off[i] ..
+// d_off[i + 1]) as far as below cap
+void launch_members_expand_short(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_members_cmd *d_cmds,
+                                 uint32_t n, uint32_t short_max, const unsigned long long *d_off, uint64_t *d_out,
+                                 uint64_t cap, hipStream_t st);
+void launch_members_expand_tiles(const BitKey *d_tab, const uint32_t *d_key, const rbx_members_cmd *d_cmds,
+                                 uint32_t tile_bytes, const unsigned long long *d_long, uint32_t nlong, uint64_t ntiles,
+                                 const unsigned long long *d_tiles, const unsigned long long *d_off, uint64_t *d_out,
+                                 uint64_t cap, hipStream_t st);
 
 // ---- bitstream_kernels.hip
 // The ordered GETBIT / SETBIT stream over many strings (rbx_bitset_stream).  Commands are

@@ -161,6 +161,23 @@ struct Tunables {
     // "rangestream_chunk": commands per chunk, 1 .. 2^30 (8 bytes of long list per command of a chunk; each chunk
     // has its own summary and wait)
     std::atomic<uint64_t> rangestream_chunk{1 << 25};
+
+    // ---- set-bit enumeration over many keys (api_bitset.cpp) ----
+    // The four knobs of rbx_bitset_members_stream mirror the range stream's.  All exact.
+    // "members_lanes": the lanes G of the group that counts and expands one short command, 4, 8, 16, 32 or 64.
+    // Measured (DESIGN 11.11 row f): on 20,000 strings of 46 bytes the five settings lie within 0.5 % (the call is
+    // host-bound there); 16 is kept.
+    std::atomic<int> members_lanes{16};
+    // "members_short_max": the bytes of the longest interval a lane group walks alone, a power of two in 64 .. 1 MiB;
+    // a longer one is cut into tiles for the whole device.  4096 is a guess: no measurement decides it (DESIGN 11.11
+    // row f's strings lie on one side of every setting).
+    std::atomic<uint32_t> members_short_max{4096};
+    // "members_tile": the bytes of a tile of a long interval, a power of two in 4 KiB .. 1 MiB.  Measured (DESIGN 11.11
+    // row f): 4 KiB tiles cost 29 %, 1 MiB tiles 10 % against 64 KiB.
+    std::atomic<uint32_t> members_tile{65536};
+    // "members_chunk": commands per chunk, 1 .. 2^30 (8 bytes of long list per command of a chunk; each chunk has its
+    // own summary and wait, and the offsets carry across chunks on the device).  2^25 is the range stream's: not measured.
+    std::atomic<uint64_t> members_chunk{1 << 25};
 };
 
 constexpr uint32_t kHllGroupsFillBlocks = 256;
