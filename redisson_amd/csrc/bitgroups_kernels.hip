@@ -1,7 +1,7 @@
 // bitgroups_kernels.hip -- many BITOPs and many BITCOUNTs of a combination in one launch (rbx_bitset_op_groups):
 // what RBitSet.and / or / xor / not and cardinality (M/RedissonBitSet.java:362-388, :462-464, :482-484) send one
 // command each, and what a batch queues through RBatch.getBitSet(name) (M/RedissonBatch.java:182-184).  DESIGN
-// section 11.9 has the rules; the phases of a call, the forwarded counts and every length are api_bitset.cpp's.
+// section 11.9 has the rules; the phases of a call, the forwarded counts and every length are api_bitset_multi.cpp's.
 //
 // Groups span six orders of magnitude -- ten thousand strings of 128 bytes, or one of 512 MiB -- so a launch is a
 // segmented sweep.  The host, which knows every length, cuts each group's span into tiles of T bytes (a power of

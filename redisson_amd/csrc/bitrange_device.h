@@ -84,4 +84,53 @@ __device__ __forceinline__ uint64_t rs_tiles(uint64_t lo, uint64_t hi, uint32_t 
     return (((hi >> 7) - (lo >> 7)) >> (tile_lg - 4)) + 1;
 }
 
+// The two tiers' list.  A group LISTS a long interval: one atomic on the chunk's list word (long
+// commands << kRsTileBits | tiles) takes a list slot and the command's tile numbers together, so entry j = first
+// tile << kRsPosBits | position ascends in j in both halves, and a later kernel finds the command of flattened
+// tile t by binary search.  Invariant: that tile is one of the command's (own < rs_tiles of its interval), both
+// being worked out from the same command, table entry and tile size; no kernel tests it.
+constexpr uint8_t kRsFailedStatus = 0xFF;  // the status of a command that failed alone
+
+// lists command i (its position in the chunk) with the tiles of [lo, hi]; one lane of its group calls it
+__device__ __forceinline__ void rs_list_claim(unsigned long long *list, unsigned long long *__restrict__ longs, uint64_t i,
+                                              uint64_t lo, uint64_t hi, uint32_t tile_lg) {
+    const unsigned long long t = rs_tiles(lo, hi, tile_lg);
+    const unsigned long long old = atomicAdd(list, (1ULL << kRsTileBits) | t);
+    longs[old >> kRsTileBits] = ((old & ((1ULL << kRsTileBits) - 1)) << kRsPosBits) | i;
+}
+
+// a list entry's command and its first tile
+__device__ __forceinline__ uint64_t rs_entry_pos(unsigned long long e) { return e & ((1ULL << kRsPosBits) - 1); }
+__device__ __forceinline__ uint64_t rs_entry_tile(unsigned long long e) { return e >> kRsPosBits; }
+
+// the listed command and the tile of it that flattened tile t is
+struct RsTile { uint64_t i, own; };  // the command, and the tile's number inside it
+__device__ __forceinline__ RsTile rs_tile_of(const unsigned long long *__restrict__ longs, uint32_t nlong, uint64_t t) {
+    uint32_t l = 0, r = nlong - 1;  // the last entry whose first tile is <= t lies in [l, r]
+    while (l < r) {
+        const uint32_t m = (l + r + 1) >> 1;
+        if (rs_entry_tile(longs[m]) <= t) l = m;
+        else r = m - 1;
+    }
+    const unsigned long long e = longs[l];
+    return RsTile{rs_entry_pos(e), t - rs_entry_tile(e)};
+}
+
+// *word = min(*word, i), a summary's "first failed position": a read past L1 spares the atomic, which decides alone
+__device__ __forceinline__ void rs_first_min(unsigned long long *word, uint64_t i) {
+    if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > i) atomicMin(word, (unsigned long long)i);
+}
+
+// The sum of x over a workgroup of 256 threads goes to use(sum) in thread 0, between the two barriers.  Every
+// thread of the workgroup calls it; the trailing barrier lets the next call rewrite s_part.
+template <class Use>
+__device__ __forceinline__ void block_sum4(unsigned long long x, unsigned long long *s_part, Use use) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) use(s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+    __syncthreads();
+}
+
 }  // namespace rbx

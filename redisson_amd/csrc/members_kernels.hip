@@ -170,10 +170,10 @@ __global__ __launch_bounds__(256) void k_words_import(const unsigned long long *
 
 // ---------------------------------------------------------------------------------
 // 5. Many keys (rbx_bitset_members_stream): command i is (key[i], cmds[i]) over the BitKey table of the bit streams,
-// in the two tiers of the range stream (rangestream_kernels.hip), and in two passes around one scan:
+// in the two tiers of the range stream (their list and summary: bitrange_device.h), and in two passes around one scan:
 //   count   k_ms_count<G>: a group of G lanes per command counts an interval of at most short_max bytes and stores
 //           the command's yield (the page's size: members_page with the command's skip and limit); a longer interval
-//           is listed with its tile numbers (one atomic, as k_rs_short), its tiles are counted by the whole grid
+//           is listed with its tile numbers (rs_list_claim), its tiles are counted by the whole grid
 //           (k_ms_tile_count) and one lane per listed command turns the tile counts into the ranks of the tiles'
 //           first ones and the command's yield (k_ms_long_yield);
 //   scan    the yields' exclusive prefix sums, in place (k_bits_block_scan), plus the carry of the chunks before;
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void k_words_import(const unsigned long long *
 //           4 KiB blocks through block_expand, the coalesced pattern of the single key.
 // off[i] = the index in `out` of command i's first position; a position whose index is not below cap is dropped.
 // ---------------------------------------------------------------------------------
-constexpr uint8_t kMsFailedStatus = 0xFF;
+constexpr int kMsFlags = rs_flags_at(kMsFirsts), kMsLong = rs_long_at(kMsFirsts);
 
 // the interval of a legal command on a key of the right type, from the table entry
 __device__ __forceinline__ bool ms_interval(const BitKey &bk, const rbx_members_cmd &c, uint64_t *lo, uint64_t *hi) {
@@ -212,22 +212,17 @@ __global__ __launch_bounds__(256) void k_ms_count(const BitKey *__restrict__ tab
             c = cmds[i];
             const uint32_t k = key[i];
             if (k >= nkeys || members_cmd_illegal(c.nargs, c.unit)) {
-                if (gl == 0) atomicOr(sum + kMsFlags, (unsigned long long)kMsIllegal);
+                if (gl == 0) atomicOr(sum + kMsFlags, (unsigned long long)kRsIllegal);
             } else {
                 const BitKey bk = tab[k];
                 store = true;
                 if (bk.flags & kBitKeyWrong) {
-                    st = kMsFailedStatus;
-                    if (gl == 0 && __hip_atomic_load(sum + kMsFirstWrong, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > i)
-                        atomicMin(sum + kMsFirstWrong, (unsigned long long)i);
+                    st = kRsFailedStatus;
+                    if (gl == 0) rs_first_min(sum, i);  // (the one "first" word: the first command on a wrong key)
                 } else if (ms_interval(bk, c, &lo, &hi)) {
                     vecs = (const uint4 *)bk.words;
                     if ((hi >> 3) - (lo >> 3) + 1 > short_max) {
-                        if (gl == 0) {  // a list slot and the command's tile numbers with one atomic
-                            const unsigned long long t = rs_tiles(lo, hi, tile_lg);
-                            const unsigned long long old = atomicAdd(sum + kMsLong, (1ULL << kRsTileBits) | t);
-                            longs[old >> kRsTileBits] = ((old & ((1ULL << kRsTileBits) - 1)) << kRsPosBits) | i;
-                        }
+                        if (gl == 0) rs_list_claim(sum + kMsLong, longs, i, lo, hi, tile_lg);
                     } else {
                         walk = true;
                     }
@@ -248,30 +243,14 @@ __global__ __launch_bounds__(256) void k_ms_count(const BitKey *__restrict__ tab
     }
 }
 
-// the listed command and the tile of it that flattened tile t is
-struct MsTile {
-    uint64_t i, own;  // the command, and the tile's number inside it
-};
-__device__ __forceinline__ MsTile ms_tile_of(const unsigned long long *__restrict__ longs, uint32_t nlong, uint64_t t) {
-    uint32_t l = 0, r = nlong - 1;  // the last entry whose first tile is <= t
-    while (l < r) {
-        const uint32_t m = (l + r + 1) >> 1;
-        if ((longs[m] >> kRsPosBits) <= t) l = m;
-        else r = m - 1;
-    }
-    const unsigned long long e = longs[l];
-    return MsTile{e & ((1ULL << kRsPosBits) - 1), t - (e >> kRsPosBits)};
-}
-
 __global__ __launch_bounds__(256) void k_ms_tile_count(const BitKey *__restrict__ tab, const uint32_t *__restrict__ key,
                                                        const rbx_members_cmd *__restrict__ cmds, uint32_t tile_lg,
                                                        const unsigned long long *__restrict__ longs, uint32_t nlong,
                                                        uint64_t ntiles, unsigned long long *__restrict__ tilecnt) {
     __shared__ unsigned long long s_part[4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t tile_vecs = 1ULL << (tile_lg - 4);
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const MsTile mt = ms_tile_of(longs, nlong, t);
+        const RsTile mt = rs_tile_of(longs, nlong, t);
         const BitKey bk = tab[key[mt.i]];
         uint64_t lo, hi, n1 = 0;
         if (ms_interval(bk, cmds[mt.i], &lo, &hi)) {  // (always: listed commands have an interval)
@@ -279,12 +258,7 @@ __global__ __launch_bounds__(256) void k_ms_tile_count(const BitKey *__restrict_
             const uint64_t v1 = hi >> 7, cb = (lo >> 7) + mt.own * tile_vecs, ce = min(cb + tile_vecs - 1, v1);
             for (uint64_t v = cb + threadIdx.x; v <= ce; v += 256) n1 += popc4(vec_wanted<false>(ld_nt16(vecs + v), v, lo, hi));
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n1 += __shfl_down((unsigned long long)n1, o, 64);
-        if (lane == 0) s_part[wave] = n1;
-        __syncthreads();
-        if (threadIdx.x == 0) tilecnt[t] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-        __syncthreads();  // s_part is rewritten by the next tile
+        block_sum4(n1, s_part, [&](unsigned long long sum) { tilecnt[t] = sum; });
     }
 }
 
@@ -295,8 +269,8 @@ __global__ __launch_bounds__(256) void k_ms_long_yield(const rbx_members_cmd *__
                                                        unsigned long long *__restrict__ off) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nlong; j += stride) {
-        const uint64_t i = longs[j] & ((1ULL << kRsPosBits) - 1), t0 = longs[j] >> kRsPosBits;
-        const uint64_t t1 = j + 1 < nlong ? longs[j + 1] >> kRsPosBits : ntiles;
+        const uint64_t i = rs_entry_pos(longs[j]), t0 = rs_entry_tile(longs[j]);
+        const uint64_t t1 = j + 1 < nlong ? rs_entry_tile(longs[j + 1]) : ntiles;
         unsigned long long run = 0;
         for (uint64_t t = t0; t < t1; ++t) {
             const unsigned long long c = tilecnt[t];
@@ -372,7 +346,7 @@ __global__ __launch_bounds__(256) void k_ms_expand_tiles(const BitKey *__restric
                                                          unsigned long long *__restrict__ out, uint64_t cap) {
     const uint64_t tile_vecs = 1ULL << (tile_lg - 4);
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {  // every condition here is uniform in the workgroup
-        const MsTile mt = ms_tile_of(longs, nlong, t);
+        const RsTile mt = rs_tile_of(longs, nlong, t);
         const unsigned long long o = off[mt.i], y = off[mt.i + 1] - o;
         if (y == 0 || o >= cap) continue;
         const rbx_members_cmd c = cmds[mt.i];
@@ -398,28 +372,14 @@ __global__ __launch_bounds__(256) void k_ms_expand_tiles(const BitKey *__restric
 // ---------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------
-static uint32_t log2_of(uint32_t pow2) {
-    uint32_t lg = 0;
-    while ((1u << lg) < pow2) ++lg;
-    return lg;
-}
-
-template <int G> static unsigned ms_grid(uint32_t n) {
-    return (unsigned)std::min<uint64_t>(((uint64_t)n + 256 / G - 1) / (256 / G), kMaxGrid);
-}
-
 void launch_members_count(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_members_cmd *d_cmds, uint32_t n,
                           uint32_t nkeys, uint32_t short_max, uint32_t tile_bytes, unsigned long long *d_off,
                           uint8_t *d_status, unsigned long long *d_sum, unsigned long long *d_long, hipStream_t st) {
     const uint32_t lg = log2_of(tile_bytes);
-#define MS_COUNT(G)                                                                                                     \
-    hipLaunchKernelGGL(k_ms_count<G>, dim3(ms_grid<G>(n)), dim3(256), 0, st, d_tab, d_key, d_cmds, n, nkeys, short_max, lg, \
+#define MS_COUNT(G)                                                                                                        \
+    hipLaunchKernelGGL(k_ms_count<G>, dim3(grid_for((uint64_t)n * G, kMaxGrid)), dim3(256), 0, st, d_tab, d_key, d_cmds, n, nkeys, short_max, lg, \
                        d_off, d_status, d_sum, d_long)
-    if (lanes == 4) MS_COUNT(4);
-    else if (lanes == 8) MS_COUNT(8);
-    else if (lanes == 32) MS_COUNT(32);
-    else if (lanes == 64) MS_COUNT(64);
-    else MS_COUNT(16);
+    RBX_FOR_LANES(lanes, MS_COUNT);
 #undef MS_COUNT
 }
 
@@ -439,14 +399,10 @@ void launch_members_carry(unsigned long long *d_off, uint64_t m1, const unsigned
 void launch_members_expand_short(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_members_cmd *d_cmds,
                                  uint32_t n, uint32_t short_max, const unsigned long long *d_off, uint64_t *d_out,
                                  uint64_t cap, hipStream_t st) {
-#define MS_EXPAND(G)                                                                                                       \
-    hipLaunchKernelGGL(k_ms_expand_short<G>, dim3(ms_grid<G>(n)), dim3(256), 0, st, d_tab, d_key, d_cmds, n, short_max, d_off, \
-                       (unsigned long long *)d_out, cap)
-    if (lanes == 4) MS_EXPAND(4);
-    else if (lanes == 8) MS_EXPAND(8);
-    else if (lanes == 32) MS_EXPAND(32);
-    else if (lanes == 64) MS_EXPAND(64);
-    else MS_EXPAND(16);
+#define MS_EXPAND(G)                                                                                                   \
+    hipLaunchKernelGGL(k_ms_expand_short<G>, dim3(grid_for((uint64_t)n * G, kMaxGrid)), dim3(256), 0, st, d_tab, d_key, d_cmds, n, short_max, \
+                       d_off, (unsigned long long *)d_out, cap)
+    RBX_FOR_LANES(lanes, MS_EXPAND);
 #undef MS_EXPAND
 }
 

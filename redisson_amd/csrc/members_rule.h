@@ -1,7 +1,7 @@
 // members_rule.h -- the rules of set-bit enumeration (rbx_bitset_members*) and of the java.util.BitSet exchange
 // (rbx_bitset_as_words / rbx_bitset_set_words; M/RedissonBitSet.java:391-420 fromByteArrayReverse /
 // toByteArrayReverse), DESIGN section 11.11.  One function each for the kernels (members_kernels.hip), the host
-// entry points (api_bitset.cpp) and the stand-alone sanitizer program tests/c/members_rule_test.cpp: like
+// entry points (api_bitset.cpp, api_bitset_multi.cpp) and the stand-alone sanitizer program tests/c/members_rule_test.cpp: like
 // range_cmd.h, whose interval rule it takes, it includes <stdint.h> and the C ABI header only and compiles
 // without HIP.  No step wraps a uint64_t, whatever skip, limit and cap are.
 #pragma once

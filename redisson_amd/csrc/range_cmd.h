@@ -2,7 +2,7 @@
 // ([redis-7.2] bitops.c bitcountCommand / bitposCommand, restated in DESIGN section 11.2), RBitSet.length()'s
 // script over (length, first byte, last byte), and what one command of rbx_bitset_range_stream (DESIGN
 // section 11.10) is from the command alone and from (command, length, missing).  One function each for the
-// kernels (bitrange_kernels.hip, rangestream_kernels.hip), the host entry points (api_bitset.cpp,
+// kernels (bitrange_kernels.hip, rangestream_kernels.hip), the host entry points (api_bitset_multi.cpp,
 // keyspace.cpp) and the stand-alone sanitizer program tests/c/range_cmd_test.cpp: it includes <stdint.h>
 // and the C ABI header only and compiles without HIP.  No step overflows an int64_t, whatever start and end are.
 #pragma once

@@ -19,9 +19,8 @@
 
 namespace rbx {
 
-constexpr uint8_t kRsFailedStatus = 0xFF;
-
-// (rs_len, the string of a table entry, and rs_tiles, the tiles of an interval: bitrange_device.h)
+// (rs_len, the string of a table entry, and the two tiers' list, tiles and summary idioms: bitrange_device.h)
+constexpr int kRsFlags = rs_flags_at(kRangeKinds), kRsLong = rs_long_at(kRangeKinds);
 
 // ---------------------------------------------------------------------------------
 // 1. One group of G lanes per command; the grid strides over the commands, and the trip count is the same in
@@ -70,14 +69,9 @@ __global__ __launch_bounds__(256) void k_rs_short(const BitKey *__restrict__ tab
                     vecs = (const uint4 *)bk.words;
                     flip = c.op == RBX_RANGE_POS && c.bit == 0;
                     if ((hi >> 3) - (lo >> 3) + 1 > short_max) {
-                        // preset the reply the tiles add to or take the minimum of, and take a list slot and the
-                        // command's tile numbers with ONE atomic: the list then ascends in its first tiles
+                        // preset the reply the tiles add to or take the minimum of, and list the command
                         reply = c.op == RBX_RANGE_COUNT ? 0 : (int64_t)kBitsNone;
-                        if (gl == 0) {
-                            const unsigned long long t = rs_tiles(lo, hi, tile_lg);
-                            const unsigned long long old = atomicAdd(sum + kRsLong, (1ULL << kRsTileBits) | t);
-                            longs[old >> kRsTileBits] = ((old & ((1ULL << kRsTileBits) - 1)) << kRsPosBits) | i;
-                        }
+                        if (gl == 0) rs_list_claim(sum + kRsLong, longs, i, lo, hi, tile_lg);
                     } else {
                         what = c.op == RBX_RANGE_COUNT ? kCount : kPos;
                     }
@@ -85,8 +79,7 @@ __global__ __launch_bounds__(256) void k_rs_short(const BitKey *__restrict__ tab
                 if (f) {
                     reply = 0;
                     st = kRsFailedStatus;
-                    unsigned long long *first = sum + kRsFirst + (f - 1);
-                    if (gl == 0 && __hip_atomic_load(first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > i) atomicMin(first, (unsigned long long)i);
+                    if (gl == 0) rs_first_min(sum + (f - 1), i);
                 }
             }
         }
@@ -123,10 +116,9 @@ __global__ __launch_bounds__(256) void k_rs_short(const BitKey *__restrict__ tab
 }
 
 // ---------------------------------------------------------------------------------
-// 2. The tiles of the listed commands, numbered across the list: entry j = first tile << kRsPosBits | position,
-// ascending in j (k_rs_short).  Workgroup w takes tiles w, w + grid, ...; it finds its entry by binary search
-// (the last one whose first tile is <= the tile), works the command's interval out again from the command and
-// the table, and sweeps the tile's vectors.  COUNT: a block reduction and one atomicAdd into the reply per tile.
+// 2. The tiles of the listed commands, numbered across the list.  Workgroup w takes tiles w, w + grid, ...; it
+// finds its command (rs_tile_of), works the command's interval out again from the command and the table, and
+// sweeps the tile's vectors.  COUNT: a block reduction and one atomicAdd into the reply per tile.
 // POS: the tile is skipped when a hit at or before its first bit is published, else scanned front to back,
 // 256 vectors per step, and the first step with a hit publishes atomicMin(reply, position) and ends the tile's
 // scan.  Exact by k_bits_pos's argument (bitrange_kernels.hip): a tile is scanned to its end or left only behind
@@ -137,17 +129,11 @@ __global__ __launch_bounds__(256) void k_rs_tiles(const BitKey *__restrict__ tab
                                                   const unsigned long long *__restrict__ longs, uint32_t nlong,
                                                   uint64_t ntiles, int64_t *replies) {
     __shared__ unsigned long long s_part[4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63;
     const uint64_t tile_vecs = 1ULL << (tile_lg - 4);
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        uint32_t l = 0, r = nlong - 1;  // the answer lies in [l, r]
-        while (l < r) {
-            const uint32_t m = (l + r + 1) >> 1;
-            if ((longs[m] >> kRsPosBits) <= t) l = m;
-            else r = m - 1;
-        }
-        const unsigned long long e = longs[l];
-        const uint64_t i = e & ((1ULL << kRsPosBits) - 1), own = t - (e >> kRsPosBits);
+        const RsTile rt = rs_tile_of(longs, nlong, t);
+        const uint64_t i = rt.i;
         const rbx_range_cmd c = cmds[i];
         const BitKey bk = tab[key[i]];
         bool missing;
@@ -156,9 +142,8 @@ __global__ __launch_bounds__(256) void k_rs_tiles(const BitKey *__restrict__ tab
         int64_t fixed;
         if (!range_cmd_plan(c, len, missing, &lo, &hi, &fixed)) continue;  // (listed commands have an interval)
         const uint4 *vecs = (const uint4 *)bk.words;
-        const uint64_t v1 = hi >> 7, cb = (lo >> 7) + own * tile_vecs;
-        if (cb > v1) continue;  // (never: own is below the command's tiles)
-        const uint64_t ce = min(cb + tile_vecs - 1, v1);
+        // cb <= v1: the tile is one of the command's (the list's invariant, bitrange_device.h)
+        const uint64_t v1 = hi >> 7, cb = (lo >> 7) + rt.own * tile_vecs, ce = min(cb + tile_vecs - 1, v1);
         auto *result = (unsigned long long *)(replies + i);
         if (c.op == RBX_RANGE_COUNT) {
             uint64_t n1 = 0;
@@ -167,15 +152,9 @@ __global__ __launch_bounds__(256) void k_rs_tiles(const BitKey *__restrict__ tab
                 if (v == (lo >> 7) || v == v1) x = vec_wanted<false>(x, v, lo, hi);
                 n1 += popc4(x);
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) n1 += __shfl_down((unsigned long long)n1, off, 64);
-            if (lane == 0) s_part[wave] = n1;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const unsigned long long sum = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+            block_sum4(n1, s_part, [&](unsigned long long sum) {
                 if (sum) atomicAdd(result, sum);
-            }
-            __syncthreads();  // s_part is rewritten by the next tile
+            });
         } else {
             const bool flip = c.bit == 0;
             // (read past L1 for the early exit only; the answer rests on the atomicMin alone)
@@ -211,7 +190,7 @@ __global__ __launch_bounds__(256) void k_rs_finish(const BitKey *__restrict__ ta
                                                    int64_t *replies) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nlong; j += stride) {
-        const uint64_t i = longs[j] & ((1ULL << kRsPosBits) - 1);
+        const uint64_t i = rs_entry_pos(longs[j]);
         const rbx_range_cmd c = cmds[i];
         if (c.op != RBX_RANGE_POS) continue;
         bool missing;
@@ -226,31 +205,14 @@ __global__ __launch_bounds__(256) void k_rs_finish(const BitKey *__restrict__ ta
 // ---------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------
-static uint32_t log2_of(uint32_t pow2) {
-    uint32_t lg = 0;
-    while ((1u << lg) < pow2) ++lg;
-    return lg;
-}
-
-template <int G>
-static void launch_short(const BitKey *d_tab, const uint32_t *d_key, const rbx_range_cmd *d_cmds, uint32_t n, uint32_t nkeys,
-                         uint32_t short_max, uint32_t tile_lg, int64_t *d_replies, uint8_t *d_status,
-                         unsigned long long *d_sum, unsigned long long *d_long, hipStream_t st) {
-    const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)n + 256 / G - 1) / (256 / G), kMaxGrid);
-    hipLaunchKernelGGL(k_rs_short<G>, dim3(grid), dim3(256), 0, st, d_tab, d_key, d_cmds, n, nkeys, short_max, tile_lg,
-                       d_replies, d_status, d_sum, d_long);
-}
-
 void launch_rangestream_short(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_range_cmd *d_cmds,
                               uint32_t n, uint32_t nkeys, uint32_t short_max, uint32_t tile_bytes, int64_t *d_replies,
                               uint8_t *d_status, unsigned long long *d_sum, unsigned long long *d_long, hipStream_t st) {
     const uint32_t lg = log2_of(tile_bytes);
-#define RS_SHORT(G) launch_short<G>(d_tab, d_key, d_cmds, n, nkeys, short_max, lg, d_replies, d_status, d_sum, d_long, st)
-    if (lanes == 4) RS_SHORT(4);
-    else if (lanes == 8) RS_SHORT(8);
-    else if (lanes == 32) RS_SHORT(32);
-    else if (lanes == 64) RS_SHORT(64);
-    else RS_SHORT(16);
+#define RS_SHORT(G)                                                                                                        \
+    hipLaunchKernelGGL(k_rs_short<G>, dim3(grid_for((uint64_t)n * G, kMaxGrid)), dim3(256), 0, st, d_tab, d_key, d_cmds, n, nkeys, short_max, lg, \
+                       d_replies, d_status, d_sum, d_long)
+    RBX_FOR_LANES(lanes, RS_SHORT);
 #undef RS_SHORT
 }
 

@@ -522,6 +522,10 @@ static constexpr size_t kHllOpsBytes = kHllSlotOps * 2;
 static constexpr size_t kHllMaxOps = 16384;
 
 constexpr const char *kWrongTypeMsg = "WRONGTYPE Operation against a key holding the wrong kind of value";
+// what RBitSet's single-key calls and their many-key forms both report (api_bitset.cpp, api_bitset_multi.cpp)
+constexpr const char *kFieldTypeMsg =
+    "ERR Invalid bitfield type. Use something like i16 u8. Note that u64 is not supported but i64 is.";
+constexpr const char *kBitopNotMsg = "ERR BITOP NOT must be called with a single source key.";
 
 // the small host tier's pinned block (api_staging.cpp): zeroed result area ahead of the keys (counts, changed words)
 static constexpr uint64_t kSmallHead = 64 << 10;
@@ -609,6 +613,9 @@ FilterDesc desc_of(const Bitmap &b, uint64_t size, uint32_t k, uint32_t fid);
 KeysDev keys_dev(const rbx_keys *k);
 int bloom_bind(rbx_ctx *c, rbx_bloom *b, bool create, hipStream_t st, bool *absent);
 int bitcount_locked(rbx_ctx *c, const std::string &name, uint64_t *out);
+// api_bitset.cpp
+int bitset_find(rbx_ctx *c, const std::string &name, std::shared_ptr<Bitmap> *out);
+int bitset_for_write(rbx_ctx *c, const std::string &name, uint64_t need_bytes, hipStream_t st, std::shared_ptr<Bitmap> *out);
 // api_hll.cpp
 int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint64_t *seg_offsets,
                   const rbx_keys *elements, uint8_t *out_changed);

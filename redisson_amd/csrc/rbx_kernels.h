@@ -437,11 +437,10 @@ void launch_words_import(const uint64_t *d_words, uint64_t n, uint64_t bytes, ui
                          hipStream_t st);
 
 // Many keys (rbx_bitset_members_stream): command i is (d_key[i], d_cmds[i]) over the BitKey table below, n <= 2^30
-// commands per chunk.  The summary words (u64) of one chunk: the first command on a key of another type (the caller
-// sets it to ~0 and the others to 0), the flags, and the range stream's list word (long commands << kRsTileBits | tiles).
+// commands per chunk, in the range stream's two tiers with its summary words (below): the one "first" word is the
+// first command on a key of another type.
 struct BitKey;
-enum { kMsFirstWrong = 0, kMsFlags = 1, kMsLong = 2, kMsSummaryWords = 3 };
-constexpr uint32_t kMsIllegal = 1;
+constexpr int kMsFirsts = 1;
 // d_off[i] = command i's yield (0 for a listed long command, whose (first tile << kRsPosBits | position) goes to
 // d_long, ascending); d_status[i] (nullable) = 0, or 0xFF on a key of another type
 void launch_members_count(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_members_cmd *d_cmds, uint32_t n,
@@ -511,12 +510,22 @@ void launch_bitstream_lengths(const BitKey *d_tab, const unsigned long long *d_k
 // ---- rangestream_kernels.hip
 // The read queries over many strings (rbx_bitset_range_stream): command i is (key[i], cmds[i]),
 // the strings are reached through the BitKey table above, range_cmd.h has the rules.
-// the summary words (u64) of one chunk: the first position of each failure kind (kRange* - 1; the caller sets
-// them to ~0 and the others to 0), the flags, and one word that hands out the long list's slots and the tile
-// numbers together: long commands << kRsTileBits | tiles
-enum { kRsFirst = 0, kRsFlags = kRangeKinds, kRsLong = kRangeKinds + 1, kRsSummaryWords = kRangeKinds + 2 };
+// The summary words (u64) of one chunk of a two-tier read stream (this one and the members stream): nfirst "first
+// position" minima (here one per failure kind, kRange* - 1; preset to ~0, the others to 0), the flags, and one
+// word that hands out the long list's slots and the tile numbers together: long commands << kRsTileBits | tiles
+constexpr int rs_flags_at(int nfirst) { return nfirst; }
+constexpr int rs_long_at(int nfirst) { return nfirst + 1; }
+constexpr int rs_summary_words(int nfirst) { return nfirst + 2; }
 constexpr uint32_t kRsIllegal = 1;
 constexpr int kRsTileBits = 33, kRsPosBits = 30;  // a chunk has <= 2^30 commands and fewer than 2^33 tiles
+// the two streams' launchers: a tile's log2 (a power of two), the "lanes" knob to LAUNCH(G); grid: grid_for(n * G)
+inline uint32_t log2_of(uint32_t pow2) { return (uint32_t)__builtin_ctz(pow2); }
+#define RBX_FOR_LANES(lanes, LAUNCH)    \
+    if ((lanes) == 4) LAUNCH(4);        \
+    else if ((lanes) == 8) LAUNCH(8);   \
+    else if ((lanes) == 32) LAUNCH(32); \
+    else if ((lanes) == 64) LAUNCH(64); \
+    else LAUNCH(16)
 // One group of `lanes` lanes (4, 8, 16, 32 or 64) per command, n <= 2^30: every command whose interval covers
 // at most short_max bytes is answered (d_replies, d_status nullable); a longer one presets its reply (0 for
 // COUNT, kBitsNone for POS) and appends (first tile << kRsPosBits | position) to d_long (n entries), ascending.

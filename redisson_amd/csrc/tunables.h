@@ -88,7 +88,7 @@ struct Tunables {
     // increments have one sign takes k_fields_incr_sat, 0 = the grouped path (tests run both on one input)
     std::atomic<int> bitfield_sat_atomic{1};
 
-    // ---- the ordered GETBIT / SETBIT stream (api_bitset.cpp) ----
+    // ---- the ordered GETBIT / SETBIT stream (api_bitset_multi.cpp) ----
     // "bitstream_path": 0 (default) = gather for a batch of GETBITs, scatter for SETBITs of one value without
     // replies, else serial up to bitstream_serial_max commands and grouped past it; 1 = always serial, 2 = always
     // grouped.  All exact.
@@ -99,7 +99,7 @@ struct Tunables {
     // commands are 1.125 GiB)
     std::atomic<uint64_t> bitstream_chunk{1 << 25};
 
-    // ---- the ordered BITFIELD stream (api_bitset.cpp) ----
+    // ---- the ordered BITFIELD stream (api_bitset_multi.cpp) ----
     // "fieldstream_path": 0 (default) = gather for a batch without SET / INCRBY, one compare-and-swap loop per
     // command for WRAP INCRBYs of one size dividing 64 at multiples of it without replies, else serial up to
     // fieldstream_serial_max commands, past it grouped by word when every command lies inside one aligned
@@ -140,12 +140,12 @@ struct Tunables {
     // 1.777 - 1.795 ms), so from 256 on P = 1 is taken.
     std::atomic<int> hllgroups_split{0};
 
-    // ---- grouped BITOPs and BITCOUNTs (api_bitset.cpp) ----
+    // ---- grouped BITOPs and BITCOUNTs (api_bitset_multi.cpp) ----
     // "bitgroups_tile": the bytes T of a tile of the segmented sweep: 0 (default) = auto, else a power of two in
     // 4 KiB .. 1 MiB.  All exact.  Auto: bitgroups_auto_tile below.
     std::atomic<uint32_t> bitgroups_tile{0};
 
-    // ---- the read queries over many keys (api_bitset.cpp) ----
+    // ---- the read queries over many keys (api_bitset_multi.cpp) ----
     // "rangestream_lanes": the lanes G of the group that answers one command, 4, 8, 16, 32 or 64.  All exact.
     // Measured (DESIGN 11.10 row d): on 20,000 strings of 46 bytes and of 1 KiB the five settings lie within 1 % (the
     // call is host-bound there); 16 is kept.
@@ -162,7 +162,7 @@ struct Tunables {
     // has its own summary and wait)
     std::atomic<uint64_t> rangestream_chunk{1 << 25};
 
-    // ---- set-bit enumeration over many keys (api_bitset.cpp) ----
+    // ---- set-bit enumeration over many keys (api_bitset_multi.cpp) ----
     // The four knobs of rbx_bitset_members_stream mirror the range stream's.  All exact.
     // "members_lanes": the lanes G of the group that counts and expands one short command, 4, 8, 16, 32 or 64.
     // Measured (DESIGN 11.11 row f): on 20,000 strings of 46 bytes the five settings lie within 0.5 % (the call is

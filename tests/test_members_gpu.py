@@ -643,3 +643,77 @@ def test_batch_members_async(client, fresh):
     for nm in ("a", "b"):
         client.getBitSet(fresh + nm).delete()
     client.getHyperLogLog(fresh + "hll").delete()
+
+
+# ---- the two read streams against each other, through the tiers they share ------------------------------------------
+@pytest.mark.parametrize("form", ["host", "dev"])
+@pytest.mark.parametrize("lanes", [4, 64])
+def test_range_stream_counts_equal_members_stream_yields(client, fresh, lanes, form):
+    """Every BITCOUNT reply of the range stream is the members stream's yield off[i + 1] - off[i] (skip 0, no limit) of
+    the same interval, and both are the models'; both streams list the same commands with the same tiles."""
+    import bitstring_model as BM
+    import rangestream_model as RM
+    import test_rangestream_gpu as RS
+    import torch
+
+    from redisson_amd.client import _members_cmds_array
+
+    SHORT_MAX, TILE, CHUNK = 64, 4096, 2
+    rng = np.random.default_rng(29)
+    missing, small, large = fresh + "none", fresh + "s", fresh + "l"
+    strings = {missing: None, small: rng.bytes(100), large: rng.bytes(3 * 4096 + 17)}
+    for nm, data in strings.items():
+        RS.put(client, nm, data)
+    names = [missing, small, large]
+    # (key, nargs, start, end, unit, the interval's bits [lo, hi] or None): a short command between the two long ones
+    cmds = [(2, 0, 0, 0, M.BYTE, (0, 8 * (3 * 4096 + 17) - 1)),  # the whole long string
+            (1, 2, 3, 40, M.BYTE, (24, 8 * 41 - 1)),
+            (2, 2, 5, 8 * (2 * 4096) + 3, M.BIT, (5, 8 * (2 * 4096) + 3)),
+            (0, 0, 0, 0, M.BYTE, None),  # the missing key
+            (1, 2, 50, 10, M.BYTE, None)]  # an empty interval
+    key = [c[0] for c in cmds]
+    m_rows = [(nargs, start, end, unit, 0, None) for _k, nargs, start, end, unit, _iv in cmds]
+    r_rows = [(RM.COUNT, 0, nargs, start, end, unit) for _k, nargs, start, end, unit, _iv in cmds]
+    # what the tiers are to do, from the intervals and the knobs alone
+    is_long = [iv is not None and (iv[1] >> 3) - (iv[0] >> 3) + 1 > SHORT_MAX for *_c, iv in cmds]
+    tiles = sum(((iv[1] >> 7) - (iv[0] >> 7)) // (TILE // 16) + 1 for *_c, iv in (c for c, lg in zip(cmds, is_long) if lg))
+    chunks = [is_long[i:i + CHUNK] for i in range(0, len(cmds), CHUNK)]
+    assert is_long == [True, False, True, False, False] and tiles == 4 + 3 and len(chunks) == 3
+    assert sum(any(ch) for ch in chunks) == 2  # the two long commands fall in different chunks
+
+    w_off, _w_out, _w_status, w_failed = M.stream(strings, names, key, m_rows)
+    ks = RS.model_of({k: v for k, v in strings.items() if v})
+    rc_model, w_counts, _st, _kinds = RM.apply_stream(ks, names, key, r_rows)
+    assert rc_model == RM.OK and not w_failed
+    assert w_counts == np.diff(w_off.astype(np.int64)).tolist()  # the two models agree
+
+    with RS.tuned(short_max=SHORT_MAX, tile=TILE, rangestream_chunk=CHUNK, rangestream_lanes=lanes):
+        rc, counts, status = RS.RUNNERS[form](client, names, key, r_rows)
+        r_last = RS.last()
+    assert rc == L.RBX_OK and status == [0] * len(cmds), L.last_error()
+    with tuned(members_short_max=SHORT_MAX, members_tile=TILE, members_chunk=CHUNK, members_lanes=lanes):
+        if form == "host":
+            rc, off, _out, m_status, total = raw_stream(client, names, key, m_rows, int(w_off[-1]), int(w_off[-1]))
+            assert rc == L.RBX_OK and total == int(w_off[-1]) and not m_status.any()
+        else:
+            d_cmds = torch.frombuffer(bytearray(bytes(_members_cmds_array(m_rows))), dtype=torch.uint8).cuda()
+            d_key = torch.from_numpy(np.asarray(key, np.int32)).cuda()
+            d_off = torch.full((len(cmds) + 1,), -2, dtype=torch.int64, device="cuda")
+            d_out = torch.full((int(w_off[-1]) + 1,), -2, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            bitset_members_stream_dev(client, names, d_key.data_ptr(), d_cmds.data_ptr(), len(cmds), int(w_off[-1]),
+                                      d_off.data_ptr(), d_out.data_ptr(), None)
+            client.synchronize()
+            off = d_off.cpu().numpy().astype(np.uint64)
+        m_last = last_call()
+    print("counts", counts, "yields", np.diff(off.astype(np.int64)).tolist(), "model", w_counts, "range last", r_last,
+          "members last", m_last)
+    assert np.array_equal(off, w_off)
+    assert counts == np.diff(off.astype(np.int64)).tolist() == w_counts
+    n_long = sum(is_long)
+    assert (m_last["short"], m_last["long"], m_last["tiles"]) == (len(cmds) - n_long, n_long, tiles) == tuple(r_last[:3])
+    assert m_last["waits"] == len(chunks)  # one wait per chunk (the host form's second run publishes the same)
+    # the range stream's host form waits once more in each chunk that listed a command, for the replies behind the tiles
+    assert r_last[3] == len(chunks) + (sum(any(ch) for ch in chunks) if form == "host" else 0)
+    for nm in (small, large):
+        client.getBitSet(nm).delete()

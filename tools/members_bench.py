@@ -71,7 +71,9 @@ def main():
                 if i >= a.warmup:
                     t[j].append(x)
         r = dict({"row": row, "operation": label, "call_ms_median": statistics.median(t[0]) * 1e3,
-                  "call_ms_min": min(t[0]) * 1e3, "call_ms_max": max(t[0]) * 1e3, "reps": reps}, **extra)
+                  "call_ms_min": min(t[0]) * 1e3, "call_ms_max": max(t[0]) * 1e3,
+                  "call_ms_p10": float(np.percentile(t[0], 10)) * 1e3, "call_ms_p90": float(np.percentile(t[0], 90)) * 1e3,
+                  "reps": reps}, **extra)
         for (blabel, _fn), tb in zip(bases, t[1:]):
             q = np.percentile(np.array(tb) * 1e3, [10, 50, 90])
             r.setdefault("baselines", []).append({"baseline": blabel, "ms_p10": q[0], "ms_median": q[1], "ms_p90": q[2],

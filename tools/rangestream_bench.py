@@ -99,7 +99,8 @@ def main():
         last = (C.c_uint32 * 4)()
         lib.rbx_bench_rangestream_last(last)
         r = dict({"row": row, "operation": label, "commands": n, "call_ms_median": m_op * 1e3, "call_ms_min": min(t_op) * 1e3,
-                  "call_ms_max": max(t_op) * 1e3, "M_commands_per_s": n / m_op / 1e6, "reps": a.reps,
+                  "call_ms_max": max(t_op) * 1e3, "call_ms_p10": float(np.percentile(t_op, 10)) * 1e3,
+                  "call_ms_p90": float(np.percentile(t_op, 90)) * 1e3, "M_commands_per_s": n / m_op / 1e6, "reps": a.reps,
                   "last_short_long_tiles_waits": list(last)}, **extra)
         if base:
             m_base = statistics.median(t_base)
