@@ -707,7 +707,10 @@ int rbx_bloom_add_multi(rbx_ctx *ctx, rbx_bloom *const *filters, uint32_t nseg,
  * (key_op[i] = 1) on filters[key_filter[i]], executed in key order -- an add is visible to
  * every later contains of the same filter, exactly as the commands would run one after
  * another (M/RedissonBloomFilter.java:99-102, :198-201).  out (nullable): per key, present /
- * newly added.  counts[0] = present contains, counts[1] = newly added.  k <= 32. */
+ * newly added.  counts[0] = present contains, counts[1] = newly added.  k <= 32.
+ * A filter without a bitmap string: the host form creates it only if one of its commands adds to it (GETBIT on a
+ * missing key creates nothing); the _dev form, whose ops are device memory, creates it for every filter it names,
+ * empty if no add reaches it.  A call that is refused (k > 32, a changed config, another type) creates none. */
 int rbx_bloom_stream_dev(rbx_ctx *ctx, rbx_bloom *const *filters, uint32_t nfilters, const uint32_t *d_key_filter,
                          const uint8_t *d_key_op, const rbx_keys *d_keys, uint8_t *d_out,
                          unsigned long long *d_counts, void *stream);

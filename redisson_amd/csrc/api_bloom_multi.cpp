@@ -41,14 +41,17 @@ static int upload_derived(FilterTable &ft, const std::vector<FilterDesc> &v, hip
 
 // Uploads the per-segment descriptor tables (cached by content + bitmap generation); *out: their view.
 // create: a missing bitmap is created (add, stream); otherwise (contains) it reads as all zero
-// through zero_bm and stays missing.
+// through zero_bm and stays missing.  writes (nullable, with create): per filter, whether the call can set a
+// bit in it -- the host stream knows; a filter it only reads stays missing like a contains'.
+// kcap: the largest k the caller runs (the stream's 32), checked per handle before it is bound.
 static int upload_filters(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nseg, hipStream_t st, bool create,
-                          FilterView *out) {
+                          FilterView *out, const uint8_t *writes = nullptr, uint32_t kcap = ~0u) {
     c->ks.sweep();
     FilterTable &ft = c->dev->filt;
     // same handles as the previous call and no keyspace change since: the tables are current
     // (100k tenants: ~5 ms of host work per call otherwise, more than the kernel takes)
-    if (ft.key_generation == c->ks.generation && ft.keys.size() == nseg && ft.create == create) {
+    if (ft.key_generation == c->ks.generation && ft.keys.size() == nseg && ft.create == create &&
+        !(create && ft.had_absent)) {
         bool same = true;
         for (uint32_t s = 0; s < nseg && same; ++s)
             same = filters[s] && ft.keys[s].first == filters[s] && ft.keys[s].second == filters[s]->serial;
@@ -64,14 +67,34 @@ static int upload_filters(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nseg, 
     uint64_t bytes = 0;
     std::vector<uint32_t> absent_segs;
     uint64_t zero_bytes = 0;
+    // A call that fails at a later handle must leave no key behind: the strings this loop creates for the
+    // handles before it are still empty (no kernel has run), so they go again with the error.
+    std::vector<rbx_bloom *> created;
+    auto undo = [&](int rc) {
+        for (rbx_bloom *b : created) {
+            Entry *e = c->ks.find(b->name);
+            if (e && e->type == KType::Bitmap && e->bm == b->bm) c->ks.erase(b->name);
+            b->bm.reset();
+            b->gen = 0;
+        }
+        return rc;
+    };
     for (uint32_t s = 0; s < nseg; ++s) {
         rbx_bloom *b = filters[s];
-        if (!b) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL filter handle");
+        if (!b) return undo(fail(RBX_E_ILLEGAL_ARGUMENT, "NULL filter handle"));
+        if (b->k > kcap) return undo(fail(RBX_E_ILLEGAL_ARGUMENT, "stream batches support k <= 32"));
         if (b->gen != c->ks.generation) {
+            const bool mk = create && (!writes || writes[s]);
+            const bool had = !mk || c->ks.find(b->name) != nullptr;
             bool absent;
-            RBX_TRY(bloom_bind(c, b, create, st, &absent));
+            const int rc = bloom_bind(c, b, mk, st, &absent);
+            if (rc != RBX_OK) return undo(rc);
+            if (!had && b->bm) created.push_back(b);
         }
-        RBX_TRY(check_offsets(b->size));
+        {
+            const int rc = check_offsets(b->size);
+            if (rc != RBX_OK) return undo(rc);
+        }
         km = std::max(km, b->k);
         if (!b->bm) {  // contains on a missing key: every GETBIT reads 0
             absent_segs.push_back(s);
@@ -84,7 +107,7 @@ static int upload_filters(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nseg, 
             fid[b->bm.get()] = id;
             bytes += (size_bits(b->size) + 7) / 8;
         }
-        if (id >= (1u << 24)) return fail(RBX_E_ILLEGAL_ARGUMENT, "more than 2^24 distinct filters in one call");
+        if (id >= (1u << 24)) return undo(fail(RBX_E_ILLEGAL_ARGUMENT, "more than 2^24 distinct filters in one call"));
         v[s] = desc_of(*b->bm, size_bits(b->size), b->k, id);
     }
     if (!absent_segs.empty()) {
@@ -116,6 +139,7 @@ static int upload_filters(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nseg, 
     for (uint32_t s = 0; s < nseg; ++s) ft.keys[s] = {filters[s], filters[s]->serial};
     ft.key_generation = c->ks.generation;
     ft.create = create;
+    ft.had_absent = !absent_segs.empty();
     ft.view.kmax = km;
     ft.view.bytes = bytes;
     *out = ft.view;
@@ -394,18 +418,18 @@ int rbx_bloom_add_multi_dev(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nseg
 
 // Ordered mixed stream (C5): see rbx.h.  Chunks of <= 2^26 pairs run probe -> contains -> commit
 // (tunables.h: stream_table8, stream_chunk).
-int rbx_bloom_stream_dev(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nfilters, const uint32_t *d_key_filter,
-                         const uint8_t *d_key_op, const rbx_keys *d_keys, uint8_t *d_out,
-                         unsigned long long *d_counts, void *stream) {
+static int stream_run(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nfilters, const uint32_t *d_key_filter,
+                      const uint8_t *d_key_op, const rbx_keys *d_keys, uint8_t *d_out, unsigned long long *d_counts,
+                      void *stream, const uint8_t *writes) {
     if (!c || !filters || nfilters == 0 || !d_key_filter || !d_key_op)
         return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL/empty argument");
     RBX_TRY(validate_keys(d_keys));
     RBX_ENTER(c, pick_stream(c, stream));
     hipStream_t st = pick_stream(c, stream);
     FilterView fv;
-    RBX_TRY(upload_filters(c, filters, nfilters, st, true, &fv));
+    RBX_TRY(upload_filters(c, filters, nfilters, st, true, &fv, writes, 32));
     const uint32_t kmax = fv.kmax;
-    if (kmax > 32) return fail(RBX_E_ILLEGAL_ARGUMENT, "stream batches support k <= 32");
+    if (kmax > 32) return fail(RBX_E_ILLEGAL_ARGUMENT, "stream batches support k <= 32");  // a table add_multi built
     if (d_keys->n == 0) return RBX_OK;
     KeysDev keys = keys_dev(d_keys);
     const uint64_t k = std::max<uint32_t>(kmax, 1);
@@ -476,12 +500,24 @@ int rbx_bloom_stream_dev(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nfilter
     return RBX_OK;
 }
 
+// The device form cannot know which filters its commands write before it binds them: every filter without a
+// string gets one (empty if no add reaches it).  The host form below reads the ops and binds for writing only
+// the filters an add names.
+int rbx_bloom_stream_dev(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nfilters, const uint32_t *d_key_filter,
+                         const uint8_t *d_key_op, const rbx_keys *d_keys, uint8_t *d_out,
+                         unsigned long long *d_counts, void *stream) {
+    return stream_run(c, filters, nfilters, d_key_filter, d_key_op, d_keys, d_out, d_counts, stream, nullptr);
+}
+
 int rbx_bloom_stream(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nfilters, const uint32_t *key_filter,
                      const uint8_t *key_op, const rbx_keys *keys, uint8_t *out, uint64_t *counts) {
     if (!c || !filters || nfilters == 0 || !key_filter || !key_op) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
     RBX_TRY(validate_keys(keys));
-    for (uint64_t i = 0; i < keys->n; ++i)
+    std::vector<uint8_t> writes(nfilters, 0);
+    for (uint64_t i = 0; i < keys->n; ++i) {
         if (key_filter[i] >= nfilters) return fail(RBX_E_ILLEGAL_ARGUMENT, "key_filter index out of range");
+        if (key_op[i]) writes[key_filter[i]] = 1;
+    }
     RBX_ENTER(c, c->stream);
     KeysDev dk;
     RBX_TRY(upload_keys(c, keys, 0, keys->n, &dk));
@@ -501,7 +537,7 @@ int rbx_bloom_stream(rbx_ctx *c, rbx_bloom *const *filters, uint32_t nfilters, c
     RBX_TRY(out_flags_dev(c, out, n, &d_out));
     // the *_dev ABI has no off_base: shift the base so that bytes + offsets[i] is key i (never read below)
     rbx_keys kd{dk.bytes - dk.off_base, dk.offsets, dk.stride, dk.n};
-    RBX_TRY(rbx_bloom_stream_dev(c, filters, nfilters, d_kf, d_op, &kd, d_out, d_cnt, c->stream));
+    RBX_TRY(stream_run(c, filters, nfilters, d_kf, d_op, &kd, d_out, d_cnt, c->stream, writes.data()));
     if (out && n) HIP_TRY(hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, c->stream));
     unsigned long long cnt[2];
     HIP_TRY(hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, c->stream));

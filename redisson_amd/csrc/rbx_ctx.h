@@ -290,6 +290,7 @@ struct FilterTable {
     std::vector<std::pair<const rbx_bloom *, uint64_t>> keys;
     uint64_t key_generation = ~0ULL;
     bool create = false;
+    bool had_absent = false;  // an entry stands on zero_bm: never reused by a call that may write
     FilterView view;  // of the tables as they are
 };
 
