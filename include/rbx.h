@@ -650,6 +650,104 @@ int rbx_bitset_range_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nk
  * missing key.  Returns what the single call returns, *reply = 0 when it fails. */
 int rbx_bitset_range_of(const uint8_t *bytes, uint64_t len, int missing, const rbx_range_cmd *cmd, int64_t *reply);
 
+/* ---- Redis string commands on the same keys -- S/RedissonConnection.java:487-627, M/RedissonBinaryStream.java -----
+ * The byte-level commands on the strings the RBitSet section's calls reach by bits ([redis-7.2, external] t_string.c,
+ * restated in DESIGN 11.12).  A string has at most 2^29 bytes (proto-max-bulk-len, and the engine's 2^32-bit cap).
+ * A key of another type -- a {name}:config hash, an HLL -- gives RBX_E_WRONGTYPE; a write keeps the key's timeout,
+ * and what lies between a string's length and its allocation's end stays zero behind every call.
+ *   getrange  GETRANGE key start end  (getRange :617, RBinaryStream's reads :128, :145).  Negative start / end count
+ *             from the end, both are clamped to the string and the reply is the bytes [start, end]; "start < 0 &&
+ *             end < 0 && start > end" and a missing key reply empty bytes (never nil).  *len = the reply's length,
+ *             min(cap, *len) bytes are written (as rbx_bloom_export; out may be NULL with cap 0).
+ *   setrange  SETRANGE key offset value  (setRange :624, the channel's write :158).  offset < 0: RBX_E_REDIS "ERR
+ *             offset is out of range", before the key is looked at.  n = 0: *new_len = the current length and nothing
+ *             is created.  offset + n > 2^29: RBX_E_REDIS "ERR string exceeds maximum allowed size
+ *             (proto-max-bulk-len)".  Otherwise the string becomes max(length, offset + n) bytes, zeros between the
+ *             old length and offset, a missing key is created, and *new_len = the new length.
+ *   append    APPEND key value  (append :610, the OutputStream's write :62).  A missing key is created holding the
+ *             value (n = 0: the empty string rbx_bitset_import_n with length 0 creates); length + n > 2^29 is the
+ *             size error above; *new_len = the new length.
+ *   truncate  the script of RBinaryStream's channel, M/RedissonBinaryStream.java:181-190, step by step: STRLEN; if
+ *             size >= length return; GETRANGE key 0 size-1; SET key that.  Its quirks are the contract: size 0 on a
+ *             non-empty key is GETRANGE 0 -1, so the content stays and only the timeout goes (a negative size keeps
+ *             the bytes [0, length + size - 1]); the SET drops the timeout and creates a missing key as the empty
+ *             string when size < 0.
+ * new_len is nullable.  The _dev forms take DEVICE byte buffers and enqueue on `stream` (NULL: the context's); like
+ * rbx_bitset_set_indexes_dev they are exceptions to the *_dev convention: each waits once, for the string's length
+ * (the range, the growth and the reply are host decisions; len / new_len are host words).  No form moves string bytes
+ * through the host except the host forms' own upload or download of the caller's bytes. */
+int rbx_string_getrange(rbx_ctx *ctx, rbx_name name, int64_t start, int64_t end, uint8_t *out, uint64_t cap, uint64_t *len);
+int rbx_string_setrange(rbx_ctx *ctx, rbx_name name, int64_t offset, const uint8_t *bytes, uint64_t n, uint64_t *new_len);
+int rbx_string_append(rbx_ctx *ctx, rbx_name name, const uint8_t *bytes, uint64_t n, uint64_t *new_len);
+int rbx_string_truncate(rbx_ctx *ctx, rbx_name name, int64_t size);
+int rbx_string_getrange_dev(rbx_ctx *ctx, rbx_name name, int64_t start, int64_t end, uint8_t *d_out, uint64_t cap,
+                            uint64_t *len, void *stream);
+int rbx_string_setrange_dev(rbx_ctx *ctx, rbx_name name, int64_t offset, const uint8_t *d_bytes, uint64_t n,
+                            uint64_t *new_len, void *stream);
+int rbx_string_append_dev(rbx_ctx *ctx, rbx_name name, const uint8_t *d_bytes, uint64_t n, uint64_t *new_len, void *stream);
+/* An ordered stream of GETRANGE / SETRANGE / APPEND / GET commands over many keys in one call: what Spring Data sends
+ * between openPipeline() and closePipeline() (get :487, mGet :499 as n GETs, append :610, getRange :617, setRange :624)
+ * and the per-entity twin of rbx_bitset_range_stream ("append today's byte to every user's string").
+ *   Commands  command i runs on names[cmd_key[i]].  GETRANGE: a = start, b = end.  SETRANGE: a = offset, the value is
+ *             vals[val_off .. val_off + val_len).  APPEND: that value.  GET: the whole string.  Fields a command does
+ *             not use are ignored.  Two entries of `names` with equal bytes are one key.
+ *   Result    exactly that of n single calls in array order: a GETRANGE / GET sees every earlier SETRANGE / APPEND of
+ *             its key, overlapping writes resolve in submission order, an APPEND lies at the running length the
+ *             commands before it produced.  replies[i] = the new length for a write, the byte count for a read.  off
+ *             = n + 1 words, the exclusive prefix sums of the reads' byte counts (a write counts 0): read i's bytes
+ *             are out[off[i] .. off[i + 1]), and *total = off[n].
+ *   Status    status[i] = 0 for a command that ran, 1 for the nil of GET on a missing key (rbx_string_getrange's
+ *             empty reply is 0), 0xFF for a command that failed alone.  replies, status and total are nullable.
+ *   Failures  the pipelined-batch rule of RBX_E_REDIS above: the failures of the single calls (SETRANGE's offset, the
+ *             key's type, the size -- which for an APPEND depends on the running length, data) fail the command
+ *             alone; it changes nothing, its reply is 0 and it does not move the running length, and a key whose only
+ *             writes failed is not created.  A GET on a key of another type fails like the others (Spring's mGet
+ *             maps it to nil).  The call returns the first failing command's code in array order, its message in
+ *             rbx_last_error().
+ *   Caller    RBX_E_ILLEGAL_ARGUMENT with nothing changed and nothing created: cmd_key[i] >= nkeys, an op above
+ *             RBX_STR_GET, a value slice that leaves vals[0 .. vals_len), NULL names / cmd_key / cmds / off with n > 0,
+ *             NULL vals with vals_len > 0, NULL out with cap > 0 -- and total > cap.  The call plans every command
+ *             before it writes any, so a call whose reads do not fit `out` is refused BEFORE any write, with off (and
+ *             *total) filled in exactly: the caller sizes `out` from them and asks again.  Nothing is truncated (as
+ *             rbx_bitset_members_stream does): a call that also writes cannot be repeated.  n = 0 sends nothing
+ *             (off[0] = 0).
+ *   Device    an allocation that fails while the written keys are created or grown (RBX_E_OOM, RBX_E_DEVICE) ends the
+ *             call before any command ran: the keys it had created by then are removed again; a key it had already
+ *             grown keeps its larger allocation, with its bytes and length as they were.
+ *   Cost      each distinct name is looked up once.  A planning pass sorts the commands by key and walks each key's
+ *             run with one lane, from the key's length word (one key holding the whole call is one lane: DESIGN
+ *             11.12); the host then creates or grows every written key once, to its final length.  A group of
+ *             rbx_tune "bytestream_lanes" lanes per key executes the key's commands in order; a command that moves
+ *             more than "bytestream_short_max" bytes is cut into tiles of "bytestream_tile" bytes that the whole
+ *             device sweeps between two walks -- one such command per key and round, so a call makes 1 + (the most
+ *             long commands on one key) rounds of launches and no wait between them.  Up to "bytestream_serial_max"
+ *             commands without a long one run as one lane group in array order.  One wait per chunk of
+ *             "bytestream_chunk" commands; the last one also brings the total and the keys' final lengths.
+ *   Scope     no handle form; the node router and the Java shim do not carry these calls.
+ * `names` is host memory in both forms; the _dev form takes device arrays (d_off[n] is the total; total stays a host
+ * word) and enqueues on `stream`. */
+enum { RBX_STR_GETRANGE = 0, RBX_STR_SETRANGE = 1, RBX_STR_APPEND = 2, RBX_STR_GET = 3 };
+typedef struct {
+    int64_t a, b;     /* GETRANGE start, end; SETRANGE offset in a */
+    uint64_t val_off; /* SETRANGE / APPEND: the value is vals[val_off .. val_off + val_len) */
+    uint32_t val_len;
+    uint8_t op; /* RBX_STR_* */
+    uint8_t pad[3];
+} rbx_string_cmd; /* 32 bytes */
+int rbx_string_stream(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key,
+                      const rbx_string_cmd *cmds, uint64_t n, const uint8_t *vals, uint64_t vals_len, uint64_t cap,
+                      uint64_t *off, uint8_t *out, int64_t *replies, uint8_t *status, uint64_t *total);
+int rbx_string_stream_dev(rbx_ctx *ctx, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                          const rbx_string_cmd *d_cmds, uint64_t n, const uint8_t *d_vals, uint64_t vals_len,
+                          uint64_t cap, uint64_t *d_off, uint8_t *d_out, int64_t *d_replies, uint8_t *d_status,
+                          uint64_t *total, void *stream);
+/* one command over a host string, no context (as rbx_bitset_range_of); missing != 0 = a missing key.  A read writes
+ * min(cap, its byte count) bytes to out; a write stores nothing (the failure and the lengths follow from len alone:
+ * bytes may be NULL for a write) and reports *new_len.  *reply as the stream's; a GET on a missing key is RBX_OK with
+ * *reply = -1.  Returns what the single call returns. */
+int rbx_string_range_of(const uint8_t *bytes, uint64_t len, int missing, const rbx_string_cmd *cmd, const uint8_t *vals,
+                        uint8_t *out, uint64_t cap, int64_t *reply, uint64_t *new_len);
+
 /* ---- replicas ("replicate the bitmap, split contains keys across GPUs") ---------
  * Redisson serves contains' GETBITs as reads that may go to a replica
  * (M/RedissonBitSet.java:277-279 readAsync, ReadMode.SLAVE M/config/BaseMasterSlaveServersConfig.java:60)

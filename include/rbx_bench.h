@@ -65,6 +65,10 @@ int rbx_bench_bitgroups_last(uint32_t out[4]);
 int rbx_bench_rangestream_last(uint32_t out[4]);
 /* The same four numbers for the last rbx_bitset_members_stream[_dev] call (the host form's second run). */
 int rbx_bench_members_last(uint32_t out[4]);
+/* What the last rbx_string_stream[_dev] call that ran did: out[0] = commands finished by lane groups (every command
+ * that is not long), out[1] = long commands (more than "bytestream_short_max" bytes: their bytes went to the tiles),
+ * out[2] = their tiles, out[3] = rounds (per chunk 1 + the most long commands on one key, added over the chunks). */
+int rbx_bench_bytestream_last(uint32_t out[4]);
 /* Process-wide tuning knobs: the whole whitelist (r06).  No knob of librbx.so changes an answer: each
  * selects between exact paths (the fallbacks the engine takes by itself on other shapes, forced so the
  * tests cover them), or sets a grid, chunk or capacity.  Knobs are atomics; a call reads each once.
@@ -186,6 +190,16 @@ int rbx_bench_members_last(uint32_t out[4]);
  *   "members_tile"          bytes of a tile of a long interval, a power of two in 4 KiB .. 1 MiB (default 65536:
  *                           4 KiB tiles cost 29 % and 1 MiB tiles 10 %, DESIGN 11.11 row f)
  *   "members_chunk"         commands per chunk, 1 .. 2^30 (default 2^25); each chunk has its own summary and wait
+ *   "bytestream_lanes"      rbx_string_stream: the lanes of the group that executes one key's commands, 4, 8, 16, 32
+ *                           or 64 (default 16).  This and the four below are the range stream's and the bit stream's
+ *                           defaults taken over; only the lanes are measured (within 2 %, host-bound: DESIGN 11.12)
+ *   "bytestream_short_max"  bytes of the longest command a lane group moves alone, a power of two in 64 .. 1 MiB
+ *                           (default 4096); a longer one is cut into tiles
+ *   "bytestream_tile"       bytes of a tile of a long command and of a single rbx_string_* call, a power of two in
+ *                           4 KiB .. 1 MiB (default 65536)
+ *   "bytestream_chunk"      commands per chunk, 1 .. 2^30 (default 2^25); each chunk has its own summary and wait
+ *   "bytestream_serial_max" the largest call one lane group runs in array order without the sort, when none of its
+ *                           commands is long (default 64)
  * Profiling build only (librbx_diag.so, `make diag`; librbx.so rejects them): "stream_diag",
  * "contains_partition_flags", "add_partition_diag" -- timing diagnostics that make answers wrong
  * (rbx_kernels.h kDiag).  Removed in r06 with the variants they selected (measured slower, never

@@ -78,6 +78,7 @@ RBX_RANGE_BYTE, RBX_RANGE_BIT = 0, 1
 RBX_RANGE_COUNT, RBX_RANGE_POS, RBX_RANGE_STRLEN, RBX_RANGE_LENGTH = 0, 1, 2, 3  # op of rbx_range_cmd
 RBX_OVERFLOW_WRAP, RBX_OVERFLOW_SAT, RBX_OVERFLOW_FAIL = 0, 1, 2
 RBX_HLL_PFADD, RBX_HLL_PFCOUNT = 0, 1  # cmd_op of rbx_hll_stream
+RBX_STR_GETRANGE, RBX_STR_SETRANGE, RBX_STR_APPEND, RBX_STR_GET = 0, 1, 2, 3  # op of rbx_string_cmd
 
 
 class RbxFieldCmd(C.Structure):
@@ -99,6 +100,13 @@ class RbxMembersCmd(C.Structure):
 
     _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("skip", C.c_uint64), ("limit", C.c_uint64),
                 ("nargs", C.c_uint8), ("unit", C.c_uint8), ("pad", C.c_uint8 * 6)]
+
+
+class RbxStringCmd(C.Structure):
+    """struct rbx_string_cmd {a, b, val_off, val_len, op, pad[3]}: 32 bytes"""
+
+    _fields_ = [("a", C.c_int64), ("b", C.c_int64), ("val_off", C.c_uint64), ("val_len", C.c_uint32),
+                ("op", C.c_uint8), ("pad", C.c_uint8 * 3)]
 
 
 # name -> (restype, argtypes); every function declared in include/rbx.h
@@ -257,6 +265,20 @@ SIGNATURES = {
                                           i64p, u8p]),
     "rbx_bitset_range_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp]),
     "rbx_bitset_range_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.POINTER(RbxRangeCmd), C.POINTER(C.c_int64)]),
+    # Redis string commands on the same keys
+    "rbx_string_getrange": (C.c_int, [vp, RbxName, C.c_int64, C.c_int64, u8p, C.c_uint64, u64p]),
+    "rbx_string_setrange": (C.c_int, [vp, RbxName, C.c_int64, u8p, C.c_uint64, u64p]),
+    "rbx_string_append": (C.c_int, [vp, RbxName, u8p, C.c_uint64, u64p]),
+    "rbx_string_truncate": (C.c_int, [vp, RbxName, C.c_int64]),
+    "rbx_string_getrange_dev": (C.c_int, [vp, RbxName, C.c_int64, C.c_int64, vp, C.c_uint64, u64p, vp]),
+    "rbx_string_setrange_dev": (C.c_int, [vp, RbxName, C.c_int64, vp, C.c_uint64, u64p, vp]),
+    "rbx_string_append_dev": (C.c_int, [vp, RbxName, vp, C.c_uint64, u64p, vp]),
+    "rbx_string_stream": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, u32p, C.POINTER(RbxStringCmd), C.c_uint64, u8p,
+                                    C.c_uint64, C.c_uint64, u64p, u8p, i64p, u8p, u64p]),
+    "rbx_string_stream_dev": (C.c_int, [vp, C.POINTER(RbxName), C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint64,
+                                        C.c_uint64, vp, vp, vp, vp, u64p, vp]),
+    "rbx_string_range_of": (C.c_int, [u8p, C.c_uint64, C.c_int, C.POINTER(RbxStringCmd), u8p, u8p, C.c_uint64, i64p,
+                                      u64p]),
     "rbx_bitset_export_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64, u64p]),
     "rbx_bitset_import_n": (C.c_int, [vp, RbxName, u8p, C.c_uint64]),
     "rbx_bitset_as_words": (C.c_int, [vp, RbxName, u64p, C.c_uint64, u64p]),
@@ -308,6 +330,7 @@ SIGNATURES = {
     "rbx_bench_bitgroups_last": (C.c_int, [u32p]),
     "rbx_bench_rangestream_last": (C.c_int, [u32p]),
     "rbx_bench_members_last": (C.c_int, [u32p]),
+    "rbx_bench_bytestream_last": (C.c_int, [u32p]),
     "rbx_bench_gather_regions": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, vp, vp]),
     # include/rbx_selftest.h
     "rbx_selftest_mod": (C.c_uint64, [C.c_uint64, C.c_uint64]),

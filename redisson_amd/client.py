@@ -62,6 +62,10 @@ class RedissonClient:
         """M/api/RedissonClient.java getBitSet(name)"""
         return RBitSet(self, name)
 
+    def getBinaryStream(self, name: str) -> "RBinaryStream":
+        """M/api/RedissonClient.java getBinaryStream(name)"""
+        return RBinaryStream(self, name)
+
     def createBatch(self) -> "RBatch":
         """M/api/RedissonClient.java createBatch()"""
         return RBatch(self, range_stream_call=lambda *a: _engine_bitset_range_stream_call(self, *a),
@@ -81,6 +85,7 @@ class RedissonClient:
     get_bloom_filter = getBloomFilter
     get_hyper_log_log = getHyperLogLog
     get_bit_set = getBitSet
+    get_binary_stream = getBinaryStream
     create_batch = createBatch
 
     def __enter__(self):
@@ -846,6 +851,150 @@ _FAILED_REPLY = 0xFF
 _BIT_OFFSET_LIMIT = 1 << 32
 
 
+class RBinaryStream(_Expirable):
+    """M/RedissonBinaryStream.java (a bucket of bytes, M/RedissonBucket.java) over the key's Redis string: the one the
+    bit commands of RBitSet reach.  The streams and the channel move bytes with APPEND, GETRANGE and SETRANGE on the
+    device; nothing but the caller's own bytes crosses the host link."""
+
+    def __init__(self, client: RedissonClient, name: str):
+        self._client = client
+        self._name = name
+
+    def getName(self) -> str:
+        return self._name
+
+    def _expire_keys(self) -> list[str]:
+        return [self._name]
+
+    def get(self) -> bytes | None:
+        """RBucket.get = GET: None for a missing key"""
+        _r, status, _off, out = string_stream(self._client, [self._name], [0], [(L.RBX_STR_GET, 0, 0, b"")])
+        return None if int(status[0]) == STRING_NIL else out
+
+    def set(self, value: bytes) -> None:
+        """RBucket.set = SET: replaces the key whatever it held and drops its timeout"""
+        nm, _keep = L.name_struct(self._name)
+        ptr, n, _buf = _u8(value)
+        _check(L.lib().rbx_bitset_import_n(self._client.ctx, nm, ptr, n))
+
+    def size(self) -> int:
+        """RBucket.size = STRLEN"""
+        nm, _keep = L.name_struct(self._name)
+        out = C.c_uint64()
+        _check(L.lib().rbx_bitset_size(self._client.ctx, nm, C.byref(out)))
+        return int(out.value) // 8
+
+    def delete(self) -> bool:
+        arr, _keep = L.names_array([self._name])
+        n = C.c_int()
+        _check(L.lib().rbx_del_n(self._client.ctx, arr, 1, C.byref(n)))
+        return n.value > 0
+
+    def isExists(self) -> bool:
+        arr, _keep = L.names_array([self._name])
+        n = C.c_int()
+        _check(L.lib().rbx_exists_n(self._client.ctx, arr, 1, C.byref(n)))
+        return n.value > 0
+
+    def getOutputStream(self) -> "_BinaryOutputStream":
+        return _BinaryOutputStream(self)
+
+    def getInputStream(self) -> "_BinaryInputStream":
+        return _BinaryInputStream(self)
+
+    def getChannel(self) -> "_BinaryChannel":
+        return _BinaryChannel(self)
+
+    get_name = getName
+    is_exists = isExists
+    get_output_stream = getOutputStream
+    get_input_stream = getInputStream
+    get_channel = getChannel
+
+
+class _BinaryOutputStream:
+    """RedissonOutputStream :44-65: write = APPEND"""
+
+    def __init__(self, owner: RBinaryStream):
+        self._o = owner
+
+    def write(self, data: bytes) -> None:
+        string_append(self._o._client, self._o._name, data)
+
+
+class _BinaryInputStream:
+    """RedissonInputStream :67-140: read = GETRANGE index index+len-1"""
+
+    def __init__(self, owner: RBinaryStream):
+        self._o = owner
+        self.index = 0
+
+    def skip(self, n: int) -> int:
+        """:86-98"""
+        if n <= 0:
+            return 0
+        old = self.index
+        self.index = min(self._o.size(), self.index + int(n))
+        return self.index - old
+
+    def available(self) -> int:
+        """:103-105"""
+        return self._o.size() - self.index
+
+    def read(self, n: int):
+        """:118-137 -- up to n bytes, or -1 at the end; the index advances by the REQUESTED length (:132)"""
+        if n < 0:
+            raise IndexError("len < 0")
+        if n == 0:
+            return b""
+        data = string_getrange(self._o._client, self._o._name, self.index, self.index + int(n) - 1)
+        if not data:
+            return -1
+        self.index += int(n)
+        return data
+
+
+class _BinaryChannel:
+    """RedissonByteChannel :142-201: read = GETRANGE, write = SETRANGE at the position, truncate = the script"""
+
+    def __init__(self, owner: RBinaryStream):
+        self._o = owner
+        self._position = 0
+
+    def read(self, n: int):
+        """:147-156 -- up to n bytes, or -1 on the empty reply; the position advances by the bytes received (:150).
+        n = 0 reads nothing: GETRANGE p p-1 would be GETRANGE 0 -1 at position 0, the whole string, which the
+        reference's empty buffer could not take either (the input stream's guard, :121-123)."""
+        if n <= 0:
+            return b""
+        data = string_getrange(self._o._client, self._o._name, self._position, self._position + int(n) - 1)
+        if not data:
+            return -1
+        self._position += len(data)
+        return data
+
+    def write(self, data: bytes) -> int:
+        """:159-165"""
+        string_setrange(self._o._client, self._o._name, self._position, data)
+        self._position += len(data)
+        return len(data)
+
+    def position(self, newPosition: int | None = None):
+        """:168-176 -- position() reads it, position(p) sets it and returns the channel"""
+        if newPosition is None:
+            return self._position
+        self._position = int(newPosition)
+        return self
+
+    def size(self) -> int:
+        return self._o.size()
+
+    def truncate(self, size: int) -> "_BinaryChannel":
+        """:184-195"""
+        string_truncate(self._o._client, self._o._name, size)
+        return self
+
+
 def bitset_stream_call(client: RedissonClient, names, cmd_key, cmd_op, cmd_index, replies: bool = True):
     """rbx_bitset_stream over host arrays without raising: (rc, message, replies).  names: str or bytes keys;
     replies is a uint8 array (0xFF = that command failed alone) or None when not asked for."""
@@ -1179,6 +1328,127 @@ def bitset_members_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_c
 _engine_bitset_members_stream_call = bitset_members_stream_call
 
 
+# ---- the byte-level string commands (rbx_string_*, include/rbx.h "Redis string commands on the same keys") ----
+STRING_NIL, STRING_FAILED = 1, 0xFF  # status of a command of rbx_string_stream: GET on a missing key, failed alone
+_STRING_OFFSET_MSG = "ERR offset is out of range"
+_STRING_SIZE_MSG = "ERR string exceeds maximum allowed size (proto-max-bulk-len)"
+
+
+def _u8(data):
+    """(u8 pointer or None, length, keep-alive) of a bytes-like value"""
+    b = bytes(data)
+    buf = (C.c_uint8 * max(1, len(b))).from_buffer_copy(b or b"\0")
+    return (buf if b else None), len(b), buf
+
+
+def string_getrange(client: RedissonClient, name, start: int, end: int) -> bytes:
+    """GETRANGE name start end (rbx_string_getrange): a second call only when the first buffer was too small"""
+    nm, _keep = L.name_struct(name)
+    n, cap = C.c_uint64(), 4096
+    while True:
+        buf = (C.c_uint8 * cap)()
+        _check(L.lib().rbx_string_getrange(client.ctx, nm, int(start), int(end), buf, cap, C.byref(n)))
+        if n.value <= cap:
+            return bytes(buf[:n.value])
+        cap = n.value
+
+
+def string_setrange(client: RedissonClient, name, offset: int, value) -> int:
+    """SETRANGE name offset value -> the new length (rbx_string_setrange)"""
+    nm, _keep = L.name_struct(name)
+    ptr, n, _buf = _u8(value)
+    out = C.c_uint64()
+    _check(L.lib().rbx_string_setrange(client.ctx, nm, int(offset), ptr, n, C.byref(out)))
+    return int(out.value)
+
+
+def string_append(client: RedissonClient, name, value) -> int:
+    """APPEND name value -> the new length (rbx_string_append)"""
+    nm, _keep = L.name_struct(name)
+    ptr, n, _buf = _u8(value)
+    out = C.c_uint64()
+    _check(L.lib().rbx_string_append(client.ctx, nm, ptr, n, C.byref(out)))
+    return int(out.value)
+
+
+def string_truncate(client: RedissonClient, name, size: int) -> None:
+    """the script of RBinaryStream's channel truncate (rbx_string_truncate)"""
+    nm, _keep = L.name_struct(name)
+    _check(L.lib().rbx_string_truncate(client.ctx, nm, int(size)))
+
+
+def _string_cmds(rows):
+    """rows of (op, a, b, value bytes) -> (an array of rbx_string_cmd, the value buffer)"""
+    arr = (L.RbxStringCmd * max(len(rows), 1))()
+    vals = bytearray()
+    for c, (op, a, b, value) in zip(arr, rows):
+        c.op, c.a, c.b, c.val_off, c.val_len = op, a, b, len(vals), len(value)
+        vals += value
+    return arr, bytes(vals)
+
+
+def string_stream_call(client: RedissonClient, names, cmd_key, rows, cap: int | None = None):
+    """rbx_string_stream over host arrays without raising: (rc, message, replies, status, off, out).  Command i runs on
+    names[cmd_key[i]]; rows: (op, a, b, value) with RBX_STR_* codes -- GETRANGE start, end; SETRANGE offset in a.
+    replies: int64, the new length of a write and the byte count of a read; status: 0, 1 (GET on a missing key: nil) or
+    0xFF (failed alone); read i's bytes are out[off[i]:off[i + 1]].  cap None: the reads' bytes are asked for again
+    with the exact size when they do not fit a first guess (such a call is refused before any write)."""
+    key = np.ascontiguousarray(cmd_key, dtype=np.uint32).reshape(-1)
+    rows = list(rows)
+    n = key.size
+    if len(rows) != n:
+        raise IllegalArgumentException("cmd_key and rows have one entry per command")
+    arr, vals = _string_cmds(rows)
+    vptr, vlen, _vbuf = _u8(vals)
+    names_arr, _keep = L.names_array(names)
+    replies, status = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint8)
+    off, total = np.zeros(n + 1, np.uint64), C.c_uint64()
+    room = 65536 if cap is None else int(cap)
+    while True:
+        out = np.zeros(max(room, 1), np.uint8)
+        rc = L.lib().rbx_string_stream(client.ctx, names_arr, len(names), key.ctypes.data_as(L.u32p), arr, n, vptr, vlen,
+                                       room, off.ctypes.data_as(L.u64p), out.ctypes.data_as(L.u8p) if room else None,
+                                       replies.ctypes.data_as(L.i64p), status.ctypes.data_as(L.u8p), C.byref(total))
+        if cap is None and rc == L.RBX_E_ILLEGAL_ARGUMENT and total.value > room:
+            room = total.value
+            continue
+        break
+    return rc, (L.last_error() if rc != L.RBX_OK else ""), replies[:n], status[:n], off, out[:min(total.value, room)].tobytes()
+
+
+def string_stream(client: RedissonClient, names, cmd_key, rows, cap: int | None = None):
+    """GETRANGE / SETRANGE / APPEND / GET commands over many keys in one call (rbx_string_stream): (replies, status,
+    off, out).  Raises the first failing command's exception after every other command ran."""
+    rc, msg, replies, status, off, out = string_stream_call(client, names, cmd_key, rows, cap)
+    raise_for(rc, msg)
+    return replies, status, off, out
+
+
+def string_stream_dev(client: RedissonClient, names, d_cmd_key: int, d_cmds: int, n: int, d_vals: int | None, vals_len: int,
+                      cap: int, d_off: int, d_out: int | None, d_replies: int | None = None, d_status: int | None = None,
+                      stream: int | None = None) -> int:
+    """string_stream over device arrays (u32 keys, 32-byte rbx_string_cmd records, the value bytes, n + 1 u64 offsets,
+    the reads' bytes, i64 replies, u8 status), enqueued on `stream`.  Returns the reads' total bytes."""
+    arr, _keep = L.names_array(names)
+    total = C.c_uint64()
+    _check(L.lib().rbx_string_stream_dev(client.ctx, arr, len(names), d_cmd_key, d_cmds, int(n), d_vals, int(vals_len),
+                                         int(cap), d_off, d_out, d_replies, d_status, C.byref(total), stream))
+    return int(total.value)
+
+
+def string_failure(client: RedissonClient, name, row) -> RedissonAmdError:
+    """what a string command that failed alone failed with, in the order of the single calls: SETRANGE's offset, the
+    key's type -- which a command that failed did not change, so a STRLEN tells it now --, else the size"""
+    op, a, _b, _value = row
+    if op == L.RBX_STR_SETRANGE and a < 0:
+        return RedisException(_STRING_OFFSET_MSG)
+    nm, _keep = L.name_struct(name)
+    out = C.c_uint64()
+    if L.lib().rbx_bitset_size(client.ctx, nm, C.byref(out)) == L.RBX_E_WRONGTYPE:
+        return RedisException(_WRONGTYPE_MSG)
+    return RedisException(_STRING_SIZE_MSG)
+
+
 class BatchFuture:
     """What a queued command returns: get() is its reply once the batch has executed (RFuture of the *Async
     methods), or raises what the command failed with."""
@@ -1215,15 +1485,18 @@ class _Queued:
     coalesces with its like where the range stream call is at hand and runs through fn otherwise; a whole-string
     BITCOUNT carries both a bitop and a range row.  An enumeration (members = (nargs, start, end, unit, skip,
     limit), fn) coalesces with its like where the members stream call is at hand and runs through fn otherwise.
+    A byte-level string command (string = (RBX_STR_*, a, b, value bytes), fn; convert(number, bytes, status) is its
+    reply) coalesces with its like where the string stream call is at hand and runs through fn otherwise.
     convert: applied to a field or HLL command's reply."""
 
-    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group", "bitop", "range", "members")
+    __slots__ = ("name", "op", "index", "fn", "future", "field", "convert", "hll", "group", "bitop", "range", "members",
+                 "string")
 
     def __init__(self, name=None, op=None, index=0, fn=None, field=None, convert=None, hll=None, group=None,
-                 bitop=None, range=None, members=None):  # noqa: A002
+                 bitop=None, range=None, members=None, string=None):  # noqa: A002
         self.name, self.op, self.index, self.fn, self.future = name, op, index, fn, BatchFuture()
         self.field, self.convert, self.hll, self.group, self.bitop = field, convert, hll, group, bitop
-        self.range, self.members = range, members
+        self.range, self.members, self.string = range, members, string
 
     def as_field(self):
         """the command as a BITFIELD sub-command: GETBIT / SETBIT are GET / SET of a u1, which leave the same
@@ -1377,8 +1650,17 @@ def _settle_members(c: _Queued, reply, status) -> None:
         c.future._set(reply)
 
 
+def _settle_string(c: _Queued, reply, status) -> None:
+    """a byte-level string command of a string run; reply = (number, bytes, the error of a failed command)"""
+    if int(status) == STRING_FAILED:
+        c.future._set(error=reply[2])
+    else:
+        c.future._set(c.convert(int(reply[0]), reply[1], int(status)) if c.convert else int(reply[0]))
+
+
 def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, hll_count_groups_call=None,
-              hll_merge_groups_call=None, bit_groups_call=None, range_stream_call=None, members_stream_call=None):
+              hll_merge_groups_call=None, bit_groups_call=None, range_stream_call=None, members_stream_call=None,
+              string_stream_call=None, string_failure=None):
     """Executes queued commands in submission order.  Every maximal run of consecutive bit commands, over any
     keys, is ONE stream_call(names, cmd_key, cmd_op, cmd_index) -> (rc, message, replies).  With a
     field_stream_call, field commands join the runs, and a run that holds at least one of them is ONE
@@ -1395,8 +1677,11 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
     BITPOS, STRLEN, length()), over any keys, is ONE range_stream_call(names, cmd_key, rows) -> (rc, message,
     replies, status); a whole-string BITCOUNT joins an open range run and otherwise starts a grouped bit run as
     before.  With a members_stream_call, every maximal run of consecutive enumerations (membersAsync), over any
-    keys, is ONE members_stream_call(names, cmd_key, rows) -> (rc, message, off, out, status).  A count run, a merge
-    run, an HLL stream run, a grouped bit run, a range run, a members run and a bit / field run each close the others.
+    keys, is ONE members_stream_call(names, cmd_key, rows) -> (rc, message, off, out, status).  With a
+    string_stream_call, every maximal run of consecutive GETRANGE / SETRANGE / APPEND / GET commands, over any keys, is
+    ONE string_stream_call(names, cmd_key, rows) -> (rc, message, replies, status, off, out); string_failure(name, row)
+    names the error of a command of it that failed alone.  A count run, a merge run, an HLL stream run, a grouped bit
+    run, a range run, a members run, a string run and a bit / field run each close the others.
     Every other command runs through its own call at its position.  Each command's future is set; returns
     (responses, first error)."""
     def joins(q):
@@ -1423,6 +1708,17 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
     def members_call(run, names, keys):
         rc, msg, off, out, status = members_stream_call(names, keys, [c.members for c in run])
         return rc, msg, [out[int(off[i]): int(off[i + 1])] for i in range(len(run))], status
+
+    def joins_strings(q):
+        return q.string is not None and string_stream_call is not None
+
+    def strings_call(run, names, keys):
+        rc, msg, replies, status, off, out = string_stream_call(names, keys, [c.string for c in run])
+        if rc not in alone:
+            return rc, msg, None, None
+        rows = [(int(replies[i]), out[int(off[i]): int(off[i + 1])],
+                 string_failure(c.name, c.string) if int(status[i]) == STRING_FAILED else None) for i, c in enumerate(run)]
+        return rc, msg, rows, status
 
     def starts_ranges(q):  # a whole-string BITCOUNT starts a grouped bit run where that call is at hand
         return joins_ranges(q) and not joins_bitops(q)
@@ -1489,6 +1785,9 @@ def run_queue(queue, stream_call, field_stream_call=None, hll_stream_call=None, 
         elif joins_members(queue[i]):
             run = run_from(i, joins_members)
             error = _run_stream(run, members_call, (L.RBX_OK, L.RBX_E_WRONGTYPE), _settle_members)
+        elif joins_strings(queue[i]):
+            run = run_from(i, joins_strings)
+            error = _run_stream(run, strings_call, alone, _settle_string)
         elif joins_bitops(queue[i]):
             run = run_from(i, joins_bitops)
             error = _run_stream(run, bitops_call, alone, _settle_bitop)

@@ -507,6 +507,86 @@ static int words_store(rbx_ctx *c, rbx_name name, const uint64_t *d_words, uint6
     return RBX_OK;
 }
 
+// ---- the byte commands on one key (rbx_string_*; byte_cmd.h has the rules) ----
+// what a command that failed alone reports (byte_cmd.h kByte*), single or in a stream
+int byte_cmd_failed(int kind) {
+    if (kind == kByteOk) return RBX_OK;
+    if (kind == kByteWrongType) return fail(RBX_E_WRONGTYPE, kWrongTypeMsg);
+    return fail(RBX_E_REDIS, kind == kByteBadOffset ? "ERR offset is out of range"
+                                                    : "ERR string exceeds maximum allowed size (proto-max-bulk-len)");
+}
+
+// the string under `name` for a byte command inside the caller's scope: its bitmap (null: missing) and its length,
+// read with the one wait on `st`
+static int string_len(rbx_ctx *c, const std::string &nm, hipStream_t st, std::shared_ptr<Bitmap> *bm, uint64_t *len) {
+    RBX_TRY(bitset_find(c, nm, bm));
+    std::vector<uint64_t> lens;
+    RBX_TRY(bitset_lens(c, {bm->get()}, st, &lens));
+    *len = *bm ? std::min(lens[0], (*bm)->cap_bytes) : 0;
+    return RBX_OK;
+}
+
+// the host forms' scratch is kept between calls up to this size; a larger one is given back behind the call's wait
+static constexpr size_t kByteScratchKeep = 64u << 20;
+static void string_scratch_trim(rbx_ctx *c) {
+    if (c->dev->bits.by_bytes.cap > kByteScratchKeep) c->dev->bits.by_bytes.release();
+}
+
+// GETRANGE into device bytes (d_out) or, through the scratch, into host bytes (out)
+static int string_getrange(rbx_ctx *c, rbx_name name, int64_t start, int64_t end, uint8_t *d_out, uint8_t *out, uint64_t cap,
+                           uint64_t *len, hipStream_t st) {
+    std::shared_ptr<Bitmap> bm;
+    uint64_t L, lo = 0, hi = 0;
+    RBX_TRY(string_len(c, name_of(name), st, &bm, &L));
+    const uint64_t cnt = byte_getrange(start, end, L, &lo, &hi) ? hi - lo : 0;
+    if (len) *len = cnt;
+    const uint64_t wr = std::min(cap, cnt);
+    if (wr == 0) return RBX_OK;
+    if (out) {
+        RBX_TRY(c->dev->bits.by_bytes.reserve(wr));
+        d_out = c->dev->bits.by_bytes.as<uint8_t>();
+    }
+    launch_bytes_copy(d_out, (const uint8_t *)bm->d_words + lo, wr, g_tune.bytestream_tile, nullptr, 0, st);
+    HIP_TRY(hipGetLastError());
+    if (out) {
+        HIP_TRY(hipMemcpyAsync(out, d_out, wr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        string_scratch_trim(c);
+    }
+    return RBX_OK;
+}
+
+// SETRANGE / APPEND of n bytes from the device (d_bytes) or, through the scratch, from the host (bytes)
+static int string_write(rbx_ctx *c, rbx_name name, int op, int64_t offset, const uint8_t *d_bytes, const uint8_t *bytes,
+                        uint64_t n, uint64_t *new_len, hipStream_t st) {
+    rbx_string_cmd cmd = {};
+    cmd.op = (uint8_t)op;
+    cmd.a = offset;
+    cmd.val_len = (uint32_t)std::min<uint64_t>(n, kStrMax + 1);  // (a value above the limit fails at any offset)
+    if (byte_key_step(0, true, false, cmd).fails == kByteBadOffset) return byte_cmd_failed(kByteBadOffset);
+    const std::string nm = name_of(name);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t L;
+    RBX_TRY(string_len(c, nm, st, &bm, &L));
+    const ByteStep s = byte_run_step(L, !bm, cmd);
+    if (s.fails) return byte_cmd_failed(s.fails);
+    if (new_len) *new_len = (uint64_t)s.reply;
+    if (!s.writes) return RBX_OK;
+    RBX_TRY(bitset_for_write(c, nm, s.len, st, &bm));
+    if (bytes && s.cnt) {
+        RBX_TRY(c->dev->bits.by_bytes.reserve(s.cnt));
+        HIP_TRY(hipMemcpyAsync(c->dev->bits.by_bytes.p, bytes, s.cnt, hipMemcpyHostToDevice, st));
+        d_bytes = c->dev->bits.by_bytes.as<uint8_t>();
+    }
+    launch_bytes_copy((uint8_t *)bm->d_words + s.at, d_bytes, s.cnt, g_tune.bytestream_tile, bm->d_len, s.len, st);
+    HIP_TRY(hipGetLastError());
+    if (bytes) {
+        HIP_TRY(hipStreamSynchronize(st));
+        string_scratch_trim(c);
+    }
+    return RBX_OK;
+}
+
 }  // namespace rbx
 
 using namespace rbx;
@@ -1058,6 +1138,90 @@ int rbx_bitset_field_rule(int op, int is_signed, int size, int overflow, int64_t
     if (field_typed((uint64_t)old, size, is_signed) != old)
         return fail(RBX_E_ILLEGAL_ARGUMENT, "old is outside the type's range");
     *nil = field_rule(op, is_signed ? 1 : 0, size, overflow, old, value, now, reply) ? 1 : 0;
+    return RBX_OK;
+}
+
+int rbx_string_getrange(rbx_ctx *c, rbx_name name, int64_t start, int64_t end, uint8_t *out, uint64_t cap, uint64_t *len) {
+    if (!c || bad_name(name) || (cap && !out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    return string_getrange(c, name, start, end, nullptr, out, out ? cap : 0, len, c->stream);
+}
+
+int rbx_string_getrange_dev(rbx_ctx *c, rbx_name name, int64_t start, int64_t end, uint8_t *d_out, uint64_t cap,
+                            uint64_t *len, void *stream) {
+    if (!c || bad_name(name) || (cap && !d_out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    return string_getrange(c, name, start, end, d_out, nullptr, cap, len, st);
+}
+
+int rbx_string_setrange(rbx_ctx *c, rbx_name name, int64_t offset, const uint8_t *bytes, uint64_t n, uint64_t *new_len) {
+    if (!c || bad_name(name) || (n && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    return string_write(c, name, RBX_STR_SETRANGE, offset, nullptr, n ? bytes : nullptr, n, new_len, c->stream);
+}
+
+int rbx_string_setrange_dev(rbx_ctx *c, rbx_name name, int64_t offset, const uint8_t *d_bytes, uint64_t n,
+                            uint64_t *new_len, void *stream) {
+    if (!c || bad_name(name) || (n && !d_bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    return string_write(c, name, RBX_STR_SETRANGE, offset, d_bytes, nullptr, n, new_len, st);
+}
+
+int rbx_string_append(rbx_ctx *c, rbx_name name, const uint8_t *bytes, uint64_t n, uint64_t *new_len) {
+    if (!c || bad_name(name) || (n && !bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    RBX_ENTER(c, c->stream);
+    return string_write(c, name, RBX_STR_APPEND, 0, nullptr, n ? bytes : nullptr, n, new_len, c->stream);
+}
+
+int rbx_string_append_dev(rbx_ctx *c, rbx_name name, const uint8_t *d_bytes, uint64_t n, uint64_t *new_len, void *stream) {
+    if (!c || bad_name(name) || (n && !d_bytes)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    return string_write(c, name, RBX_STR_APPEND, 0, d_bytes, nullptr, n, new_len, st);
+}
+
+// M/RedissonBinaryStream.java:181-190: STRLEN; if size >= len return; GETRANGE key 0 size-1; SET key that.  The
+// GETRANGE starts at 0, so what it keeps is a prefix: the SET is the string cut in place, what it cuts off cleared.
+int rbx_string_truncate(rbx_ctx *c, rbx_name name, int64_t size) {
+    if (!c || bad_name(name)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    const std::string nm = name_of(name);
+    std::shared_ptr<Bitmap> bm;
+    uint64_t L, lo = 0, hi = 0;
+    RBX_TRY(string_len(c, nm, st, &bm, &L));
+    if (size >= (int64_t)L) return RBX_OK;
+    if (!bm) return bitmap_import(c, nm, nullptr, 0);  // a negative size on a missing key: SET key ""
+    // (size - 1 for the smallest size is clamped; every end below -L gives the empty reply alike)
+    const uint64_t keep = byte_getrange(0, size > INT64_MIN ? size - 1 : INT64_MIN, L, &lo, &hi) ? hi : 0;
+    if (keep < L) HIP_TRY(hipMemsetAsync((uint8_t *)bm->d_words + keep, 0, L - keep, st));
+    launch_bytes_copy(nullptr, nullptr, 0, g_tune.bytestream_tile, bm->d_len, keep, st);
+    HIP_TRY(hipGetLastError());
+    if (Entry *e = c->ks.find(nm)) e->expire_at = -1;  // SET without KEEPTTL
+    HIP_TRY(hipStreamSynchronize(st));
+    return RBX_OK;
+}
+
+int rbx_string_range_of(const uint8_t *bytes, uint64_t len, int missing, const rbx_string_cmd *cmd, const uint8_t *vals,
+                        uint8_t *out, uint64_t cap, int64_t *reply, uint64_t *new_len) {
+    (void)vals;  // a write stores nothing here
+    if (!cmd || !reply) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (cmd->op > RBX_STR_GET) return fail(RBX_E_ILLEGAL_ARGUMENT, "unknown string command");
+    if (len > kStrMax) return fail(RBX_E_ILLEGAL_ARGUMENT, "string exceeds the 512 MiB Redis limit");
+    if (missing) len = 0;
+    *reply = 0;
+    if (new_len) *new_len = len;
+    const ByteStep s = byte_run_step(len, missing != 0, *cmd);
+    if (s.fails) return byte_cmd_failed(s.fails);
+    if (new_len) *new_len = s.len;
+    *reply = s.nil ? -1 : s.reply;
+    if (!s.writes && s.cnt) {
+        const uint64_t wr = std::min(cap, s.cnt);
+        if (!bytes || (wr && !out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+        memcpy(out, bytes + s.at, wr);
+    }
     return RBX_OK;
 }
 

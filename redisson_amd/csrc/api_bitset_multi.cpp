@@ -634,6 +634,185 @@ static int members_stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t
     return stream_names_check(c, names, nkeys);
 }
 
+// ---- GETRANGE / SETRANGE / APPEND / GET over many keys (rbx_string_stream) ----
+enum { kBlShortDone = 0, kBlLongCmds = 1, kBlTiles = 2, kBlRounds = 3 };  // what rbx_bench_bytestream_last shows
+static std::atomic<uint32_t> g_bytestream_last[4];
+static const char *const kStringIllegalMsg =
+    "a command's key is not below nkeys, its op is unknown, or its value leaves the value buffer";
+
+// The key table over the strings as the plan left them: every canonical key a command that ran writes is created or
+// grown to its planned final length, the others are looked up.  When a creation or a growth fails (memory), the keys
+// this call created so far are removed again: the call ran nothing, and leaves no empty string behind.
+static int string_keys_table(rbx_ctx *c, StreamKeys &sk, const ByteKeyState *state, hipStream_t st, const BitKey **d_tab) {
+    const uint32_t *canon = sk.canon();
+    const uint8_t *wrong = sk.wrong();
+    std::vector<BitKey> tab(sk.nkeys);
+    std::vector<uint32_t> created;
+    int rc = RBX_OK;
+    for (uint32_t i = 0; i < sk.nkeys && rc == RBX_OK; ++i) {
+        BitKey &k = tab[i];
+        if (canon[i] != i) {
+            k = tab[canon[i]];
+            continue;
+        }
+        k = BitKey{nullptr, 0, nullptr, wrong[i] ? kBitKeyWrong : 0u, i};
+        if (wrong[i]) continue;
+        std::shared_ptr<Bitmap> bm;
+        if (state[i].flags & kByWritten) {
+            const bool was_missing = c->ks.find(sk.nm[i]) == nullptr;
+            rc = bitset_for_write(c, sk.nm[i], state[i].len, st, &bm);
+            if (rc == RBX_OK && was_missing) created.push_back(i);
+        } else {
+            rc = bitset_find(c, sk.nm[i], &bm);
+        }
+        if (rc == RBX_OK && bm) k = BitKey{bm->d_words, bm->cap_bytes * 8, bm->d_len, 0u, i};
+    }
+    if (rc != RBX_OK) {
+        for (uint32_t i : created) c->ks.erase(sk.nm[i]);
+        return rc;
+    }
+    *d_tab = c->dev->bits.bst_table.sync(tab, st);
+    return *d_tab ? RBX_OK : c->dev->bits.bst_table.err;
+}
+
+// A batch of n > 0 commands over device arrays inside the caller's scope on `st`; d_replies and d_status nullable.
+// d_off (n + 1 words) is always written in full.  The reads go to d_out, or -- the host form, which cannot size its
+// buffer before the plan -- to out_buf, reserved for the total.  *failed = the failure kind of the first command in
+// array order that failed alone; *total_out = off[n]; *over = the reads exceed cap and nothing ran.  Three steps:
+// the plan of every chunk (one wait each; nothing is written), the host's decisions (the caller's errors, total
+// against cap, every written key created or grown once, the table), then per chunk the rounds, and the lengths.
+static int string_stream_run(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_key,
+                             const rbx_string_cmd *d_cmds, uint64_t n, const uint8_t *d_vals, uint64_t vals_len, uint64_t cap,
+                             unsigned long long *d_off, uint8_t *d_out, DevBuf *out_buf, int64_t *d_replies,
+                             uint8_t *d_status, hipStream_t st, int *failed, uint64_t *total_out, bool *over) {
+    *failed = kByteOk;
+    *over = false;
+    if (nkeys == 0) return fail(RBX_E_ILLEGAL_ARGUMENT, kStringIllegalMsg);
+    const uint32_t tile = g_tune.bytestream_tile, short_max = g_tune.bytestream_short_max;
+    const int lanes = g_tune.bytestream_lanes;
+    // one list word hands out a round's list slots and tile numbers: its tiles stay below 2^kRsTileBits
+    const uint64_t chunk = std::min<uint64_t>(g_tune.bytestream_chunk, ((1ULL << kRsTileBits) - 1) / (kStrMax / tile + 2));
+    const bool tiny = n <= g_tune.bytestream_serial_max && n <= chunk;
+    const uint32_t cmax = (uint32_t)std::min(n, chunk);
+    const int key_bits = significant_bits(nkeys);  // cell nkeys: a command that is the caller's error
+    BitsetScratch &b = c->dev->bits;
+    StreamKeys sk(c, names, nkeys);
+    const BitKey *d_tab;
+    bool writes;
+    RBX_TRY(stream_keys_table(c, sk, nullptr, st, &d_tab, &writes));
+    RBX_TRY(b.by_state.reserve((size_t)nkeys * sizeof(ByteKeyState)));
+    RBX_TRY(b.by_plan.reserve(n * 8));
+    RBX_TRY(b.by_sum.reserve((kBySummaryWords + 1) * 8));  // and the offsets' carry
+    RBX_TRY(b.by_runs.reserve((size_t)cmax * 8));  // cursors | heads
+    RBX_TRY(b.by_long.reserve((size_t)cmax * 8));
+    if (!tiny) RBX_TRY(cell_sort_reserve<uint32_t>(b.bst_sort, cmax, 0, key_bits));
+    const size_t pin_bytes = (size_t)nkeys * sizeof(ByteKeyState) + (kBySummaryWords + 1) * 8;
+    RBX_TRY(bg_pin(b.by_pin, pin_bytes));
+    auto *d_state = b.by_state.as<ByteKeyState>();
+    auto *d_plan = b.by_plan.as<unsigned long long>(), *d_sum = b.by_sum.as<unsigned long long>();
+    auto *h_sum = b.by_pin.as<unsigned long long>();  // summary words | total | states
+    auto *h_state = (ByteKeyState *)(h_sum + kBySummaryWords + 1);
+    auto *d_carry = d_sum + kBySummaryWords;  // the yield of the chunks before: the next plan overwrites d_off[i0]
+    HIP_TRY(hipMemsetAsync(d_carry, 0, 8, st));
+    launch_bytestream_state_init(d_tab, nkeys, d_state, st);
+
+    // 1. the plan, chunk by chunk; the running states and the offsets carry across the chunks on the device
+    std::vector<uint32_t> rounds;
+    uint64_t first[kByteKinds] = {~0ULL, ~0ULL, ~0ULL}, stats[4] = {0, 0, 0, 0};
+    bool illegal = false;
+    for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
+        const uint32_t m = (uint32_t)std::min(chunk, n - i0);
+        HIP_TRY(hipMemsetAsync(d_sum, 0xFF, kByteKinds * 8, st));
+        HIP_TRY(hipMemsetAsync(d_sum + kByteKinds, 0, (kBySummaryWords - kByteKinds) * 8, st));
+        int64_t *d_r = d_replies ? d_replies + i0 : nullptr;
+        uint8_t *d_s = d_status ? d_status + i0 : nullptr;
+        if (tiny) {
+            launch_bytestream_plan_serial(d_tab, d_key, d_cmds, m, nkeys, vals_len, short_max, tile, d_state, d_plan, d_off,
+                                          d_r, d_s, d_sum, st);
+        } else {
+            RBX_TRY(sort_failed(launch_bytestream_sort(d_tab, d_key + i0, d_cmds + i0, m, nkeys, vals_len, key_bits, d_sum,
+                                                       b.bst_sort.p, b.bst_sort.cap, st)));
+            RBX_TRY(sort_failed(launch_bytestream_plan(d_tab, d_cmds + i0, m, nkeys, i0, short_max, tile, d_state,
+                                                       d_plan + i0, d_off + i0, d_r, d_s, d_sum, b.bst_sort.p,
+                                                       b.bst_sort.cap, st)));
+        }
+        launch_bits_scan(d_off + i0, m, st);  // d_off[i0 + m] = the chunk's yield
+        if (i0) launch_members_carry(d_off + i0, (uint64_t)m + 1, d_carry, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(d_carry, d_off + i0 + m, 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h_sum, d_sum, kBySummaryWords * 8, hipMemcpyDeviceToHost, st));
+        if (i0 + m == n) {  // the last chunk's wait also brings the total and the keys' final states
+            HIP_TRY(hipMemcpyAsync(h_sum + kBySummaryWords, d_off + n, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(h_state, d_state, (size_t)nkeys * sizeof(ByteKeyState), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));  // the chunk's one wait
+        illegal = illegal || (h_sum[kByFlags] & kRsIllegal);
+        for (int k = 0; k < kByteKinds; ++k) first[k] = std::min<uint64_t>(first[k], h_sum[k]);
+        rounds.push_back(1 + (uint32_t)h_sum[kByMostLong]);
+        stats[kBlLongCmds] += h_sum[kByLongCmds];
+        stats[kBlTiles] += h_sum[kByTiles];
+    }
+    // 2. the host's decisions
+    if (illegal) return fail(RBX_E_ILLEGAL_ARGUMENT, kStringIllegalMsg);
+    const uint64_t total = h_sum[kBySummaryWords];
+    *total_out = total;
+    if (total > cap) {
+        *over = true;
+        return fail(RBX_E_ILLEGAL_ARGUMENT, "the reads yield more bytes than cap: off and total are exact, nothing ran");
+    }
+    if (out_buf && total) {
+        RBX_TRY(out_buf->reserve(total));
+        d_out = out_buf->as<uint8_t>();
+    }
+    std::vector<ByteKeyState> state(h_state, h_state + nkeys);  // (bitset_for_write may wait: the pinned words are reused)
+    RBX_TRY(string_keys_table(c, sk, state.data(), st, &d_tab));
+    // 3. the rounds of every chunk, then the lengths
+    auto *d_cur = b.by_runs.as<uint32_t>(), *d_heads = d_cur + cmax;
+    auto *d_long = b.by_long.as<unsigned long long>();
+    if (tiny && stats[kBlLongCmds] == 0) {
+        launch_bytestream_walk_serial(lanes, d_tab, d_key, d_cmds, d_vals, d_plan, d_off, d_out, (uint32_t)n, st);
+        stats[kBlRounds] = 1;
+    } else {
+        RBX_TRY(cell_sort_reserve<uint32_t>(b.bst_sort, cmax, 0, key_bits));
+        size_t ci = 0;
+        for (uint64_t i0 = 0; i0 < n; i0 += chunk, ++ci) {
+            const uint32_t m = (uint32_t)std::min(chunk, n - i0);
+            if (tiny || n > chunk)  // the scratch holds another chunk's pairs, or none
+                RBX_TRY(sort_failed(launch_bytestream_sort(d_tab, d_key + i0, d_cmds + i0, m, nkeys, vals_len, key_bits, d_sum,
+                                                           b.bst_sort.p, b.bst_sort.cap, st)));
+            HIP_TRY(hipMemsetAsync(d_sum + kByHeads, 0, 8, st));
+            RBX_TRY(sort_failed(launch_bytestream_heads(m, nkeys, d_cur, d_heads, d_sum + kByHeads, b.bst_sort.p,
+                                                        b.bst_sort.cap, st)));
+            for (uint32_t r = 0; r < rounds[ci]; ++r) {
+                HIP_TRY(hipMemsetAsync(d_sum + kByList, 0, 8, st));
+                RBX_TRY(sort_failed(launch_bytestream_walk(lanes, d_tab, d_cmds + i0, d_vals, d_plan + i0, d_off + i0, d_out, m,
+                                                           d_cur, d_heads, d_sum + kByHeads, tile, d_sum + kByList, d_long,
+                                                           b.bst_sort.p, b.bst_sort.cap, st)));
+                if (r + 1 < rounds[ci])  // (the last round walks what lies behind every key's last long command)
+                    launch_bytestream_tiles(d_tab, d_key + i0, d_cmds + i0, d_vals, d_plan + i0, d_off + i0, d_out, tile,
+                                            d_sum + kByList, d_long, st);
+            }
+            stats[kBlRounds] += rounds[ci];
+        }
+    }
+    launch_bytestream_lengths(d_tab, d_state, nkeys, st);
+    HIP_TRY(hipGetLastError());
+    stats[kBlShortDone] = n - stats[kBlLongCmds];
+    for (int i = 0; i < 4; ++i) g_bytestream_last[i] = (uint32_t)std::min<uint64_t>(stats[i], 0xFFFFFFFFu);
+    uint64_t at = ~0ULL;
+    for (int k = 0; k < kByteKinds; ++k)
+        if (first[k] < at) at = first[k], *failed = k + 1;
+    return RBX_OK;
+}
+
+static int string_stream_args_check(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, uint64_t n, const void *key,
+                                    const void *cmds, const void *vals, uint64_t vals_len, const void *off, const void *out,
+                                    uint64_t cap) {
+    if ((n && (!key || !cmds)) || !off || (vals_len && !vals) || (cap && !out)) return fail(RBX_E_ILLEGAL_ARGUMENT, "NULL argument");
+    if (n > (1ULL << 32)) return fail(RBX_E_ILLEGAL_ARGUMENT, "a batch takes at most 2^32 commands");
+    return stream_names_check(c, names, nkeys);
+}
+
 }  // namespace rbx
 
 using namespace rbx;
@@ -843,5 +1022,71 @@ int rbx_bitset_members_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys,
 }
 
 int rbx_bench_members_last(uint32_t out[4]) { return last_show(g_members_last, out); }
+
+int rbx_string_stream_dev(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *d_cmd_key,
+                          const rbx_string_cmd *d_cmds, uint64_t n, const uint8_t *d_vals, uint64_t vals_len, uint64_t cap,
+                          uint64_t *d_off, uint8_t *d_out, int64_t *d_replies, uint8_t *d_status, uint64_t *total,
+                          void *stream) {
+    RBX_TRY(string_stream_args_check(c, names, nkeys, n, d_cmd_key, d_cmds, d_vals, vals_len, d_off, d_out, cap));
+    if (total) *total = 0;
+    hipStream_t st = pick_stream(c, stream);
+    RBX_ENTER(c, st);
+    if (n == 0) {  // no command is sent
+        HIP_TRY(hipMemsetAsync(d_off, 0, 8, st));
+        return RBX_OK;
+    }
+    int failed;
+    uint64_t tot = 0;
+    bool over;
+    const int rc = string_stream_run(c, names, nkeys, d_cmd_key, d_cmds, n, d_vals, vals_len, cap, (unsigned long long *)d_off,
+                                     d_out, nullptr, d_replies, d_status, st, &failed, &tot, &over);
+    if (total) *total = tot;
+    RBX_TRY(rc);
+    return byte_cmd_failed(failed);
+}
+
+int rbx_string_stream(rbx_ctx *c, const rbx_name *names, uint32_t nkeys, const uint32_t *cmd_key, const rbx_string_cmd *cmds,
+                      uint64_t n, const uint8_t *vals, uint64_t vals_len, uint64_t cap, uint64_t *off, uint8_t *out,
+                      int64_t *replies, uint8_t *status, uint64_t *total) {
+    RBX_TRY(string_stream_args_check(c, names, nkeys, n, cmd_key, cmds, vals, vals_len, off, out, cap));
+    if (total) *total = 0;
+    off[0] = 0;
+    if (n == 0) return RBX_OK;
+    for (uint64_t i = 0; i < n; ++i)  // the caller's errors, before any device work
+        if (cmd_key[i] >= nkeys || byte_cmd_illegal(cmds[i], vals_len)) return fail(RBX_E_ILLEGAL_ARGUMENT, kStringIllegalMsg);
+    hipStream_t st = c->stream;
+    RBX_ENTER(c, st);
+    BitsetScratch &b = c->dev->bits;
+    RBX_TRY(b.by_cmds.reserve(n * (sizeof(rbx_string_cmd) + 4)));  // commands | keys
+    RBX_TRY(b.by_vals.reserve(vals_len));
+    RBX_TRY(b.by_off.reserve((n + 1) * 8));
+    RBX_TRY(b.by_replies.reserve(n * 9));  // replies | status
+    rbx_string_cmd *d_cmds = b.by_cmds.as<rbx_string_cmd>();
+    uint32_t *d_key = (uint32_t *)(d_cmds + n);
+    auto *d_off = b.by_off.as<unsigned long long>();
+    int64_t *d_replies = b.by_replies.as<int64_t>();
+    uint8_t *d_status = (uint8_t *)(d_replies + n);
+    HIP_TRY(hipMemcpyAsync(d_cmds, cmds, n * sizeof(rbx_string_cmd), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_key, cmd_key, n * 4, hipMemcpyHostToDevice, st));
+    if (vals_len) HIP_TRY(hipMemcpyAsync(b.by_vals.p, vals, vals_len, hipMemcpyHostToDevice, st));
+    int failed;
+    uint64_t tot = 0;
+    bool over;
+    const int rc = string_stream_run(c, names, nkeys, d_key, d_cmds, n, b.by_vals.as<uint8_t>(), vals_len, cap, d_off, nullptr,
+                                     &b.by_out, replies ? d_replies : nullptr, status ? d_status : nullptr, st, &failed, &tot,
+                                     &over);
+    if (total) *total = tot;
+    if (rc != RBX_OK && !over) return rc;
+    HIP_TRY(hipMemcpyAsync(off, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (rc == RBX_OK) {
+        if (tot) HIP_TRY(hipMemcpyAsync(out, b.by_out.p, tot, hipMemcpyDeviceToHost, st));
+        if (replies) HIP_TRY(hipMemcpyAsync(replies, d_replies, n * 8, hipMemcpyDeviceToHost, st));
+        if (status) HIP_TRY(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc != RBX_OK ? rc : byte_cmd_failed(failed);
+}
+
+int rbx_bench_bytestream_last(uint32_t out[4]) { return last_show(g_bytestream_last, out); }
 
 }  // extern "C"

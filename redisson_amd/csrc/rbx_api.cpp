@@ -347,6 +347,11 @@ static const TuneRow kTuneRows[] = {
     {"members_short_max", POW2(64, 1 << 20), false, FIELD(members_short_max)},
     {"members_tile", POW2(4096, 1 << 20), false, FIELD(members_tile)},
     {"members_chunk", RANGE(1, 1 << 30), false, FIELD(members_chunk)},
+    {"bytestream_lanes", ONE_OF(4, 8, 16, 32, 64), false, FIELD(bytestream_lanes)},
+    {"bytestream_short_max", POW2(64, 1 << 20), false, FIELD(bytestream_short_max)},
+    {"bytestream_tile", POW2(4096, 1 << 20), false, FIELD(bytestream_tile)},
+    {"bytestream_chunk", RANGE(1, 1 << 30), false, FIELD(bytestream_chunk)},  // positions in a chunk are 30-bit
+    {"bytestream_serial_max", RANGE(0, kIntMax), false, FIELD(bytestream_serial_max)},
 };
 #undef RANGE
 #undef ONE_OF

@@ -409,6 +409,12 @@ struct BitsetScratch {
     // the enumeration over many keys (rbx_bitset_members_stream) shares bst_table, rs_cmds (commands | keys), rs_out
     // (the host form's offsets), rs_status, rs_sum and rs_long with the range stream; its own: the tiles' counts
     DevBuf mem_tiles;
+    // the byte commands (rbx_string_*).  The single calls: the host forms' bytes on the device.  The
+    // stream shares bst_table and bst_sort (the sorted pairs); its own: the keys' running states, the plan words (8
+    // bytes per command of the call), the summary words, a chunk's cursors | run list and its long list, the host
+    // form's commands | keys, values, offsets, replies | status and read bytes, and where states and total come back to
+    DevBuf by_bytes, by_state, by_plan, by_sum, by_runs, by_long, by_cmds, by_vals, by_off, by_replies, by_out;
+    PinBuf by_pin;
 };
 
 // Buffers more than one subsystem uses; one call at a time holds them (CallScope orders the calls).
@@ -617,6 +623,7 @@ int bitcount_locked(rbx_ctx *c, const std::string &name, uint64_t *out);
 // api_bitset.cpp
 int bitset_find(rbx_ctx *c, const std::string &name, std::shared_ptr<Bitmap> *out);
 int bitset_for_write(rbx_ctx *c, const std::string &name, uint64_t need_bytes, hipStream_t st, std::shared_ptr<Bitmap> *out);
+int byte_cmd_failed(int kind);
 // api_hll.cpp
 int hll_add_multi(rbx_ctx *c, const std::vector<std::string> &names, const uint64_t *seg_offsets,
                   const rbx_keys *elements, uint8_t *out_changed);

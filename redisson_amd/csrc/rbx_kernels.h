@@ -11,6 +11,7 @@
 #include "bk_entry.h"
 #include "rbx_device.h"
 #include "range_cmd.h"  // after rbx_device.h: it keeps an RBX_HD that is already defined
+#include "byte_cmd.h"
 
 namespace rbx {
 
@@ -537,6 +538,66 @@ void launch_rangestream_short(int lanes, const BitKey *d_tab, const uint32_t *d_
 void launch_rangestream_tiles(const BitKey *d_tab, const uint32_t *d_key, const rbx_range_cmd *d_cmds,
                               uint32_t tile_bytes, const unsigned long long *d_long, uint32_t nlong, uint64_t ntiles,
                               int64_t *d_replies, hipStream_t st);
+
+// ---- bytestream_kernels.hip
+// GETRANGE / SETRANGE / APPEND / GET over many strings (rbx_string_stream): command i is (key[i],
+// cmds[i]), the strings are reached through the BitKey table above, byte_cmd.h has the rules.
+// A key's running state through the plan: its length, whether it exists now and whether a command that runs writes
+// it (the host creates or grows it to `len`; the lengths kernel stores `len`); nlong is the serial plan's own.
+struct ByteKeyState {
+    unsigned long long len;
+    uint32_t flags, nlong;
+};
+constexpr uint32_t kByExists = 1, kByWritten = 2;
+// The summary words (u64) of one chunk: the first position per failure kind (kByte* - 1; preset to ~0, the others to
+// 0), the flags (kRsIllegal), the chunk's long commands, their tiles, the most long commands on one key; then two
+// words the rounds use: the round's list word (long commands << kRsTileBits | tiles) and the number of runs.
+enum { kByFlags = kByteKinds, kByLongCmds, kByTiles, kByMostLong, kByList, kByHeads, kBySummaryWords };
+// the single calls: cnt bytes from src to dst in tiles over the grid, then *d_len (nullable) = new_len
+void launch_bytes_copy(uint8_t *dst, const uint8_t *src, uint64_t cnt, uint32_t tile_bytes, unsigned long long *d_len,
+                       uint64_t new_len, hipStream_t st);
+// d_state[i] = canonical key i's length and existence (nkeys entries)
+void launch_bytestream_state_init(const BitKey *d_tab, uint32_t nkeys, ByteKeyState *d_state, hipStream_t st);
+// The chunk's m <= 2^30 commands sorted by canonical key into the scratch (cell_sort_scratch_bytes<uint32_t>(m, 0,
+// key_bits), key_bits = the significant bits of nkeys: a command that is the caller's error takes cell nkeys and
+// sets kRsIllegal).  The three launchers below read the sorted pairs from the same scratch.  0 or a hipError_t.
+int launch_bytestream_sort(const BitKey *d_tab, const uint32_t *d_key, const rbx_string_cmd *d_cmds, uint32_t m,
+                           uint32_t nkeys, uint64_t vals_len, int key_bits, unsigned long long *d_sum, void *d_scratch,
+                           size_t scratch_bytes, hipStream_t st);
+// One lane per key's run plans it from d_state: d_plan / d_yield (the bytes a read yields, for the scan) / d_replies /
+// d_status (nullable) are the chunk's slices, i0 its first position in the call.  Nothing is written to a string.
+int launch_bytestream_plan(const BitKey *d_tab, const rbx_string_cmd *d_cmds, uint32_t m, uint32_t nkeys, uint64_t i0,
+                           uint32_t short_max, uint32_t tile_bytes, ByteKeyState *d_state, unsigned long long *d_plan,
+                           unsigned long long *d_yield, int64_t *d_replies, uint8_t *d_status, unsigned long long *d_sum,
+                           void *d_scratch, size_t scratch_bytes, hipStream_t st);
+// the same for a whole call of few commands in array order, one lane, without the sort
+void launch_bytestream_plan_serial(const BitKey *d_tab, const uint32_t *d_key, const rbx_string_cmd *d_cmds, uint32_t m,
+                                   uint32_t nkeys, uint64_t vals_len, uint32_t short_max, uint32_t tile_bytes,
+                                   ByteKeyState *d_state, unsigned long long *d_plan, unsigned long long *d_yield,
+                                   int64_t *d_replies, uint8_t *d_status, unsigned long long *d_sum, hipStream_t st);
+// the runs of the sorted chunk: d_cur (m entries) gets each head's cursor, d_heads (m entries) the heads, *d_nheads
+// (zeroed by the caller) their number
+int launch_bytestream_heads(uint32_t m, uint32_t nkeys, uint32_t *d_cur, uint32_t *d_heads, unsigned long long *d_nheads,
+                            void *d_scratch, size_t scratch_bytes, hipStream_t st);
+// One round's walk: a group of `lanes` lanes per run executes its short commands from the cursor and lists its next
+// long one in d_long (m entries) through *d_list (zeroed by the caller).  d_cmds / d_plan / d_off are the chunk's
+// slices; d_off holds the final offsets into d_out.
+int launch_bytestream_walk(int lanes, const BitKey *d_tab, const rbx_string_cmd *d_cmds, const uint8_t *d_vals,
+                           const unsigned long long *d_plan, const unsigned long long *d_off, uint8_t *d_out, uint32_t m,
+                           uint32_t *d_cur, const uint32_t *d_heads, const unsigned long long *d_nheads,
+                           uint32_t tile_bytes, unsigned long long *d_list, unsigned long long *d_long, void *d_scratch,
+                           size_t scratch_bytes, hipStream_t st);
+// a whole call of few commands, none of them long, in array order by one group
+void launch_bytestream_walk_serial(int lanes, const BitKey *d_tab, const uint32_t *d_key, const rbx_string_cmd *d_cmds,
+                                   const uint8_t *d_vals, const unsigned long long *d_plan, const unsigned long long *d_off,
+                                   uint8_t *d_out, uint32_t m, hipStream_t st);
+// the tiles of the commands the walk just listed, swept by the whole grid (the list word is read on the device)
+void launch_bytestream_tiles(const BitKey *d_tab, const uint32_t *d_key, const rbx_string_cmd *d_cmds, const uint8_t *d_vals,
+                             const unsigned long long *d_plan, const unsigned long long *d_off, uint8_t *d_out,
+                             uint32_t tile_bytes, const unsigned long long *d_list, const unsigned long long *d_long,
+                             hipStream_t st);
+// *len = the planned final length for every key a command that ran writes
+void launch_bytestream_lengths(const BitKey *d_tab, const ByteKeyState *d_state, uint32_t nkeys, hipStream_t st);
 
 // ---- fieldstream_kernels.hip
 // The ordered stream of single-sub-command BITFIELDs over many strings (rbx_bitset_field_stream, DESIGN

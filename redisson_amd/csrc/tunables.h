@@ -178,6 +178,24 @@ struct Tunables {
     // "members_chunk": commands per chunk, 1 .. 2^30 (8 bytes of long list per command of a chunk; each chunk has its
     // own summary and wait, and the offsets carry across chunks on the device).  2^25 is the range stream's: not measured.
     std::atomic<uint64_t> members_chunk{1 << 25};
+
+    // ---- GETRANGE / SETRANGE / APPEND / GET over many keys (api_bitset_multi.cpp) ----
+    // The five knobs of rbx_string_stream.  All exact.  Every default is the range stream's (the serial one the bit
+    // stream's), taken over.  Measured (DESIGN 11.12 row d): on 100,000 keys of 46 bytes the five lane widths
+    // lie within 2 % (the call is host-bound there), so 16 is kept; the other four are NOT measured.
+    // "bytestream_lanes": the lanes G of the group that executes one key's commands, 4, 8, 16, 32 or 64
+    std::atomic<int> bytestream_lanes{16};
+    // "bytestream_short_max": the bytes of the longest command a lane group moves alone, a power of two in 64 .. 1 MiB;
+    // a longer one is cut into tiles for the whole device
+    std::atomic<uint32_t> bytestream_short_max{4096};
+    // "bytestream_tile": the bytes of a tile of a long command (and of a single call), a power of two in 4 KiB .. 1 MiB
+    std::atomic<uint32_t> bytestream_tile{65536};
+    // "bytestream_chunk": commands per chunk, 1 .. 2^30 (12 bytes of sort scratch plus 16 of cursor, run list and long
+    // list per command of a chunk; each chunk has its own summary and wait)
+    std::atomic<uint64_t> bytestream_chunk{1 << 25};
+    // "bytestream_serial_max": the largest call that one lane group runs in array order without the sort (when none
+    // of its commands is long)
+    std::atomic<uint64_t> bytestream_serial_max{64};
 };
 
 constexpr uint32_t kHllGroupsFillBlocks = 256;

@@ -9,7 +9,8 @@ StringCodec pass the bytes through), PFADD's integer reply as a Long.
 The bit commands mirror redisson-spring-data-31's RedissonConnection (S/ = redisson-spring-data/
 redisson-spring-data-31/src/main/java/org/redisson/spring/data/connection/RedissonConnection.java): getBit /
 setBit S:628-636, bitCount S:638-646, bitOp S:650-661, strLen S:663-666, bitField S:2241-2291,
-bitPos S:2337-2359.
+bitPos S:2337-2359.  The byte-level commands on the same strings sit directly above them: get S:487, mGet S:499,
+set S:506, append S:610, getRange S:617, setRange S:624.
 
 Keys are binary-safe: they travel as (bytes, length) pairs through the *_n entry points
 (rbx_hll_add_multi_n / rbx_hll_count_n / rbx_hll_merge_n), so a key may hold any byte, zero
@@ -25,7 +26,8 @@ import numpy as np
 from . import _lib as L
 from .client import (GETBIT, PFADD, PFCOUNT, SETBIT0, SETBIT1, RedissonClient, _bit_index, _check, _Queued, _range_row,
                      bitset_field_stream_call, bitset_op_groups_call, bitset_range_stream_call, bitset_stream_call,
-                     hll_count_groups_call, hll_merge_groups_call, hll_stream_call, run_queue)
+                     hll_count_groups_call, hll_merge_groups_call, hll_stream_call, run_queue, STRING_FAILED, STRING_NIL,
+                     string_append, string_failure, string_getrange, string_setrange, string_stream_call, _u8)
 from .exceptions import IllegalArgumentException, UnsupportedOperationException
 from .keys import Arena
 
@@ -206,7 +208,30 @@ def _bit_pos_range(key, bit, range=(None, None)):  # noqa: A002
                            L.RBX_RANGE_BYTE), None
 
 
-def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=None, rng=None):
+def _string_get(key):
+    """(key, row, convert) of a pipelined get: the bytes, None for a missing key"""
+    return key, (L.RBX_STR_GET, 0, 0, b""), lambda _n, data, status: None if status == STRING_NIL else data
+
+
+def _string_get_range(key, start, end):
+    return key, (L.RBX_STR_GETRANGE, int(start), int(end), b""), lambda _n, data, _status: data
+
+
+def _string_set_range(key, value, offset):
+    """setRange is void (S:624-627)"""
+    return key, (L.RBX_STR_SETRANGE, _int64(offset), 0, bytes(value)), lambda _n, _data, _status: None
+
+
+def _string_append(key, value):
+    return key, (L.RBX_STR_APPEND, 0, 0, bytes(value)), lambda n, _data, _status: n
+
+
+def _int64(v) -> int:
+    """a Java long; what lies outside is as wrong as its nearest end"""
+    return max(-(1 << 63), min((1 << 63) - 1, int(v)))
+
+
+def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=None, rng=None, string=None):
     """A command method of RedissonConnection: while a pipeline is open it queues itself and returns None
     (the result comes back from closePipeline); bit = (key, op, index) of a GETBIT / SETBIT, which travels with
     its neighbours in one rbx_bitset_stream call; field = (key, row, convert) of a BITFIELD with one sub-command
@@ -217,7 +242,9 @@ def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=Non
     rbx_hll_count_groups / rbx_hll_merge_groups call; bitop = ((RBX_BITOP_*, destination or None, sources), convert)
     of a BITOP or a whole-string BITCOUNT (or None for any other), which travels with its like in one
     rbx_bitset_op_groups call; rng = (key, row, convert) of a read query (BITCOUNT, BITPOS, STRLEN; or None for any
-    other), which travels with its like in one rbx_bitset_range_stream call -- a whole-string BITCOUNT carries both."""
+    other), which travels with its like in one rbx_bitset_range_stream call -- a whole-string BITCOUNT carries both;
+    string = (key, row, convert) of a GET / GETRANGE / SETRANGE / APPEND, which travels with its like in one
+    rbx_string_stream call."""
 
     def wrap(f):
         @functools.wraps(f)
@@ -229,6 +256,13 @@ def _pipelined(fn=None, *, bit=None, field=None, hll=None, group=None, bitop=Non
                 self._pipeline.append(_Queued(_key(key), op, _bit_index(index)))
                 return None
             single = lambda: f(self, *args, **kwargs)  # noqa: E731
+            if string is not None:
+                try:
+                    key, row, convert = string(*args, **kwargs)
+                    self._pipeline.append(_Queued(_key(key), fn=single, string=row, convert=convert))
+                except (IllegalArgumentException, TypeError, ValueError):
+                    self._pipeline.append(_Queued(fn=single))  # the single call raises it at its position
+                return None
             query = None
             if rng is not None:
                 try:
@@ -302,7 +336,9 @@ class RedissonConnection:
         two or more keys are one rbx_hll_count_groups call, consecutive pfMerge commands one rbx_hll_merge_groups
         call.  Consecutive bitOp and bitCount(key) commands, over any keys, are one rbx_bitset_op_groups call;
         consecutive bitCount(key, begin, end), bitPos and strLen commands one rbx_bitset_range_stream call, which a
-        bitCount(key) behind them joins.  Every command runs; then the first failure is raised."""
+        bitCount(key) behind them joins.  Consecutive get / getRange / setRange / append commands, over any keys, are
+        one rbx_string_stream call; set runs singly at its position.  Every command runs; then the first failure is
+        raised."""
         if self._pipeline is None:
             return []
         queue, self._pipeline = self._pipeline, None
@@ -312,7 +348,9 @@ class RedissonConnection:
                                    lambda *a: hll_count_groups_call(self._client, *a),
                                    lambda *a: hll_merge_groups_call(self._client, *a),
                                    lambda *a: bitset_op_groups_call(self._client, *a),
-                                   lambda *a: bitset_range_stream_call(self._client, *a))
+                                   lambda *a: bitset_range_stream_call(self._client, *a),
+                                   string_stream_call=lambda *a: string_stream_call(self._client, *a)[:6],
+                                   string_failure=lambda *a: string_failure(self._client, *a))
         if error is not None:
             raise error
         return results
@@ -350,6 +388,66 @@ class RedissonConnection:
         srcs, keep = L.names_array([_key(k) for k in sourceKeys])
         dest, keep_d = L.name_struct(_key(destinationKey))
         _check(L.lib().rbx_hll_merge_n(self._client.ctx, dest, srcs, len(sourceKeys)))
+
+    # ---- byte-level commands on strings (rbx_string_*, binary names) ---------------------------
+    def _string_one(self, key, row):
+        """one command through rbx_string_stream: (number, bytes, status); raises what the command fails with"""
+        rc, msg, replies, status, off, out = string_stream_call(self._client, [_key(key)], [0], [row])
+        if rc != L.RBX_OK:
+            if rc in (L.RBX_E_REDIS, L.RBX_E_WRONGTYPE) and int(status[0]) == STRING_FAILED:
+                raise string_failure(self._client, _key(key), row)
+            _check(rc)
+        return int(replies[0]), out, int(status[0])
+
+    @_pipelined(string=_string_get)
+    def get(self, key: bytes):
+        """GET key -> the bytes, None for a missing key  S:487-490"""
+        _n, data, status = self._string_one(key, (L.RBX_STR_GET, 0, 0, b""))
+        return None if status == STRING_NIL else data
+
+    @_pipelined
+    def set(self, key: bytes, value: bytes) -> bool:  # noqa: A003
+        """SET key value  S:506-509: replaces the key whatever it held and drops its timeout"""
+        nm, _keep = L.name_struct(_key(key))
+        ptr, n, _buf = _u8(value)
+        _check(L.lib().rbx_bitset_import_n(self._client.ctx, nm, ptr, n))
+        return True
+
+    def mGet(self, *keys: bytes) -> list:
+        """MGET k1..kn  S:499-503: one rbx_string_stream call of GETs; a missing key and a key of another type are
+        None, and nothing is raised for them.  While pipelined it queues itself as one command."""
+        def run():
+            ks = [_key(k) for k in keys]
+            if not ks:
+                return []
+            rc, msg, _r, status, off, out = string_stream_call(self._client, ks, list(range(len(ks))),
+                                                               [(L.RBX_STR_GET, 0, 0, b"")] * len(ks))
+            if rc not in (L.RBX_OK, L.RBX_E_WRONGTYPE):
+                _check(rc)
+            return [out[int(off[i]): int(off[i + 1])] if int(status[i]) == 0 else None for i in range(len(ks))]
+        if self._pipeline is not None:
+            self._pipeline.append(_Queued(fn=run))
+            return None
+        return run()
+
+    @_pipelined(string=_string_append)
+    def append(self, key: bytes, value: bytes) -> int:
+        """APPEND key value -> the new length  S:610-614"""
+        return string_append(self._client, _key(key), value)
+
+    @_pipelined(string=_string_get_range)
+    def getRange(self, key: bytes, start: int, end: int) -> bytes:
+        """GETRANGE key start end  S:617-621"""
+        return string_getrange(self._client, _key(key), _int64(start), _int64(end))
+
+    @_pipelined(string=_string_set_range)
+    def setRange(self, key: bytes, value: bytes, offset: int) -> None:
+        """SETRANGE key offset value  S:624-627 (void)"""
+        string_setrange(self._client, _key(key), _int64(offset), value)
+
+    m_get = mGet
+    get_range = getRange
+    set_range = setRange
 
     # ---- bit commands on strings (rbx_bitset_*, binary names) ---------------------------------
     @_pipelined(bit=lambda key, offset: (key, GETBIT, offset))
